@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X-native Wan2.1 denoising path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One *step* = one classifier-free-guided denoising step of the 50-step sampler
@@ -12,8 +12,18 @@ update (text2video.py:243-252), all inputs resident in HBM, synthetic data,
 random-init weights of the real architecture.  Each rank runs its own replica
 on its own clip (inference shards by clip, no data-path collective:
 "scaling": "weak"); `value` = steps of all ranks / max-over-ranks time.
+Past the sampler's 50 steps the next step begins a new sample from the same
+noise, so K + W may exceed 50.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR: after the timed steps, rank 0 writes the latent its last
+timed step returned to DIR/latent.npy (float32; the inputs are seeded, so two
+builds can be compared output for output).
+--full: everything else as well — the in-situ per-kernel timings, telemetry
+and the objects below, the VAE / single-frame / encoder / training legs, and
+the full record in a side file the line names.
+
+Extra objects on the JSON line (--full):
   roofline      dominant kernel (self-attention flash kernel): algorithmic
                 FLOPs per launch / average launch duration measured with HIP
                 events on the launch stream over the timed region, vs the
@@ -741,7 +751,14 @@ def main():
                          "self-attention, comparable across rounds) or as one batch-2 forward as WanT2V.generate does "
                          "(bit-identical; measured 560.0 vs 561.6 ms per step at S = 32760, 16.2 vs 22.6 ms at S = 1560)")
     ap.add_argument("--only-train", action="store_true", help="profiling aid: run just the training leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the latent the last timed step returned to DIR/latent.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: in-situ kernel timings and roofline, telemetry, the VAE, "
+                         "single-frame, encoder, CPU-baseline and training legs, and the side file with the full record")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py --steps must be at least 1")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: no HIP device visible (there is no CPU fallback)")
@@ -823,7 +840,6 @@ def main():
     # --cfg batched: cond and uncond forward of a step as ONE forward on a batch of two (what WanT2V.generate does;
     # bit-identical to two calls, pipeline tests)
     nb = 2 if args.cfg == "batched" else 1
-    timer = KernelTimer(ops, "flash_attn_raw", lambda *a, **k: a[7] == a[8] and a[7] == seq_len)  # Lq == Lk == S
     # secondary in-situ timings: the widest GEMM (FFN up-projection + GELU) and the HBM-bound LN+modulate pass
     # every GEMM shape of a DiT block at M = S, by (M, N, K, epilogue, gated?) — the argument order of ops.gemm_raw is
     # (A, B, C, M, N, K, lda, ldb, ldc, epilogue, ...); the V^T projection runs with swapped operands (M = d, N = S)
@@ -846,9 +862,13 @@ def main():
                 return "o_proj_gate_resid" if k.get("gate0") is not None else "cross_o_proj_resid"
             return "cross_q_proj"
         return None
-    gemm_timer = BucketTimer(ops, "gemm_raw", gemm_bucket)
-    cross_timer = KernelTimer(ops, "flash_attn_raw", lambda *a, **k: a[7] == seq_len and a[8] != seq_len)
-    ln_timer = KernelTimer(ops, "layernorm_modulate_raw", lambda *a, **k: a[2] == nb * seq_len and a[3] == 1536)
+    timers = []
+    if args.full:
+        timer = KernelTimer(ops, "flash_attn_raw", lambda *a, **k: a[7] == a[8] and a[7] == seq_len)  # Lq == Lk == S
+        gemm_timer = BucketTimer(ops, "gemm_raw", gemm_bucket)
+        cross_timer = KernelTimer(ops, "flash_attn_raw", lambda *a, **k: a[7] == seq_len and a[8] != seq_len)
+        ln_timer = KernelTimer(ops, "layernorm_modulate_raw", lambda *a, **k: a[2] == nb * seq_len and a[3] == 1536)
+        timers = [timer, gemm_timer, cross_timer, ln_timer]
 
     # as WanT2V.generate does: what depends on the prompt alone is computed once per sample, not per forward
     st_c, st_u = model.encode_context([ctx]), model.encode_context([ctx_null])
@@ -856,6 +876,8 @@ def main():
 
     def run_steps(n, sched, x):
         for i in range(n):
+            if sched.step_index == len(sched.timesteps):       # the sample is complete: the next step begins a new one
+                sched, x = fresh_sched(), latent
             t = sched.timesteps[sched.step_index or 0].reshape(1).to(device)
             if split is not None:
                 c, u = split.exchange(model([x], t, st_c if split.runs_conditional else st_u, seq_len)[0])
@@ -868,7 +890,7 @@ def main():
                 c = model([x], t, st_c, seq_len)[0]
                 u = model([x], t, st_u, seq_len)[0]
             x = sched.step_cfg(c, u, guide, x)
-        return x
+        return sched, x
 
     def fresh_sched():
         s = sched_mod.FlowUniPCMultistepScheduler(num_train_timesteps=1000, shift=1, use_dynamic_shifting=False)
@@ -880,26 +902,32 @@ def main():
         res_ = {"train": train_legs(model, device, world, dist)}
         emit(json.dumps(res_) if rank == 0 else None)          # (a profiling aid, not the driver's line: the full record)
         return
-    sched = fresh_sched()
-    x = run_steps(args.warmup, sched, latent)
+    sched, x = run_steps(args.warmup, fresh_sched(), latent)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.enabled = gemm_timer.enabled = ln_timer.enabled = cross_timer.enabled = True
-    tele = Telemetry(local_rank)
-    tele.start()
+    for tm in timers:
+        tm.enabled = True
+    tele = Telemetry(local_rank) if args.full else None
+    if tele is not None:
+        tele.start()
     t0 = time.perf_counter()
-    x = run_steps(args.steps, sched, x)
+    sched, x = run_steps(args.steps, sched, x)
     torch.cuda.synchronize()
-    telemetry = tele.stop()
+    telemetry = tele.stop() if tele is not None else None
     torch.cuda.synchronize()
     own_elapsed = time.perf_counter() - t0
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    timer.enabled = gemm_timer.enabled = ln_timer.enabled = cross_timer.enabled = False
+    for tm in timers:
+        tm.enabled = False
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latent.npy"), x.float().cpu().numpy())
     per_rank_ms = None
     if dist:
         # every rank's own time for the K steps (before the closing barrier): the first real multi-GPU run explains
@@ -925,7 +953,7 @@ def main():
         - 2 * 512 * (4096 * 1536 + 1536 * 1536)
     if args.cfg == "two":          # forward_cfg_pair: block 0's self-attention sub-layer once per PAIR of forwards
         executed_flops -= 0.5 * (8.0 * seq_len * 1536 * 1536 + 4.0 * seq_len * seq_len * 1536)
-    attn_ms = timer.avg_ms()
+    attn_ms = timer.avg_ms() if args.full else None
     attn_flops = 4.0 * seq_len * seq_len * 1536 * nb             # one launch covers the batch
     roofline = None
     if attn_ms:
@@ -969,7 +997,7 @@ def main():
             roofline["mfma_sustained_note"] = "probe failed: %r" % (ex,)
 
     secondary = {}
-    l_ms = ln_timer.avg_ms()
+    l_ms = ln_timer.avg_ms() if args.full else None
     # the GEMM shapes of a block at M = S, each timed in situ (HIP events on the launch stream, every launch of the
     # timed steps): flops = 2 M N K, fraction of the 2.5 PFLOP/s dense bf16 MFMA peak
     shapes = {"qkv_proj_fused": (seq_len, 3 * DM, DM, "q|k|v projection + bias in ONE launch per clip (OMH_EPI_BF16_SPLIT_T): q|k bf16, V^T transposed"),
@@ -982,7 +1010,7 @@ def main():
               "ffn_down_gate_resid": (MS, DM, FF, "x += (u W2^T + b) * gate")}
     tot_f = tot_ms = five_f = five_ms = 0.0
     for name, (M_, N_, K_, what) in shapes.items():
-        ms_ = gemm_timer.avg_ms(name)
+        ms_ = gemm_timer.avg_ms(name) if args.full else None
         if not ms_:
             continue
         gf = 2.0 * M_ * N_ * K_
@@ -1001,7 +1029,7 @@ def main():
                                     "each per block)",
                           "tflop_per_block": round(five_f / 1e12, 3), "ms_per_block": round(five_ms, 4),
                           "with_cross_attention_projections_frac": round(tot_f / tot_ms / 1e9 / PEAK_BF16_TFLOPS, 4)}
-    c_ms = cross_timer.avg_ms()
+    c_ms = cross_timer.avg_ms() if args.full else None
     if c_ms:      # cross-attention launch: S queries x (un-padded) context keys, 12 heads, D = 128
         lk = 0.5 * (ctx.shape[0] + ctx_null.shape[0])
         cf = 4.0 * nb * seq_len * lk * 1536
@@ -1016,7 +1044,7 @@ def main():
                                           "launches_timed": len(ln_timer.pairs)}
 
     vae = None
-    if not args.no_vae:
+    if args.full and not args.no_vae:
         try:
             vae_bench = importlib.import_module(PKG + ".wan.modules.vae").bench_decode
             # The metric's VAE half is WanVAE(dtype=torch.float): the reference's own arithmetic class (its VAE computes
@@ -1033,14 +1061,14 @@ def main():
             vae = {"frames_per_s": None, "note": f"VAE path not built: {e}"}
 
     single = None
-    if not args.no_single_frame:
+    if args.full and not args.no_single_frame:
         try:
             single = single_frame_bench(model, device)
         except Exception as e:
             single = {"forwards_per_s": None, "error": repr(e)[:300]}
 
     encoders = None
-    if not args.no_encoders and rank == 0:
+    if args.full and not args.no_encoders and rank == 0:
         try:
             encoders = encoders_bench(device)
         except Exception as e:
@@ -1048,7 +1076,7 @@ def main():
 
     # before the training leg: that one updates the weights the full-size parity check compares
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(model, latent, torch.tensor([999.0]), ctx, seq_len)
         cpu["unit"] = "denoising steps/s (the sample is 1/60 of a step: 1 of 30 blocks of 1 of 2 forwards, extrapolated)"
         if not args.no_cpu_legs:
@@ -1065,7 +1093,7 @@ def main():
                 cpu["vae"] = {"value": None, "error": repr(e)[:200]}
 
     train = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         try:
             train = train_legs(model, device, world, dist)
         except Exception as e:  # the headline line must survive a failure of this extra leg
@@ -1158,7 +1186,7 @@ def main():
             "single_frame": single, "vae": vae, "encoders": encoders, "train": train, "roofline": roofline,
             "cpu_baseline": cpu,
         }
-        emit(compact_line(out, write_detail(out)))
+        emit(compact_line(out, write_detail(out) if args.full else None))
     else:
         emit(None)
 

@@ -231,6 +231,7 @@ def main():
                         timesteps=r.timesteps.numpy())
 
     golden_dpmpp()
+    golden_small_ref()
 
     # ---- full-size Wan2.1-T2V-1.3B forward (config 1): checksums + 64 probe elements
     if os.environ.get("OMH_GOLDEN_FULL", "1") == "1":
@@ -246,6 +247,28 @@ def main():
                             abs_mean=np.float64(out.double().abs().mean()),
                             coarse=out[:, 0, ::6, ::8].numpy())
         print("1.3B", float(out.abs().mean()))
+
+
+def small_ref_case():
+    """Shared by the generator and the tests: a 3-layer d = 128 DiT and a dim-16 VAE decode on small inputs."""
+    cfg = O.DiTConfig(dim=128, ffn_dim=256, num_heads=1, num_layers=3, text_dim=32, text_len=16, freq_dim=32)
+    xs = [torch.from_numpy(detgen.normalish("live/x", (16, 1, 4, 4)))]
+    ctx = [torch.from_numpy(detgen.normalish("live/c", (5, 32)))]
+    cfgv = V.VAEConfig(dim=16)
+    z = torch.from_numpy(detgen.normalish("live/z", (16, 2, 4, 4)))
+    return cfg, xs, ctx, torch.tensor([7.]), 6, cfgv, z
+
+
+def golden_small_ref():
+    """The REAL reference's DiT forward and VAE decode on small_ref_case() -> tests/golden/small_ref_dit_vae.npz."""
+    os.makedirs(OUT, exist_ok=True)
+    cfg, xs, ctx, t, seq_len, cfgv, z = small_ref_case()
+    dit = ref_import.build_reference_dit(cfg, O.synth_state_dict(cfg, "live"))(xs, t, ctx, seq_len)[0]
+    vae = ref_import.build_reference_vae(V.synth_state_dict(cfgv, "live/vae"), dim=16)
+    scale = [torch.tensor(V.LATENT_MEAN), 1.0 / torch.tensor(V.LATENT_STD)]
+    dec = vae.decode(z[None], scale).clamp(-1, 1)[0]
+    np.savez_compressed(os.path.join(OUT, "small_ref_dit_vae.npz"), dit=dit.float().numpy(), vae_decode=dec.float().numpy())
+    print("small reference case", float(dit.abs().mean()), float(dec.abs().mean()))
 
 
 def encoder_cases():
@@ -284,6 +307,11 @@ def golden_encoders():
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "encoders":
     torch.set_grad_enabled(False)
     golden_encoders()
+    sys.exit(0)
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "small_ref":
+    torch.set_grad_enabled(False)
+    golden_small_ref()
     sys.exit(0)
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "train_i2v":

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -34,9 +35,9 @@ def test_bench_prints_one_json_line(forced_rccl):
     env.pop("OMH_CONV_TILE", None)
     if forced_rccl:
         env.update(OMH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-vae",
-                        "--no-single-frame", "--no-train", "--no-cpu-baseline", "--no-encoders"], env=env, capture_output=True, text=True,
-                       timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0",
+                        "--no-vae", "--no-single-frame", "--no-train", "--no-cpu-baseline", "--no-encoders"], env=env,
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d, full = _line_and_detail(r.stdout)
     assert "kernels" in full["dit"] and "dit" not in d          # the per-kernel table lives in the side file
@@ -48,6 +49,34 @@ def test_bench_prints_one_json_line(forced_rccl):
     assert "workload" in d["config"]
 
 
+def test_plain_bench_times_the_steps_and_dumps_the_last_latent(tmp_path):
+    """A plain run (no --full) prints the contract's fields and nothing measured beside the headline, times exactly
+    --steps steps also past the sampler's 50 (step 51 begins a new sample from the same noise), and --dump-outputs
+    writes the latent of the last timed step: after 51 steps the same array as after one, since the inputs are seeded."""
+    env = dict(os.environ)
+    env.pop("OMH_GEMM_KERNEL", None)
+    env.pop("OMH_CONV_TILE", None)
+    dumps = {}
+    for steps in (51, 1):
+        out = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "1", "--steps", str(steps),
+                            "--warmup", "0", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+            assert key in d, key
+        assert d["steps"] == steps and d["warmup"] == 0 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "detail" not in d
+        dumps[steps] = np.load(out / "latent.npy")
+        assert dumps[steps].dtype == np.float32 and dumps[steps].shape == (16, 1, 60, 104)
+        assert np.isfinite(dumps[steps]).all()
+    a, b = dumps[51].astype(np.float64), dumps[1].astype(np.float64)
+    assert np.linalg.norm(a - b) <= 1e-4 * np.linalg.norm(b)
+
+
 def test_bench_gpus_2_launches_itself():
     """`python bench.py --gpus 2` with no launcher around it (how the driver calls it) must start its own ranks under
     torch.distributed.run and still print ONE line, with n_gpus = 2 and a two-rank gradient all-reduce in the training
@@ -56,8 +85,8 @@ def test_bench_gpus_2_launches_itself():
     for k in ("OMH_GEMM_KERNEL", "OMH_CONV_TILE", "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env.update(OMH_DIST_BACKEND="gloo", OMH_TRAIN_LEGS="primary", OMH_TRAIN_BATCH="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--no-vae", "--no-single-frame", "--no-cpu-baseline", "--no-encoders"], env=env, capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup",
+                        "0", "--no-vae", "--no-single-frame", "--no-cpu-baseline", "--no-encoders"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d, full = _line_and_detail(r.stdout)
@@ -83,8 +112,8 @@ def test_bench_gpus_8_launches_itself(mode):
         env.pop(k, None)
     env.update(OMH_DIST_BACKEND="gloo", OMH_TRAIN_LEGS="primary", OMH_TRAIN_BATCH="1", OMH_TRAIN_STEPS="1",
                OMH_TRAIN_WARMUP="1", OMH_GRAD_COLLECTIVE="rs_ag", OMH_GRAD_PAYLOAD="bf16")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--no-vae",
-           "--no-single-frame", "--no-cpu-baseline", "--no-encoders"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "1", "--warmup", "0",
+           "--no-vae", "--no-single-frame", "--no-cpu-baseline", "--no-encoders"]
     if mode == "cfg_split":
         cmd += ["--cfg", "split", "--no-train"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)

@@ -1,6 +1,5 @@
 """CPU: the oracle (oracle/*.py) against the golden vectors produced by the REAL
-reference (oracle/make_golden.py), and against the live reference when
-/root/reference is present (build container only)."""
+reference (oracle/make_golden.py)."""
 import os
 
 import numpy as np
@@ -111,23 +110,19 @@ def test_oracle_1_3b_forward_matches_reference_probes():
     assert abs(float(out.double().abs().mean()) - float(g["abs_mean"])) < 1e-5
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/seaweed_apt"), reason="reference tree not present")
 def test_oracle_against_live_reference():
-    from oracle import detgen, ref_import, wan_dit_oracle as O, wan_vae_oracle as V
-    cfg = O.DiTConfig(dim=128, ffn_dim=256, num_heads=1, num_layers=3, text_dim=32, text_len=16, freq_dim=32)
-    sd = O.synth_state_dict(cfg, "live")
-    ref = ref_import.build_reference_dit(cfg, sd)
-    xs = [torch.from_numpy(detgen.normalish("live/x", (16, 1, 4, 4)))]
-    ctx = [torch.from_numpy(detgen.normalish("live/c", (5, 32)))]
+    """A 3-layer d = 128 DiT forward and a dim-16 VAE decode of the oracle against the reference's own outputs on the
+    same inputs (oracle/make_golden.py small_ref, `small_ref_dit_vae.npz`)."""
+    from oracle import make_golden, wan_dit_oracle as O, wan_vae_oracle as V
+    g = _g("small_ref_dit_vae.npz")
+    cfg, xs, ctx, t, seq_len, cfgv, z = make_golden.small_ref_case()
     with torch.no_grad():
-        r = ref(xs, torch.tensor([7.]), ctx, 6)[0]
-    assert rel_rms(O.dit_forward(sd, cfg, xs, torch.tensor([7.]), ctx, 6)[0], r) < 1e-5
-    cfgv = V.VAEConfig(dim=16)
-    sdv = V.synth_state_dict(cfgv, "live/vae")
-    refv = ref_import.build_reference_vae(sdv, dim=16)
-    z = torch.from_numpy(detgen.normalish("live/z", (16, 2, 4, 4)))
-    scale = [torch.tensor(V.LATENT_MEAN), 1.0 / torch.tensor(V.LATENT_STD)]
-    assert rel_rms(V.vae_decode(sdv, cfgv, z), refv.decode(z[None], scale).clamp(-1, 1)[0]) < 1e-5
+        out = O.dit_forward(O.synth_state_dict(cfg, "live"), cfg, xs, t, ctx, seq_len)[0]
+    assert out.shape == g["dit"].shape
+    assert rel_rms(out, torch.from_numpy(g["dit"])) < 1e-5
+    dec = V.vae_decode(V.synth_state_dict(cfgv, "live/vae"), cfgv, z)
+    assert dec.shape == g["vae_decode"].shape
+    assert rel_rms(dec, torch.from_numpy(g["vae_decode"])) < 1e-5
 
 
 def test_detgen_is_stable():
