@@ -285,6 +285,15 @@ typedef struct omh_attn_bwd_args {
 int omh_flash_attn_bwd_d128(const omh_attn_bwd_args* args, omh_stream_t stream);
 /* Scratch size the call can use (0: none needed / no split for these shapes); depends on B, H, Lq, Lk, phase. */
 int64_t omh_flash_attn_bwd_workspace_bytes(const omh_attn_bwd_args* args);
+/* Additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout changed): the backward of the forward's band
+   (omh_attn_args.window_left / window_right).  Query i of sample b (qlen = Lq: no q_lens here, klen = k_lens[b] or Lk)
+   has P = 0 for every key j outside  i + (klen - Lq) - window_left <= j <= i + (klen - Lq) + window_right  (a side < 0
+   unbounded; (-1, -1) = full attention through the band kernels).  `args` as for omh_flash_attn_bwd_d128 with o32
+   REQUIRED (OMH_E_BADARG without it or with a missing pointer); q_prescaled, out_bf16 and phase 0..3 as there.  Rows
+   whose band is empty (lse = -inf) contribute nothing; keys and queries no band reaches get zero gradients (written).
+   The workspace is declined (never split); no atomics: repeatable bit for bit. */
+int omh_flash_attn_bwd_band_d128(const omh_attn_bwd_args* args, int32_t window_left, int32_t window_right,
+                                 omh_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * LayerNorm (no affine) fused with adaLN modulation, fp32 in -> bf16 out.

@@ -50,16 +50,19 @@ __device__ __forceinline__ uint4 ld16(const uint16_t* p, bool ok) {
 //   PRE   q carries scale * log2(e): the scores need no factor
 //   FOLD  the score accumulators started from -lse / sc and the dP accumulators from -delta (MFMA C operand of the first
 //         product): P = exp2(sc s), dS = P dp — the fma and the subtraction per score are gone
-//   MASK  keys key_base + 16 (r >> 3) + (r & 7) at or past `klen` get P = 0 (the dQ kernel's last key tile only)
-template <bool PRE, bool FOLD, bool MASK>
+//   MASK  1: keys key_base + 16 (r >> 3) + (r & 7) at or past `klen` get P = 0 (the dQ kernel's last key tile only);
+//         2: keys outside [key_lo, klen] get P = 0 (the band kernels: `klen` is then the row's last key of its band)
+template <bool PRE, bool FOLD, int MASK>
 __device__ __forceinline__ void p_and_ds(const f32x16& s, const f32x16& dp, float lv, float dl, int key_base, int klen,
-                                         float sc, bf16x8* pf, bf16x8* dsf) {
+                                         float sc, bf16x8* pf, bf16x8* dsf, int key_lo = 0) {
     float p[16], ds[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float x = FOLD ? (PRE ? s[r] : s[r] * sc) : (PRE ? s[r] - lv : fmaf(s[r], sc, -lv));
         p[r] = __builtin_amdgcn_exp2f(x);
-        if (MASK) p[r] = (key_base + ((r >> 3) << 4) + (r & 7) < klen) ? p[r] : 0.f;
+        const int key = key_base + ((r >> 3) << 4) + (r & 7);
+        if (MASK == 1) p[r] = (key < klen) ? p[r] : 0.f;
+        if (MASK == 2) p[r] = (key >= key_lo && key <= klen) ? p[r] : 0.f;   // (a select: exp2 of a score outside may be inf)
         ds[r] = p[r] * (FOLD ? dp[r] : dp[r] - dl);
     }
 #pragma unroll
@@ -196,9 +199,13 @@ struct BwdSplit {
     float* ws;            // dQ: [n_tail][splits][128][128];  dK, dV: [n_tail][splits][2][128][128]  fp32
 };
 
-template <bool PRE>
+// WIN: the band of omh_flash_attn_bwd_band_d128 (include/omh.h; the forward's flash_attn_fwd_d128_kernel<true>, with
+// qlen = Lq): query i sees key j iff i + shift - wl <= j <= i + shift + wr, shift = klen - Lq, a side < 0 unbounded.  The
+// workgroup loops over the key tiles that meet the band of its live rows only and masks every score against its row's
+// band (key_lo, key_hi) — a separate instantiation: the full-attention kernel keeps its instruction stream.  Never split.
+template <bool PRE, bool WIN>
 __global__ __launch_bounds__(256, 2)
-void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk) {
+void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk, const int wl, const int wr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][K tile | V tile]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
     const bool worker = (int)blockIdx.x >= wk.n_regular;
@@ -212,7 +219,7 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     klen = min(max(klen, 0), p.Lk);
     const int n_tiles_all = (klen + TB - 1) / TB;
     int t_first = 0, n_tiles = n_tiles_all;
-    if (worker) {
+    if (!WIN && worker) {
         const int per = (n_tiles_all + wk.splits - 1) / wk.splits;
         t_first = min(split * per, n_tiles_all);
         n_tiles = min(t_first + per, n_tiles_all) - t_first;
@@ -224,6 +231,21 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     const uint16_t* V = (const uint16_t*)p.v + (int64_t)b * p.k_bs + head * D;
     const int q_row = qb * 128 + wave * 32 + li;
     const bool q_ok = q_row < p.Lq;
+    int key_lo = 0, key_hi = klen - 1;                               // WIN: this lane's (query row's) band of keys
+    if constexpr (WIN) {
+        const int shift = klen - p.Lq;
+        const int q0 = qb * 128, q1 = min(q0 + 128, p.Lq) - 1;      // live query rows of this workgroup
+        const int lo = wl < 0 ? 0 : max(0, q0 + shift - wl);
+        const int hi = wr < 0 ? klen - 1 : min(klen - 1, q1 + shift + wr);
+        if (hi < lo) {
+            n_tiles = 0;
+        } else {
+            t_first = lo / TB;
+            n_tiles = hi / TB - t_first + 1;
+        }
+        if (wl >= 0) key_lo = max(0, q_row + shift - wl);
+        if (wr >= 0) key_hi = min(klen - 1, q_row + shift + wr);
+    }
     bf16x8 qf[8], dof[8];
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
@@ -257,7 +279,7 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     // one tile of 64 keys; `masked`: the tile reaches past klen (the last one at most — every other tile skips the
     // compare + select per score)
     auto tile_body = [&](const unsigned char* kt, const unsigned char* vt, int k0, auto masked) {
-        constexpr bool MASK = decltype(masked)::value;
+        constexpr int MASK = decltype(masked)::value;
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
             // S^T = K Q^T and dP^T = V dO^T as [key][query], lane = query; register r <-> key k0 + 32hb + 16(r>>3) + 8lh + (r&7)
@@ -272,7 +294,7 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[kk], dp, 0, 0, 0);
             }
             bf16x8 pf[2], dsf[2];
-            p_and_ds<PRE, false, MASK>(s, dp, l2, del, k0 + 32 * hb + lh * 8, klen, sc, pf, dsf);
+            p_and_ds<PRE, false, MASK>(s, dp, l2, del, k0 + 32 * hb + lh * 8, MASK == 2 ? key_hi : klen, sc, pf, dsf, key_lo);
             // dQ^T += K^T dS^T   ([d][query], lane = query): K^T gathered from the row-major K tile
 #pragma unroll
             for (int a = 0; a < 2; ++a)
@@ -283,6 +305,18 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
                 }
         }
     };
+    if constexpr (WIN) {                                             // every tile masked against the rows' bands
+        for (int t = 0; t < n_tiles; ++t) {
+            const unsigned char* kt = smem + (t & 1) * 2 * TILE_BYTES;
+            if (t + 1 < n_tiles) {
+                const uint32_t nk = wave_lds + ((t + 1) & 1) * 2 * TILE_BYTES;
+                tile_dma(ks, t_first + t + 1, nk);
+                tile_dma(vs, t_first + t + 1, nk + TILE_BYTES);
+            }
+            tile_body(kt, kt + TILE_BYTES, (t_first + t) * TB, std::integral_constant<int, 2>());
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
+    } else {
     // the tile that reaches past klen (the last one of the sequence, if any) is peeled off the loop: two bodies inside
     // one loop keep both sets of hoisted addresses live and spill
     const bool edge = n_tiles > 0 && (t_first + n_tiles) * TB > klen;
@@ -294,18 +328,19 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
             tile_dma(ks, t_first + t + 1, nk);
             tile_dma(vs, t_first + t + 1, nk + TILE_BYTES);
         }
-        tile_body(kt, kt + TILE_BYTES, (t_first + t) * TB, std::false_type());
+        tile_body(kt, kt + TILE_BYTES, (t_first + t) * TB, std::integral_constant<int, 0>());
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
     if (edge) {
         const unsigned char* kt = smem + (n_plain & 1) * 2 * TILE_BYTES;
-        tile_body(kt, kt + TILE_BYTES, (t_first + n_plain) * TB, std::true_type());
+        tile_body(kt, kt + TILE_BYTES, (t_first + n_plain) * TB, std::integral_constant<int, 1>());
+    }
     }
 #pragma unroll
     for (int db = 0; db < 4; ++db)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[db][r] *= p.scale;             // dQ = scale dS K
-    if (worker) {                                                    // partial sums over this worker's keys
+    if (!WIN && worker) {                                            // partial sums over this worker's keys
         float* W = wk.ws + (((int64_t)(wid - wk.n_regular) * wk.splits + split) * 128 + wave * 32 + li) * D;
 #pragma unroll
         for (int db = 0; db < 4; ++db)
@@ -396,9 +431,12 @@ __device__ __forceinline__ void dkdv_store(const omh_attn_bwd_args& p, const Bwd
 // operand registers + 64 score + 32 packed P / dS + fragments + addresses) is ~290 > 256 arch VGPRs, and hipcc spills
 // 334 registers (812 bytes of scratch per lane).  It needs an asm-owned register map with P / dS overlaid on the score
 // registers and lse / delta folded into the MFMA C operand.
-template <int WAVES, int KPW, bool PRE>
+//
+// WIN: the band (see attn_bwd2_dq_kernel).  Key j is reached by queries [j - shift - wr, j - shift + wl]: the workgroup loops over
+// the query tiles that meet the union of its live keys' ranges, and every score is masked against its key's range.
+template <int WAVES, int KPW, bool PRE, bool WIN>
 __global__ __launch_bounds__(64 * WAVES, 1)
-void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk) {
+void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk, const int wl, const int wr) {
     constexpr int THREADS = 64 * WAVES;
     static_assert(WAVES * KPW == 4, "a workgroup covers 128 keys");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][Q tile | dO tile] + lse/delta
@@ -413,10 +451,27 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     klen = min(max(klen, 0), p.Lk);
     const int n_tiles_all = (p.Lq + TB - 1) / TB;
     int t_first = 0, n_tiles = n_tiles_all;
-    if (worker) {                                                    // this worker's share of the query tiles
+    if (!WIN && worker) {                                            // this worker's share of the query tiles
         const int per = (n_tiles_all + wk.splits - 1) / wk.splits;
         t_first = min(split * per, n_tiles_all);
         n_tiles = min(t_first + per, n_tiles_all) - t_first;
+    }
+    int q_lo = 0, q_hi = 0;                                          // WIN: this lane's (key's) range of queries
+    if constexpr (WIN) {
+        static_assert(KPW == 1, "one key per lane");
+        const int shift = klen - p.Lq;
+        const int k0 = kb * 128, k1 = min(k0 + 128, klen) - 1;      // live keys of this workgroup
+        const int lo = wr < 0 ? 0 : max(0, k0 - shift - wr);
+        const int hi = wl < 0 ? p.Lq - 1 : min(p.Lq - 1, k1 - shift + wl);
+        if (k1 < k0 || hi < lo) {
+            n_tiles = 0;
+        } else {
+            t_first = lo / TB;
+            n_tiles = hi / TB - t_first + 1;
+        }
+        const int key = kb * 128 + wave * 32 + li;
+        q_lo = wr < 0 ? -(1 << 30) : key - shift - wr;
+        q_hi = wl < 0 ? (1 << 30) : key - shift + wl;
     }
 
     const uint16_t* Q = (const uint16_t*)p.q + (int64_t)b * p.q_bs + head * D;
@@ -534,9 +589,16 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         };
         // no key mask: a lane is ONE key, and a key at or past klen only spoils its own dK / dV column (zeroed after the loop)
         u32x4 cp[2][2], cd[2][2];                                    // packed P / dS: [half][16-query group]
+        // WIN: the lane's query range relative to query 64 t + 8 lh of this tile (register r of half hb: + 32 hb + 16 (r >> 3) + (r & 7))
+        const int rel_lo = q_lo - ((t_first + t) * TB + 8 * lh), rel_hi = q_hi - ((t_first + t) * TB + 8 * lh);
         auto slice_b = [&](int hb, int i) {                          // scores 2i, 2i+1 of a half (p_and_ds FOLD, no mask)
-            const float p0 = __builtin_amdgcn_exp2f(PRE ? s[hb][2 * i] : s[hb][2 * i] * sc);
-            const float p1 = __builtin_amdgcn_exp2f(PRE ? s[hb][2 * i + 1] : s[hb][2 * i + 1] * sc);
+            float p0 = __builtin_amdgcn_exp2f(PRE ? s[hb][2 * i] : s[hb][2 * i] * sc);
+            float p1 = __builtin_amdgcn_exp2f(PRE ? s[hb][2 * i + 1] : s[hb][2 * i + 1] * sc);
+            if constexpr (WIN) {                                     // (a select: exp2 of a score outside the band may be inf)
+                const int o0 = 32 * hb + 16 * ((2 * i) >> 3) + ((2 * i) & 7), o1 = o0 + 1;
+                p0 = (o0 >= rel_lo && o0 <= rel_hi) ? p0 : 0.f;
+                p1 = (o1 >= rel_lo && o1 <= rel_hi) ? p1 : 0.f;
+            }
             cp[hb][i >> 2][i & 3] = pack_bf2(p0, p1);
             cd[hb][i >> 2][i & 3] = pack_bf2(p0 * dp[hb][2 * i], p1 * dp[hb][2 * i + 1]);
         };
@@ -585,7 +647,7 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     }
 #pragma unroll
     for (int c = 0; c < KPW; ++c)
-        dkdv_store(p, wk, worker, wid, split, b, head, wave * (32 * KPW) + 32 * c + li, lh, key0 + 32 * c, klen, ds_scale, dk[c], dv[c]);
+        dkdv_store(p, wk, !WIN && worker, wid, split, b, head, wave * (32 * KPW) + 32 * c + li, lh, key0 + 32 * c, klen, ds_scale, dk[c], dv[c]);
 }
 
 // ---------------------------------------------------------------------------------------------- dK, dV: the stream
@@ -891,10 +953,10 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
     constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
         (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_w64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, OMH_ATTN_BWD_W64_LDS);
         (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_w64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, OMH_ATTN_BWD_W64_LDS);
         (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_w64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, OMH_ATTN_BWD_DQ_W64_LDS);
@@ -924,8 +986,8 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (bwd2_dq_stream()) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
             else hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
-        } else if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dq_kernel<true>, grid, dim3(256), LDS_DQ, s, a, q_blocks, wq);
-        else hipLaunchKernelGGL(attn_bwd2_dq_kernel<false>, grid, dim3(256), LDS_DQ, s, a, q_blocks, wq);
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1);
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1);
         if (wq.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<1>, dim3((wq.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, q_blocks, wq);
     }
@@ -935,10 +997,52 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (!(e && e[0] == '0')) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
             else hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
-        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv);
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv);
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1);
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1);
         if (wkv.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<2>, dim3((wkv.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, k_blocks, wkv);
+    }
+    return 0;
+}
+
+// called by omh_flash_attn_bwd_band_d128 (attention_bwd.hip) with validated arguments and o32 set: the same phases as
+// omh_launch_attn_bwd2, on the WIN instantiations of the HIP kernels (the w64 streams are full-attention only); never
+// split (the entry declines the workspace).
+int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, hipStream_t s) {
+    if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
+        ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
+        return OMH_E_SHAPE;
+    if (((uintptr_t)a.o32 & 15) || (a.o_rs & 3) || (a.o_bs & 3)) return OMH_E_ALIGN;
+    if (a.phase < 0 || a.phase > 3) return OMH_E_BADARG;
+    const int64_t pairs = (int64_t)a.B * a.Lq * a.H;
+    if (pairs >= 0x7fffffffLL) return OMH_E_SHAPE;
+    // a side wider than the problem is unbounded in effect; clamped so that the kernels' index arithmetic stays in int
+    const int wmax = a.Lq + a.Lk;
+    wl = wl < 0 ? -1 : (wl > wmax ? wmax : wl);
+    wr = wr < 0 ? -1 : (wr > wmax ? wmax : wr);
+    constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        attr_set = true;
+    }
+    if (a.phase == 0 || a.phase == 1) {
+        hipLaunchKernelGGL(attn_bwd2_delta_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, s, a);
+        if (a.phase == 1) return 0;
+    }
+    const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
+    if (a.phase == 0 || a.phase == 2) {
+        const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr);
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr);
+    }
+    if (a.phase == 0 || a.phase == 3) {
+        const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr);
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr);
     }
     return 0;
 }

@@ -203,7 +203,7 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
 
 
 def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_prescaled=False, out=None, o32=None,
-                   phase=0, delta=None, split=True):
+                   phase=0, delta=None, split=True, window=(-1, -1)):
     """Fused attention backward (include/omh.h).  q, dout: bf16 [B*Lq, H*128]; k, v: bf16 [B*Lk, H*128] (row stride
     free); lse fp32 [B, H, Lq] from ``flash_attn_raw(..., lse=)``; k_lens int32 [B] or None.
     Returns fp32 dq [B*Lq, H*128], dk, dv [B*Lk, H*128] — or, with ``out=(dq, dk, dv)`` bf16 2-D tensors (row stride
@@ -213,7 +213,9 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     delta from dO . o32); without it round 2's kernels run (three transposes + a delta pass over the keys).
     ``phase`` (with o32): 0 everything; 1 delta only, 2 dQ only, 3 dK / dV only — 2 and 3 read the ``delta`` tensor
     (fp32 [B, H, Lq]) a phase-1 call filled and may run on two streams.  ``split`` (with o32): hand the kernels scratch so
-    that a partly filled last round of workgroups is split over the inner loop (include/omh.h, ABI v8)."""
+    that a partly filled last round of workgroups is split over the inner loop (include/omh.h, ABI v8).
+    ``window`` = (left, right): the backward of ``flash_attn_raw(..., window=)``'s band (omh_flash_attn_bwd_band_d128,
+    additive to ABI v12): a bounded side requires ``o32``; the band kernels run unsplit.  (-1, -1): the call above."""
     _dev(q, k, v, dout, lse, k_lens, o32)
     d = H * 128
     for t in (q, k, v, dout):
@@ -258,6 +260,11 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
                          Lk * dk.stride(0), dk.stride(0), d * ldq, d * ldk, ldq, ldk,
                          float(scale if scale is not None else 128 ** -0.5), int(q_prescaled), bf, _p(o32), int(phase),
                          None, 0)
+    if window[0] >= 0 or window[1] >= 0:
+        assert o32 is not None, "flash_attn_bwd: a bounded window needs the forward's fp32 output (o32=)"
+        check(lib.omh_flash_attn_bwd_band_d128(C.byref(a), int(window[0]), int(window[1]), _stream()),
+              "omh_flash_attn_bwd_band_d128")
+        return dq, dk, dv
     need = lib.omh_flash_attn_bwd_workspace_bytes(C.byref(a)) if split else 0     # partial sums of the split last round
     if need > 0:
         ws = torch.empty(need, dtype=torch.uint8, device=dev)

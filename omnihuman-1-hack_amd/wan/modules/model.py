@@ -232,8 +232,9 @@ class WanSelfAttention(nn.Module):
             ops.gemm_raw(ptr(wv), ptr(h), ptr(vt), d, S, d, d, d, Sp, EPI_BF16, bias=ptr(bv), bias_mode=BIAS_M, batch=B,
                          strideA=0, strideB=S * d, strideC=d * Sp)
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
+        # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
-                           d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1)
+                           d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1, window=tuple(self.window_size))
         return o
 
     def forward(self, x, seq_lens, grid_sizes, freqs, _fc: Optional["_FwdCtx"] = None):
