@@ -628,6 +628,24 @@ int omh_softmax_bwd_rows(const void* p_bf16, int64_t ldp, const float* dp, int64
 /* Adjoint of omh_unpatchify: g fp32 [Cout, f*pt, h*ph, w*pw] -> dtok bf16 [f*h*w, pt*ph*pw*Cout]. */
 int omh_unpatchify_bwd(const float* g, void* dtok_bf16, int32_t Cout, int32_t f, int32_t h, int32_t w,
                        int32_t pt, int32_t ph, int32_t pw, omh_stream_t stream);
+/* Gradients w.r.t. the inputs of WanModel.forward (the reference's autograd fills them: model.py:502-563 takes x, y,
+ * context, clip_fea and t as ordinary differentiable tensors).  Additive to ABI v12.
+ *
+ * Adjoint of omh_patchify (model.py:515-518, the Conv3d of patch_embedding seen from its input): token gradients
+ * dtok fp32 [f*h*w, ld >= Kp] (column layout of omh_patchify) -> the latent gradient fp32 [C, F, H, W], written as two
+ * destinations split at channel c_split: out0 [c_split, F, H, W] (the x of model.py:514) and out1 [C - c_split, F, H, W]
+ * (the y concatenated behind it).  Either destination may be NULL (not both).  f*pt <= F, h*ph <= H, w*pw <= W: frames,
+ * rows and columns that no patch covers are written as zero.  Every output element is written exactly once (no atomics,
+ * no zero fill by the caller).  16-byte loads and stores along W when W, Kp and ld are multiples of 4 and the pointers
+ * are 16-byte aligned; one element per lane otherwise. */
+int omh_patchify_bwd(const float* dtok, int64_t ld, float* out0, float* out1, int32_t C, int32_t c_split, int32_t F,
+                     int32_t H, int32_t W, int32_t f, int32_t h, int32_t w, int32_t pt, int32_t ph, int32_t pw,
+                     int32_t Kp, omh_stream_t stream);
+/* Adjoint of omh_sinusoidal_embedding (model.py:17-27, :526-528): dsin fp32 [B, dim] and t [B] -> dt fp32 [B],
+ * dt[b] = sum_i w_i (cos(t_b w_i) dsin[b][half + i] - sin(t_b w_i) dsin[b][i]), w_i = 10000^(-i/half): the same
+ * frequency table and argument order, in fp64, summed in a fixed order. */
+int omh_sinusoidal_embedding_bwd(const float* dsin, const float* t, float* dt, int32_t B, int32_t dim,
+                                 omh_stream_t stream);
 /* Backward of omh_dense_f32 (act_out must have been 0): dW += dy^T act(x), db += sum_b dy,
  * dx (=|+=) (dy W) * act'(x).  dW_accum / dx may be NULL. */
 int omh_dense_f32_bwd(const float* x, const float* W, const float* dy, float* dW_accum, float* db_accum,

@@ -558,6 +558,108 @@ void unpatchify_bwd_kernel(const float* __restrict__ g, uint16_t* __restrict__ d
     }
 }
 
+// ------------------------------------------------------------------ patchify backward (gradient w.r.t. the latents)
+// Adjoint of patchify_kernel: out[c][f*pt+a][h*ph+i][w*pw+j] = dtok[(f,h,w)][((c*pt+a)*ph+i)*pw+j], zero where no patch
+// covers the element.  One workgroup per (patch frame, patch row, chunk of TW patch columns): the chunk's token rows are
+// one contiguous run of TW * Kp floats — read with 16-byte loads, staged in LDS with an odd row pitch — and every
+// (c, a, i) then owns a contiguous run of the output's W axis, written VW floats per lane.  Channels below c_split go
+// to out0 [c_split, F, H, W], the rest to out1 [C - c_split, F, H, W]; a null destination is skipped.  Every output
+// element has exactly one writer.
+constexpr int PB_LDS_FLOATS = 8192;
+
+template <int VW>
+__global__ __launch_bounds__(256)
+void patchify_bwd_kernel(const float* __restrict__ dtok, int64_t ld, float* __restrict__ out0, float* __restrict__ out1,
+                         int C, int c_split, int F, int H, int W, int gf, int gh, int gw, int pt, int ph, int pw,
+                         int Kp, int TW, int nchunk) {
+    __shared__ float tile[PB_LDS_FLOATS];
+    const int tid = threadIdx.x;
+    const int chunk = blockIdx.x % nchunk;
+    const int hi = (blockIdx.x / nchunk) % ((H + ph - 1) / ph);
+    const int fi = blockIdx.x / (nchunk * ((H + ph - 1) / ph));
+    const bool covered = fi < gf && hi < gh;
+    const int t0 = chunk * TW;                                  // first patch column of the chunk
+    const int nt = covered ? min(TW, gw - t0) : 0;               // its token rows
+    const int ldk = Kp + 1;                                     // odd pitch: the column reads below spread over the banks
+    if (nt > 0) {
+        const float* src = dtok + (((int64_t)fi * gh + hi) * gw + t0) * ld;
+        if (VW == 4) {                                          // ld, Kp multiples of 4 and a 16-byte aligned base
+            const int k4n = Kp >> 2;
+            for (int i = tid; i < nt * k4n; i += 256) {
+                const int tk = i / k4n, k4 = i - tk * k4n;
+                const float4 v = *(const float4*)(src + (int64_t)tk * ld + 4 * k4);
+                float* d = tile + tk * ldk + 4 * k4;
+                d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+            }
+        } else {
+            for (int i = tid; i < nt * Kp; i += 256) {
+                const int tk = i / Kp, k = i - tk * Kp;
+                tile[tk * ldk + k] = src[(int64_t)tk * ld + k];
+            }
+        }
+    }
+    __syncthreads();
+    // the chunk's columns of the output: [w_lo, w_hi); the last chunk also owns the columns no patch covers
+    const int w_lo = t0 * pw;
+    const int w_hi = (chunk == nchunk - 1) ? W : (t0 + TW) * pw;
+    const int wcov = covered ? min((t0 + nt) * pw, gw * pw) : 0;  // columns below this one come from the tile
+    const int ngrp = (w_hi - w_lo + VW - 1) / VW;
+    const int rows = C * pt * ph;
+    for (int item = tid; item < rows * ngrp; item += 256) {
+        const int r = item / ngrp, g = item - r * ngrp;
+        const int i = r % ph, a = (r / ph) % pt, c = r / (ph * pt);
+        const int ff = fi * pt + a, hh = hi * ph + i;
+        if (ff >= F || hh >= H) continue;
+        float* dst = c < c_split ? out0 : out1;
+        if (!dst) continue;
+        const int cc = c < c_split ? c : c - c_split;
+        const int w0 = w_lo + g * VW;
+        float v[VW];
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            const int ww = w0 + e;
+            float val = 0.f;
+            if (ww < wcov) {
+                const int tk = ww / pw - t0, j = ww % pw;
+                val = tile[tk * ldk + r * pw + j];
+            }
+            v[e] = val;
+        }
+        float* o = dst + (((int64_t)cc * F + ff) * H + hh) * W + w0;
+        if (VW == 4) {
+            *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);   // W and w0 multiples of 4: aligned, inside the row
+        } else {
+            o[0] = v[0];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ sinusoidal embedding backward (gradient w.r.t. t)
+// forward (sinusoid_kernel): out[b][k] = cos(t_b w_k), out[b][half + k] = sin(t_b w_k), w_k = 10000^(-k / half), fp64.
+// dt[b] = sum_k w_k (cos(t_b w_k) dsin[b][half + k] - sin(t_b w_k) dsin[b][k]): one workgroup per b, summed in a fixed
+// order (fp64).
+__global__ __launch_bounds__(256)
+void sinusoid_bwd_kernel(const float* __restrict__ dsin, const float* __restrict__ t, float* __restrict__ dt, int dim) {
+    __shared__ double red[256];
+    const int half = dim / 2;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* g = dsin + (int64_t)b * dim;
+    const double tb = (double)t[b];
+    double s = 0.0;
+    for (int k = tid; k < half; k += 256) {
+        const double wk = pow(10000.0, -(double)k / (double)half);
+        const double ang = tb * wk;
+        s += wk * (cos(ang) * (double)g[half + k] - sin(ang) * (double)g[k]);
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int n = 128; n > 0; n >>= 1) {
+        if (tid < n) red[tid] += red[tid + n];
+        __syncthreads();
+    }
+    if (tid == 0) dt[b] = (float)red[0];
+}
+
 // ------------------------------------------------------------------ tiny fp32 dense backward (time embedding)
 // forward: y[b][n] = sum_k act(x[b][k]) W[n][k] + bias[n]
 __global__ __launch_bounds__(256)
@@ -810,6 +912,41 @@ extern "C" int omh_unpatchify_bwd(const float* g, void* dtok_bf16, int32_t Cout,
     omh_clear_status();
     hipLaunchKernelGGL(unpatchify_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, g,
                        (uint16_t*)dtok_bf16, Cout, f, h, w, pt, ph, pw);
+    return omh_launch_status();
+}
+
+extern "C" int omh_patchify_bwd(const float* dtok, int64_t ld, float* out0, float* out1, int32_t C, int32_t c_split,
+                                int32_t F, int32_t H, int32_t W, int32_t f, int32_t h, int32_t w, int32_t pt, int32_t ph,
+                                int32_t pw, int32_t Kp, omh_stream_t stream) {
+    if (!dtok || (!out0 && !out1) || C <= 0 || F <= 0 || H <= 0 || W <= 0 || f <= 0 || h <= 0 || w <= 0 || pt <= 0 ||
+        ph <= 0 || pw <= 0 || c_split < 0 || c_split > C)
+        return OMH_E_BADARG;
+    if ((int64_t)f * pt > F || (int64_t)h * ph > H || (int64_t)w * pw > W || Kp < (int64_t)C * pt * ph * pw || ld < Kp ||
+        Kp + 1 > PB_LDS_FLOATS)
+        return OMH_E_SHAPE;
+    int TW = PB_LDS_FLOATS / (Kp + 1);                              // patch columns per workgroup
+    if (TW >= w) TW = w;
+    else if (TW >= 4) TW &= ~3;                                    // chunk starts stay 16-byte aligned along W
+    const int nchunk = (w + TW - 1) / TW;
+    const int64_t blocks = (int64_t)((F + pt - 1) / pt) * ((H + ph - 1) / ph) * nchunk;
+    if (blocks > 0x7fffffff) return OMH_E_SHAPE;
+    const bool vec = !(W & 3) && !(Kp & 3) && !(ld & 3) && (nchunk == 1 || !((TW * pw) & 3)) &&
+                     !(((uintptr_t)dtok | (uintptr_t)out0 | (uintptr_t)out1) & 15);
+    omh_clear_status();
+    if (vec)
+        hipLaunchKernelGGL(patchify_bwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dtok, ld, out0,
+                           out1, C, c_split, F, H, W, f, h, w, pt, ph, pw, Kp, TW, nchunk);
+    else
+        hipLaunchKernelGGL(patchify_bwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dtok, ld, out0,
+                           out1, C, c_split, F, H, W, f, h, w, pt, ph, pw, Kp, TW, nchunk);
+    return omh_launch_status();
+}
+
+extern "C" int omh_sinusoidal_embedding_bwd(const float* dsin, const float* t, float* dt, int32_t B, int32_t dim,
+                                            omh_stream_t stream) {
+    if (!dsin || !t || !dt || B <= 0 || dim <= 0 || (dim & 1)) return OMH_E_BADARG;
+    omh_clear_status();
+    hipLaunchKernelGGL(sinusoid_bwd_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, dsin, t, dt, dim);
     return omh_launch_status();
 }
 

@@ -761,6 +761,42 @@ def unpatchify_bwd(g: torch.Tensor, grid, patch):
     return out
 
 
+def patchify_bwd(dtok: torch.Tensor, grid, patch, shape, c_split=None, need=(True, True), out=None):
+    """Adjoint of ``patchify``: dtok fp32 [>= f*h*w, Kp] (row stride free) -> the gradient of the latent ``shape`` =
+    (C, F, H, W), split at channel ``c_split`` (None: C) into (fp32 [c_split, F, H, W], fp32 [C - c_split, F, H, W]) by
+    one launch; a part ``need`` does not ask for (or an empty one) is None and is not written.  Elements no patch covers
+    are zero.  ``out``: the two destinations, instead of fresh tensors."""
+    _dev(dtok)
+    assert dtok.dtype == torch.float32 and dtok.dim() == 2 and dtok.stride(1) == 1
+    Cc, F, H, W = shape
+    f, h, w = grid
+    pt, ph, pw = patch
+    cs = Cc if c_split is None else int(c_split)
+    assert 0 <= cs <= Cc and dtok.shape[0] >= f * h * w and dtok.shape[1] >= Cc * pt * ph * pw
+    if out is None:
+        out = tuple(torch.empty(n, F, H, W, dtype=torch.float32, device=dtok.device) if (n > 0 and want) else None
+                    for n, want in ((cs, need[0]), (Cc - cs, need[1])))
+    o0, o1 = out
+    _dev(o0, o1)
+    for o, n in ((o0, cs), (o1, Cc - cs)):
+        assert o is None or (o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (n, F, H, W))
+    check(lib.omh_patchify_bwd(_p(dtok), dtok.stride(0), _p(o0), _p(o1), Cc, cs, F, H, W, f, h, w, pt, ph, pw,
+                               dtok.shape[1], _stream()), "omh_patchify_bwd")
+    return o0, o1
+
+
+def sinusoidal_embedding_bwd(dsin: torch.Tensor, t: torch.Tensor):
+    """Adjoint of ``sinusoidal_embedding``: dsin fp32 [B, dim], t [B] -> dt fp32 [B]."""
+    _dev(dsin, t)
+    assert dsin.dtype == torch.float32 and dsin.is_contiguous() and dsin.dim() == 2
+    t = t.reshape(-1).to(torch.float32).contiguous()
+    assert t.shape[0] == dsin.shape[0]
+    dt = torch.empty(t.shape[0], dtype=torch.float32, device=dsin.device)
+    check(lib.omh_sinusoidal_embedding_bwd(_p(dsin), _p(t), _p(dt), t.shape[0], dsin.shape[1], _stream()),
+          "omh_sinusoidal_embedding_bwd")
+    return dt
+
+
 def dense_f32_bwd(x, w, dy, dW=None, db=None, dx=None, dx_accumulate=False, act_in=0):
     _dev(x, w, dy, dW, db, dx)
     B, K = x.shape

@@ -642,13 +642,30 @@ class WanModel(nn.Module):
         if device.type != "cuda":
             raise ops.OmhError("WanModel.forward runs on the MI355X only (no CPU fallback): move the model "
                                "to a GPU device")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                        or self._input_requires_grad(x, t, context, clip_fea, y, extra_conditions)):
+            # a frozen model whose INPUT requires grad (a critic backbone, guidance by a gradient, a rollout) takes the
+            # training forward too: the reference's autograd differentiates through x, y, context, clip_fea and t
             if isinstance(context, ContextState):
                 raise ValueError("a ContextState is an inference-time cache: pass the raw context when training")
             from .model_train import forward_train
             return forward_train(self, x, t, context, seq_len, clip_fea, y, extra_conditions)
         with torch.no_grad():
             return self._forward_infer(x, t, context, seq_len, clip_fea, y, extra_conditions)
+
+    @staticmethod
+    def _input_requires_grad(x, t, context, clip_fea, y, extra_conditions):
+        """Does any tensor input ask for a gradient: the elements of x, y and context, clip_fea, a floating t, the
+        condition tokens."""
+        def any_of(v):
+            if v is None or isinstance(v, ContextState):
+                return False
+            if isinstance(v, torch.Tensor):
+                return v.requires_grad
+            if isinstance(v, dict):
+                return any_of(v.get("tokens"))
+            return any(isinstance(u, torch.Tensor) and u.requires_grad for u in v)
+        return any(any_of(v) for v in (x, y, context, clip_fea, t, extra_conditions))
 
     def _embed(self, x, t, context, seq_len, clip_fea, y, extra_conditions=None):
         device = self.patch_embedding.weight.device

@@ -41,7 +41,10 @@ GELU' is an epilogue of the FFN dgrad GEMM.  q, k, v share one gradient buffer
 [rows, 3 dim], so their input gradient and their weight gradients are ONE GEMM
 each (K = 3 dim / M = 3 dim); likewise k, v of the cross-attention.  Gradients
 w.r.t. the time-embedding vector ``e0``, the text context and ``e`` are
-accumulated in a per-forward state object and consumed by the embed node.
+accumulated in a per-forward state object and consumed by the embed node, which also returns the gradients w.r.t.
+the model's INPUTS — x, y, context, clip_fea, t, the condition tokens: its direct arguments — whenever one of them
+requires grad (the reference's autograd does, model.py:502-563).  A model without a trainable parameter runs this
+forward too when an input requires grad; its blocks then form no weight or bias gradient.
 
 bf16 operand copies of the weights (and the transposed copies the dgrad GEMMs
 read) are rebuilt by ONE launch per step (``TrainPacks``, omh_pack_weights_multi)
@@ -798,6 +801,11 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     tgt = tgt or {}
     slots = slots or {}                                               # fresh weight gradients written into reducer buckets
     deferred = [] if _DEFER_COLSUM else None                          # second launches of the norm backwards (main stream)
+    # a block without a trainable parameter (a frozen backbone differentiated w.r.t. its input) only carries dx — and, when
+    # someone upstream reads it, the context gradient: no weight-gradient products, no bias sums, nothing for the second
+    # stream to do on their behalf
+    train = any(p.requires_grad for _, p in _block_params(model, idx))
+    need_ctx = train or getattr(st, "need_ctx", True)
 
     def acc1(name, n):
         """The fp32 accumulator of a 1-D gradient: the parameter's own .grad (added to) or a zeroed arena slice."""
@@ -808,6 +816,8 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
         """Bias gradients = column sums of dy, deferred to arena.flush() at the end of the block (``now``: launched here,
         on the current stream); ``names``: the parameters stacked along dy's columns, each ``d`` wide when there are
         several.  One pair for the whole width unless a parameter accumulates into its own .grad."""
+        if not train:
+            return
         if len(names) == 1 or not any(n in tgt for n in names):
             out = acc1(names[0], dy.shape[1]) if len(names) == 1 else arena.take(dy.shape[1])
             pairs = [(dy, out)]
@@ -826,6 +836,9 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     def wgrad(dy, x, names):
         """Weight gradients dy^T x into g[names] (parameters stacked along dy's columns, ``d`` wide each): one product,
         or one per parameter — same tiles, same launch — when a parameter accumulates into its own .grad."""
+        if not train:
+            return
+
         def one(dy_, n):
             p = tgt.get(n)
             if p is not None:
@@ -903,7 +916,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     wgrad(dy2, oc, ["cross_attn.o.weight"]), bgrad(dy2, ["cross_attn.o.bias"])
     doc = _dgrad(dy2, P["wo_cT"], epilogue=EPI_BF16)
     Rc = B * Lt
-    ctx2 = fc.ctx.view(B * Lc, d) if not i2v else fc.ctx[:, n_img:].contiguous().view(Rc, d)
+    ctx2 = None if not train else fc.ctx.view(B * Lc, d) if not i2v else fc.ctx[:, n_img:].contiguous().view(Rc, d)
     vc = ops.transpose_bf16_batched(S["vtc"], Lt)                     # [B*Lt, d]
     dqc = bf(R, d)
     dkv = bf(Rc, 2 * d)                                               # dk | dv of the text keys, one buffer
@@ -912,8 +925,9 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
                   (dqc, dkv[:, :d], dkv[:, d:]), S["o32_ca"], False)
     else:                                                             # the image-token branch: same q, same dO
         oi, ki = S["oi"], S["ki"]
-        wg.launch()                                                  # (the second product ADDS to the first one's result)
-        wg.add(dy2, oi, out=g["cross_attn.o.weight"])
+        if train:
+            wg.launch()                                              # (the second product ADDS to the first one's result)
+            wg.add(dy2, oi, out=g["cross_attn.o.weight"])
         dq32, dk32, dv32 = ops.flash_attn_bwd(qc, kc, vc, oc, doc, S["lse_ca"], fc.ctx_lens32, B, N, Sq, Lt, D ** -0.5)
         vi = ops.transpose_bf16_batched(S["vti"], n_img)
         dqi, dki, dvi = ops.flash_attn_bwd(qc, ki, vi, oi, doc, S["lse_ci"], None, B, N, Sq, n_img, D ** -0.5)
@@ -921,16 +935,17 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
         ops.cast_bf16(dq32, out=dqc)
         ops.cast_bf16_strided(dk32, dkv[:, :d])
         ops.cast_bf16_strided(dv32, dkv[:, d:])
-        Ri = B * n_img
-        ctxi = fc.ctx[:, :n_img].contiguous().view(Ri, d)
-        dkvi = bf(Ri, 2 * d)
-        ops.cast_bf16_strided(dki, dkvi[:, :d])
-        ops.cast_bf16_strided(dvi, dkvi[:, d:])
-        rms_bwd(ptr(S["kfi"]), False, d, ptr(dkvi), 2 * d, Ri, [ca._norm_w("norm_k_img")], ca.qk_norm, False,
-                ["cross_attn.norm_k_img.weight"], ca)
-        wgrad(dkvi, ctxi, ["cross_attn.k_img.weight", "cross_attn.v_img.weight"])
-        bgrad(dkvi, ["cross_attn.k_img.bias", "cross_attn.v_img.bias"])
-        _dgrad_ctx(dkvi, P["wkv_iT"], st.d_ctx, 0, n_img)
+        if need_ctx:
+            Ri = B * n_img
+            ctxi = fc.ctx[:, :n_img].contiguous().view(Ri, d) if train else None
+            dkvi = bf(Ri, 2 * d)
+            ops.cast_bf16_strided(dki, dkvi[:, :d])
+            ops.cast_bf16_strided(dvi, dkvi[:, d:])
+            rms_bwd(ptr(S["kfi"]), False, d, ptr(dkvi), 2 * d, Ri, [ca._norm_w("norm_k_img")], ca.qk_norm, False,
+                    ["cross_attn.norm_k_img.weight"], ca)
+            wgrad(dkvi, ctxi, ["cross_attn.k_img.weight", "cross_attn.v_img.weight"])
+            bgrad(dkvi, ["cross_attn.k_img.bias", "cross_attn.v_img.bias"])
+            _dgrad_ctx(dkvi, P["wkv_iT"], st.d_ctx, 0, n_img)
         del dq32, dk32, dv32, dqi, dki, dvi
     rms_bwd(ptr(S["qcb"]), True, d, ptr(dqc), d, R, [ca._norm_w("norm_q")], ca.qk_norm, False, ["cross_attn.norm_q.weight"], ca)
     h3 = S["h3"]
@@ -947,7 +962,9 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
                 ["cross_attn.norm_k.weight"], ca, defer=False)
         bgrad(dkv, ["cross_attn.k.bias", "cross_attn.v.bias"], now=True)
         _dgrad_ctx(dkv, P["wkv_cT"], st.d_ctx, n_img, Lt)
-    if _SIDE_KV and not i2v:
+    if not need_ctx:
+        pass                                                         # frozen block, nobody reads the context gradient
+    elif _SIDE_KV and not i2v and train:
         _on_side(dev, kv_path, (dkv, S["kf"], st.d_ctx, arena.buf, fc.ctx))
     else:
         kv_path()
@@ -1055,6 +1072,14 @@ def keep_activations(model, rows, device, batch=1):
     return need < 0.5 * (free - pending_step_bytes(model))
 
 
+def _no_double_backward():
+    """The hand-written backward is not itself differentiable: under ``create_graph=True`` its results would come back
+    detached from the graph the caller asked for — refuse instead of returning gradients that silently lack theirs."""
+    if torch.is_grad_enabled():
+        raise RuntimeError("WanModel's backward runs hand-written kernels and cannot be differentiated again: "
+                           "backward(create_graph=True) / double backward through the model is not supported")
+
+
 # ----------------------------------------------------------------------------- block node
 class _BlockFn(torch.autograd.Function):
 
@@ -1074,6 +1099,7 @@ class _BlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx_out):
+        _no_double_backward()
         (x0,) = ctx.saved_tensors
         model, st, idx = ctx.model, ctx.st, ctx.idx
         blk = model.blocks[idx]
@@ -1168,6 +1194,7 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
+        _no_double_backward()
         (x,) = ctx.saved_tensors
         model, st, grids = ctx.model, ctx.st, ctx.grids
         head = model.head
@@ -1190,7 +1217,9 @@ class _HeadFn(torch.autograd.Function):
             w, _ = head._packed.get("head", (head.head.weight, head.head.bias), lambda: (
                 ops.cast_bf16(head.head.weight.detach().float().contiguous()),
                 head.head.bias.detach().float().contiguous()))
-            gw, gb_ = _wgrad(dtok, hh), _bgrad(dtok)
+            # (a frozen head — a frozen backbone differentiated w.r.t. its input — has no weight gradient to form)
+            gw = _wgrad(dtok, hh) if head.head.weight.requires_grad else None
+            gb_ = _bgrad(dtok) if head.head.bias.requires_grad else None
             dhh = _dgrad(dtok, _wT(head, "head", w))
             dx = torch.zeros(R, d, dtype=torch.float32, device=dev)
             d_hb = torch.zeros(B, 2, d, dtype=torch.float32, device=dev)
@@ -1221,9 +1250,11 @@ def _embed_params(model):
     return out
 
 
-def _img_emb_backward(model, clip_fea, d_img, g):
+def _img_emb_backward(model, clip_fea, d_img, g, tr=lambda name: True):
     """Backward of MLPProj (model.py:362-374: LayerNorm, Linear, GELU(erf), Linear, LayerNorm) on the CLIP tokens:
-    recompute keeping the pre-activations, then the chain rule.  d_img fp32 [B*257, dim] = gradient of its output."""
+    recompute keeping the pre-activations, then the chain rule.  d_img fp32 [B*257, dim] = gradient of its output.
+    ``tr(name)``: does that parameter want a gradient (weight-gradient products of frozen ones are not launched).
+    Returns the gradient w.r.t. the CLIP tokens, fp32 [B*257, 1280]."""
     proj = model.img_emb.proj
     ln0, l1, l3, ln4 = proj[0], proj[1], proj[3], proj[4]
     dev = d_img.device
@@ -1244,22 +1275,57 @@ def _img_emb_backward(model, clip_fea, d_img, g):
                                    ptr(db4), 0, rows)
     dz3b = ops.cast_bf16(dz3)
     g["img_emb.proj.4.weight"], g["img_emb.proj.4.bias"] = dw4, db4
-    g["img_emb.proj.3.weight"], g["img_emb.proj.3.bias"] = _wgrad(dz3b, g1), _bgrad(dz3b)
+    if tr("img_emb.proj.3.weight"):
+        g["img_emb.proj.3.weight"] = _wgrad(dz3b, g1)
+    if tr("img_emb.proj.3.bias"):
+        g["img_emb.proj.3.bias"] = _bgrad(dz3b)
     dg1 = ops.gemm(dz3b, _wT_once(w3), epilogue=EPI_BF16)
     dz1 = ops.gelu_erf_bwd(dg1, z1)
-    g["img_emb.proj.1.weight"], g["img_emb.proj.1.bias"] = _wgrad(dz1, h0), _bgrad(dz1)
+    if tr("img_emb.proj.1.weight"):
+        g["img_emb.proj.1.weight"] = _wgrad(dz1, h0)
+    if tr("img_emb.proj.1.bias"):
+        g["img_emb.proj.1.bias"] = _bgrad(dz1)
     dh0 = _dgrad(dz1, _wT_once(w1))
-    dx = torch.zeros(rows, cin, dtype=torch.float32, device=dev)      # (gradient w.r.t. the CLIP tokens: not needed)
+    dx = torch.zeros(rows, cin, dtype=torch.float32, device=dev)      # the gradient w.r.t. the CLIP tokens
     dw0, db0 = torch.zeros(cin, dtype=torch.float32, device=dev), torch.zeros(cin, dtype=torch.float32, device=dev)
     ops.layernorm_modulate_bwd_raw(ptr(x), ptr(dh0), ptr(dx), rows, cin, ln0.eps, 0.0, ptr(w0), None, 0, ptr(dw0),
                                    ptr(db0), 0, rows)
     g["img_emb.proj.0.weight"], g["img_emb.proj.0.bias"] = dw0, db0
+    return dx
+
+
+def _flatten_input(v):
+    """An input of WanModel.forward as direct arguments of the embed node, so that autograd sees it: (tensors, n) — a list
+    of n tensors as it is, one batched tensor as itself with n = -1, None as nothing with n = None."""
+    if v is None:
+        return [], None
+    if isinstance(v, torch.Tensor):
+        return [v], -1
+    v = list(v)
+    return v, len(v)
 
 
 class _EmbedFn(torch.autograd.Function):
+    """Arguments: model, state, seq_len, layout = (n_x, n_y, n_context) of _flatten_input, then the tensors themselves —
+    x, y, context (flattened), clip_fea, t, the extra condition tokens — and the embedding parameters.  The reference
+    differentiates WanModel.forward w.r.t. all of them (model.py:502-563 is plain autograd); each input gradient is
+    computed only when ``needs_input_grad`` asks for it."""
+    N_FIXED = 4
 
     @staticmethod
-    def forward(ctx, model, st, x_list, t, context, seq_len, clip_fea, y, extra_tokens, *params):
+    def forward(ctx, model, st, seq_len, layout, *flat):
+        pos, groups = 0, []
+        for n in layout:
+            cnt = 0 if n is None else 1 if n == -1 else n
+            groups.append((pos, cnt, n))
+            pos += cnt
+        clip_fea, t, extra_tokens = flat[pos:pos + 3]
+        ctx.groups, ctx.pos_rest = groups, pos
+
+        def unpack(k):
+            p0, cnt, n = groups[k]
+            return None if n is None else list(flat[p0].unbind(0)) if n == -1 else list(flat[p0:p0 + cnt])
+        x_list, y, context = unpack(0), unpack(1), unpack(2)
         with torch.no_grad():
             xs, e, fc, grids, lens, ctx_lens = model._embed(x_list, t, context, seq_len, clip_fea, y, extra_tokens)
         ctx.n_extra = 0 if extra_tokens is None else int(extra_tokens.shape[1])
@@ -1272,16 +1338,31 @@ class _EmbedFn(torch.autograd.Function):
         st.d_ctx = torch.zeros(B, fc.Lc, d, dtype=torch.float32, device=dev)
         ctx.model, ctx.st = model, st
         ctx.inputs = (x_list, t, context, seq_len, y, clip_fea)
+        ctx.batched = tuple(None if flat_n != -1 else flat[p0].shape for p0, _, flat_n in groups)
         return xs
 
     @staticmethod
     def backward(ctx, dxs):
+        _no_double_backward()
         model, st = ctx.model, ctx.st
         x_list, t, context, seq_len, y, clip_fea = ctx.inputs
         fc = st.fc
         B, d = fc.B, fc.dim
         dev = dxs.device
         g = {}
+        named = _embed_params(model)
+        trainable = {n for n, p in named if p.requires_grad}
+        tr = trainable.__contains__
+        needs = ctx.needs_input_grad[_EmbedFn.N_FIXED:]
+        groups, pos = ctx.groups, ctx.pos_rest
+        gin = [None] * (pos + 3)                                     # gradients of the flattened inputs, clip_fea, t, tokens
+
+        def wanted(k):
+            """Per sample: does element b of input group k (x, y, context) want a gradient."""
+            p0, cnt, n = groups[k]
+            return [False] * B if n is None else [bool(needs[p0])] * B if n == -1 else [bool(needs[p0 + b]) for b in range(B)]
+        need_x, need_y, need_c = wanted(0), wanted(1), wanted(2)
+        need_clip, need_t = bool(needs[pos]) and clip_fea is not None, bool(needs[pos + 1])
         with torch.no_grad():
             _wgrad_join(dev)            # st.d_ctx, st.d_e0: the blocks' second-stream work adds into them
             dxs = dxs.contiguous().float()
@@ -1289,63 +1370,117 @@ class _EmbedFn(torch.autograd.Function):
             pt, ph, pw = model.patch_size
             kin = model.in_dim * pt * ph * pw
             Kp = _ru(kin, 8)
-            if y is not None:
-                x_list = [torch.cat([u, v], dim=0) for u, v in zip(x_list, y)]
-            dW = torch.zeros(d, Kp, dtype=torch.float32, device=dev)
-            db = torch.zeros(d, dtype=torch.float32, device=dev)
+            w_pe, b_pe = tr("patch_embedding.weight"), tr("patch_embedding.bias")
+            dW = torch.zeros(d, Kp, dtype=torch.float32, device=dev) if w_pe else None
+            db = torch.zeros(d, dtype=torch.float32, device=dev) if b_pe else None
+            wpeT = None
+            gx = [None if shp is None else torch.empty(shp, dtype=torch.float32, device=dev) if any(nd) else None
+                  for shp, nd in zip(ctx.batched[:2], (need_x, need_y))]      # batched x / y: one gradient tensor
             for b, u in enumerate(x_list):
                 n = st.lens[b]
-                tok = ops.patchify(u.to(device=dev, dtype=torch.float32).contiguous(), model.patch_size, Kp)
-                dxb = ops.cast_bf16(dxs[b, :n].contiguous())
-                ops.gemm_tn(dxb, tok, out=dW, accumulate=True)
-                ops.colsum_accum(dxs[b, :n], db)
-            g["patch_embedding.weight"] = dW[:, :kin].contiguous()
+                dxb = ops.cast_bf16(dxs[b, :n].contiguous()) if (w_pe or need_x[b] or need_y[b]) else None
+                if w_pe:
+                    full = u if y is None else torch.cat([u, y[b]], dim=0)
+                    tok = ops.patchify(full.to(device=dev, dtype=torch.float32).contiguous(), model.patch_size, Kp)
+                    ops.gemm_tn(dxb, tok, out=dW, accumulate=True)
+                if b_pe:
+                    ops.colsum_accum(dxs[b, :n], db)
+                if need_x[b] or need_y[b]:
+                    # the latent's gradient: dtok = bf16(dxs) Wpe on the dgrad GEMM (fp32 out), then the adjoint of
+                    # patchify scatters it into x's and y's channels with one launch
+                    if wpeT is None:
+                        wpe = torch.nn.functional.pad(model.patch_embedding.weight.detach().flatten(1).float(), (0, Kp - kin))
+                        wpeT = ops.transpose_bf16(ops.cast_bf16(wpe.contiguous()))      # [Kp, d]
+                    dtok = _dgrad(dxb, wpeT)
+                    cx = u.shape[0]
+                    shape = (model.in_dim,) + tuple(u.shape[1:])
+                    want = (need_x[b], need_y[b])
+                    dst = [None, None]
+                    for k, nch in ((0, cx), (1, model.in_dim - cx)):
+                        if want[k]:
+                            dst[k] = gx[k][b] if gx[k] is not None else \
+                                torch.empty(nch, *u.shape[1:], dtype=torch.float32, device=dev)
+                    ops.patchify_bwd(dtok, st.grids[b], model.patch_size, shape, c_split=cx, out=tuple(dst))
+                    for k, src in ((0, u), (1, y[b] if y is not None else None)):
+                        if want[k] and gx[k] is None:
+                            gin[groups[k][0] + b] = dst[k].to(device=src.device, dtype=src.dtype)
+            for k in (0, 1):
+                if gx[k] is not None:
+                    src = (x_list, y)[k][0]
+                    gin[groups[k][0]] = gx[k].to(device=src.device, dtype=src.dtype)
+            if w_pe:
+                g["patch_embedding.weight"] = dW[:, :kin].contiguous()
             g["patch_embedding.bias"] = db
             # ---- time embedding (fp32): z0 = W0 sin + b0 ; e = W2 silu(z0) + b2 ; e0 = Wp silu(e) + bp
-            te0, te2, tp1 = model.time_embedding[0], model.time_embedding[2], model.time_projection[1]
-            W0, W2, Wp = (m.weight.detach().float().contiguous() for m in (te0, te2, tp1))
-            sin = ops.sinusoidal_embedding(t.to(dev), model.freq_dim)
-            z0 = ops.dense_f32(sin, W0, te0.bias.detach().float(), 0, 0)
-            e = st.e
-            dWp, dbp = torch.zeros_like(Wp), torch.zeros(Wp.shape[0], dtype=torch.float32, device=dev)
-            ops.dense_f32_bwd(e, Wp, st.d_e0.view(B, 6 * d), dW=dWp, db=dbp, dx=st.d_e, dx_accumulate=True, act_in=1)
-            dW2, db2 = torch.zeros_like(W2), torch.zeros(d, dtype=torch.float32, device=dev)
-            dz0 = torch.empty(B, d, dtype=torch.float32, device=dev)
-            ops.dense_f32_bwd(z0, W2, st.d_e, dW=dW2, db=db2, dx=dz0, act_in=1)
-            dW0, db0 = torch.zeros_like(W0), torch.zeros(d, dtype=torch.float32, device=dev)
-            ops.dense_f32_bwd(sin, W0, dz0, dW=dW0, db=db0, dx=None, act_in=0)
-            g.update({"time_projection.1.weight": dWp, "time_projection.1.bias": dbp, "time_embedding.2.weight": dW2,
-                      "time_embedding.2.bias": db2, "time_embedding.0.weight": dW0, "time_embedding.0.bias": db0})
+            if need_t or any(n.startswith(("time_embedding.", "time_projection.")) for n in trainable):
+                te0, te2, tp1 = model.time_embedding[0], model.time_embedding[2], model.time_projection[1]
+                W0, W2, Wp = (m.weight.detach().float().contiguous() for m in (te0, te2, tp1))
+                t_dev = t.to(dev)
+                sin = ops.sinusoidal_embedding(t_dev, model.freq_dim)
+                z0 = ops.dense_f32(sin, W0, te0.bias.detach().float(), 0, 0)
+                e = st.e
+                dWp, dbp = torch.zeros_like(Wp), torch.zeros(Wp.shape[0], dtype=torch.float32, device=dev)
+                ops.dense_f32_bwd(e, Wp, st.d_e0.view(B, 6 * d), dW=dWp, db=dbp, dx=st.d_e, dx_accumulate=True, act_in=1)
+                dW2, db2 = torch.zeros_like(W2), torch.zeros(d, dtype=torch.float32, device=dev)
+                dz0 = torch.empty(B, d, dtype=torch.float32, device=dev)
+                ops.dense_f32_bwd(z0, W2, st.d_e, dW=dW2, db=db2, dx=dz0, act_in=1)
+                dW0, db0 = torch.zeros_like(W0), torch.zeros(d, dtype=torch.float32, device=dev)
+                dsin = torch.empty(B, model.freq_dim, dtype=torch.float32, device=dev) if need_t else None
+                ops.dense_f32_bwd(sin, W0, dz0, dW=dW0, db=db0, dx=dsin, act_in=0)
+                if need_t:
+                    gin[pos + 1] = ops.sinusoidal_embedding_bwd(dsin, t_dev).view(t.shape).to(device=t.device, dtype=t.dtype)
+                g.update({"time_projection.1.weight": dWp, "time_projection.1.bias": dbp, "time_embedding.2.weight": dW2,
+                          "time_embedding.2.bias": db2, "time_embedding.0.weight": dW0, "time_embedding.0.bias": db0})
             # ---- text embedding: ctx = W2t gelu(W0t cin + b0t) + b2t
-            ctx_in = torch.zeros(B, model.text_len, model.text_dim, dtype=torch.float32, device=dev)
-            for b, u in enumerate(context):
-                ctx_in[b, :u.shape[0]] = u.to(device=dev, dtype=torch.float32)
-            t0, t2 = model.text_embedding[0], model.text_embedding[2]
-            w0 = ops.cast_bf16(t0.weight.detach().float().contiguous())
-            w2 = ops.cast_bf16(t2.weight.detach().float().contiguous())
-            cin = ops.cast_bf16(ctx_in).view(B * model.text_len, model.text_dim)
-            pre = ops.gemm(cin, w0, bias=t0.bias.detach().float(), epilogue=EPI_BF16)
-            gl = ops.gelu_tanh(pre)
             n_img = fc.Lc - model.text_len
-            dctx = st.d_ctx[:, n_img:].contiguous().view(B * model.text_len, d)
-            dctx_b = ops.cast_bf16(dctx)
-            g["text_embedding.2.weight"], g["text_embedding.2.bias"] = _wgrad(dctx_b, gl), _bgrad(dctx_b)
-            dgl = ops.gemm(dctx_b, _wT_once(w2), epilogue=EPI_BF16)
-            dpre = ops.gelu_tanh_bwd(dgl, pre)
-            g["text_embedding.0.weight"], g["text_embedding.0.bias"] = _wgrad(dpre, cin), _bgrad(dpre)
+            if any(tr(f"text_embedding.{n}") for n in ("0.weight", "0.bias", "2.weight", "2.bias")) or any(need_c):
+                ctx_in = torch.zeros(B, model.text_len, model.text_dim, dtype=torch.float32, device=dev)
+                for b, u in enumerate(context):
+                    ctx_in[b, :u.shape[0]] = u.to(device=dev, dtype=torch.float32)
+                t0, t2 = model.text_embedding[0], model.text_embedding[2]
+                w0 = ops.cast_bf16(t0.weight.detach().float().contiguous())
+                w2 = ops.cast_bf16(t2.weight.detach().float().contiguous())
+                cin = ops.cast_bf16(ctx_in).view(B * model.text_len, model.text_dim)
+                pre = ops.gemm(cin, w0, bias=t0.bias.detach().float(), epilogue=EPI_BF16)
+                dctx = st.d_ctx[:, n_img:].contiguous().view(B * model.text_len, d)
+                dctx_b = ops.cast_bf16(dctx)
+                if tr("text_embedding.2.weight"):
+                    g["text_embedding.2.weight"] = _wgrad(dctx_b, ops.gelu_tanh(pre))
+                if tr("text_embedding.2.bias"):
+                    g["text_embedding.2.bias"] = _bgrad(dctx_b)
+                dgl = ops.gemm(dctx_b, _wT_once(w2), epilogue=EPI_BF16)
+                dpre = ops.gelu_tanh_bwd(dgl, pre)
+                if tr("text_embedding.0.weight"):
+                    g["text_embedding.0.weight"] = _wgrad(dpre, cin)
+                if tr("text_embedding.0.bias"):
+                    g["text_embedding.0.bias"] = _bgrad(dpre)
+                if any(need_c):
+                    # the raw text features' gradient: dpre W0t, fp32, cut to each sample's true length
+                    dcin = _dgrad(dpre, _wT_once(w0)).view(B, model.text_len, -1)[..., :model.text_dim]
+                    p0, cnt, n = groups[2]
+                    if n == -1:
+                        full = torch.zeros(ctx.batched[2], dtype=torch.float32, device=dev)
+                        L = min(full.shape[1], model.text_len)
+                        full[:, :L] = dcin[:, :L]
+                        gin[p0] = full.to(device=context[0].device, dtype=context[0].dtype)
+                    else:
+                        for b, u in enumerate(context):
+                            if need_c[b]:
+                                gin[p0 + b] = dcin[b, :u.shape[0]].to(device=u.device, dtype=u.dtype)
             # ---- image embedding (i2v): the first n_img context rows came from img_emb(clip_fea)
-            if n_img and clip_fea is not None:
-                _img_emb_backward(model, clip_fea, st.d_ctx[:, :n_img].contiguous().view(B * n_img, d), g)
+            if n_img and clip_fea is not None and (need_clip or any(n.startswith("img_emb.") for n in trainable)):
+                dclip = _img_emb_backward(model, clip_fea, st.d_ctx[:, :n_img].contiguous().view(B * n_img, d), g, tr)
+                if need_clip:
+                    gin[pos] = dclip.view(clip_fea.shape).to(device=clip_fea.device, dtype=clip_fea.dtype)
         out = []
-        for n, p in _embed_params(model):
+        for n, p in named:
             gg = g.get(n) if p.requires_grad else None
             out.append(None if gg is None else gg.view(p.shape).to(p.dtype))
         # condition tokens of the OmniHuman adapters (omnihuman_wan_t2v.py:453-488): they sit in front of the text
         # in the context, so their gradient is the leading rows of the context gradient
-        d_extra = None
-        if ctx.n_extra and ctx.needs_input_grad[8]:
-            d_extra = st.d_ctx[:, :ctx.n_extra].contiguous().to(ctx.extra_dtype)
-        return (None, None, None, None, None, None, None, None, d_extra, *out)
+        if ctx.n_extra and needs[pos + 2]:
+            gin[pos + 2] = st.d_ctx[:, :ctx.n_extra].contiguous().to(ctx.extra_dtype)
+        return (None, None, None, None, *gin, *out)
 
 
 def forward_train(model, x, t, context, seq_len, clip_fea=None, y=None, extra_conditions=None):
@@ -1360,10 +1495,16 @@ def forward_train(model, x, t, context, seq_len, clip_fea=None, y=None, extra_co
     # forwards of this model whose backward has not run yet: with more than one of them in a pass the
     # engine sums their contributions to a shared parameter on the main stream, so none of them may defer its join
     model.__dict__.setdefault("_omh_live_states", weakref.WeakSet()).add(st)
-    x_list = list(x) if not isinstance(x, (list, tuple)) else list(x)
-    eparams = [p for _, p in _embed_params(model)]
+    named = _embed_params(model)
+    eparams = [p for _, p in named]
     tok = extra_conditions.get("tokens") if isinstance(extra_conditions, dict) else extra_conditions
-    xs = _EmbedFn.apply(model, st, x_list, t, list(context), seq_len, clip_fea, y, tok, *eparams)
+    # the tensor inputs go to the embed node as direct arguments (inside a list autograd would not see them)
+    (fx, nx), (fy, ny), (fctx, nc) = _flatten_input(x), _flatten_input(y), _flatten_input(context)
+    # does anybody read the context gradient the blocks accumulate (st.d_ctx): the text / image embedding's parameters,
+    # the raw context, the CLIP tokens, the condition tokens — a frozen block skips its share of it otherwise
+    st.need_ctx = any(p.requires_grad for n, p in named if n.startswith(("text_embedding.", "img_emb."))) or \
+        any(isinstance(u, torch.Tensor) and u.requires_grad for u in (*fctx, clip_fea, tok))
+    xs = _EmbedFn.apply(model, st, seq_len, (nx, ny, nc), *fx, *fy, *fctx, clip_fea, t, tok, *eparams)
     if not xs.requires_grad:
         xs.requires_grad_(True)          # keeps the chain alive when the embed parameters are frozen
     st.keep = keep_activations(model, xs.shape[0] * xs.shape[1], xs.device, batch=xs.shape[0])
