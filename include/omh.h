@@ -294,6 +294,20 @@ int64_t omh_flash_attn_bwd_workspace_bytes(const omh_attn_bwd_args* args);
    The workspace is declined (never split); no atomics: repeatable bit for bit. */
 int omh_flash_attn_bwd_band_d128(const omh_attn_bwd_args* args, int32_t window_left, int32_t window_right,
                                  omh_stream_t stream);
+/* Additive to ABI v12 as well: the backward of omh_flash_attn_fwd_d128 for ANY combination of q_lens, k_lens and band
+   (what autograd through flash-attn's varlen call gives the reference, attention.py:96-127).  `q_lens`: int32 [B] device
+   pointer or NULL.  Per sample  qlen = clamp(q_lens[b], 0, Lq)  (Lq when q_lens is NULL), klen as above; query i < qlen
+   sees key j < klen iff  i + (klen - qlen) - window_left <= j <= i + (klen - qlen) + window_right  (a side < 0
+   unbounded; (-1, -1) with q_lens = full attention over the first qlen rows).
+   Rows i >= qlen DO NOT EXIST, as in flash-attn's packed batch: their dq is written as exact zeros, they contribute
+   nothing to dk / dv, and their dout, q, lse and o32 values are never used — the loads and the delta are predicated,
+   so the result is the same when those rows hold NaN (delta is written as 0 there).  Keys no live query reaches (keys
+   past k_lens included) get dk = dv = 0, written; live rows with an empty band get dq = 0.
+   Everything else as for the band entry: o32 REQUIRED, phases 0..3, out_bf16, q_prescaled; the workspace is declined
+   (never split); no atomics: repeatable bit for bit.  With q_lens == NULL the call IS omh_flash_attn_bwd_band_d128
+   (the same kernels, the same bits); a q_lens that holds Lq everywhere gives those bits too. */
+int omh_flash_attn_bwd_varlen_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, int32_t window_left,
+                                   int32_t window_right, omh_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * LayerNorm (no affine) fused with adaLN modulation, fp32 in -> bf16 out.

@@ -181,6 +181,7 @@ _SIGS = {
     "omh_flash_attn_bwd_d128": (i32, [C.POINTER(AttnBwdArgs), vp]),
     "omh_flash_attn_bwd_workspace_bytes": (i64, [C.POINTER(AttnBwdArgs)]),
     "omh_flash_attn_bwd_band_d128": (i32, [C.POINTER(AttnBwdArgs), i32, i32, vp]),
+    "omh_flash_attn_bwd_varlen_d128": (i32, [C.POINTER(AttnBwdArgs), vp, i32, i32, vp]),
     "omh_layernorm_modulate": (i32, [vp, vp, i64, i32, f32, f32, vp, vp, i64, vp, vp, i64, i64, vp]),
     "omh_rmsnorm_rope": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, vp]),
     "omh_rmsnorm_rope_bf16": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, f32, vp]),

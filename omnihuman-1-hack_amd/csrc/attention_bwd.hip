@@ -390,7 +390,7 @@ void attn_bwd_dq_kernel(const omh_attn_bwd_args p, const int q_blocks) {
 
 // attention_bwd2.hip: the round-3 kernel pair (needs the forward's fp32 output for delta), and its band form
 int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s);
-int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, hipStream_t s);
+int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, hipStream_t s);
 
 static bool bwd_ptrs_set(const omh_attn_bwd_args& a) {
     return a.q && a.k && a.v && a.dout && a.lse && a.delta && a.dq && a.dk && a.dv;
@@ -413,7 +413,20 @@ extern "C" int omh_flash_attn_bwd_band_d128(const omh_attn_bwd_args* args, int32
     const int rc0 = bwd2_check(*args);
     if (rc0) return rc0;
     omh_clear_status();
-    const int rc = omh_launch_attn_bwd2_band(*args, window_left, window_right, (hipStream_t)stream);
+    const int rc = omh_launch_attn_bwd2_band(*args, window_left, window_right, nullptr, (hipStream_t)stream);
+    return rc ? rc : omh_launch_status();
+}
+
+// the band entry with the forward's q_lens: the same argument rules; q_lens is a device pointer the kernels clamp to
+// [0, Lq] themselves (NULL: the band entry's kernels)
+extern "C" int omh_flash_attn_bwd_varlen_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, int32_t window_left,
+                                              int32_t window_right, omh_stream_t stream) {
+    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
+    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
+    const int rc0 = bwd2_check(*args);
+    if (rc0) return rc0;
+    omh_clear_status();
+    const int rc = omh_launch_attn_bwd2_band(*args, window_left, window_right, q_lens, (hipStream_t)stream);
     return rc ? rc : omh_launch_status();
 }
 

@@ -158,8 +158,11 @@ __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 
 // an fma chain over the lane's 8 channels, then a fixed butterfly over the 16 lanes — one arithmetic, whatever the
 // phase (round 3 had a second copy of it in the dQ kernel's prologue and a 38 us LDS-staged kernel here; 57 MB at
 // 4 clips: ~12 us of traffic).
+// VLEN (omh_flash_attn_bwd_varlen_d128): rows at or past q_lens[b] do not exist — their dO / o32 are not read (they may
+// hold NaN) and their delta is written as zero.
+template <bool VLEN>
 __global__ __launch_bounds__(256)
-void attn_bwd2_delta_kernel(const omh_attn_bwd_args p) {
+void attn_bwd2_delta_kernel(const omh_attn_bwd_args p, const int32_t* __restrict__ q_lens) {
     const int tid = threadIdx.x;
     const uint32_t npairs = (uint32_t)p.B * (uint32_t)p.Lq * (uint32_t)p.H;      // < 2^31: checked by the launcher
     const uint32_t pair = blockIdx.x * 16u + (uint32_t)(tid >> 4);
@@ -172,15 +175,19 @@ void attn_bwd2_delta_kernel(const omh_attn_bwd_args p) {
         head = (int)(pair - row * (uint32_t)p.H);
         b = (int)(row / (uint32_t)p.Lq);
         q = (int)(row - (uint32_t)b * (uint32_t)p.Lq);
-        const int64_t off = (int64_t)b * p.o_bs + (int64_t)q * p.o_rs + head * D + sub * 8;
-        const uint4 dw = *(const uint4*)((const uint16_t*)p.dout + off);
-        const float4 o0 = *(const float4*)(p.o32 + off);
-        const float4 o1 = *(const float4*)(p.o32 + off + 4);
-        del = bf_lo(dw.x) * o0.x;
-        del = fmaf(bf_hi(dw.x), o0.y, del);
-        del = fmaf(bf_lo(dw.y), o0.z, del); del = fmaf(bf_hi(dw.y), o0.w, del);
-        del = fmaf(bf_lo(dw.z), o1.x, del); del = fmaf(bf_hi(dw.z), o1.y, del);
-        del = fmaf(bf_lo(dw.w), o1.z, del); del = fmaf(bf_hi(dw.w), o1.w, del);
+        bool live = true;
+        if constexpr (VLEN) live = q < min(max(q_lens[b], 0), p.Lq);
+        if (live) {
+            const int64_t off = (int64_t)b * p.o_bs + (int64_t)q * p.o_rs + head * D + sub * 8;
+            const uint4 dw = *(const uint4*)((const uint16_t*)p.dout + off);
+            const float4 o0 = *(const float4*)(p.o32 + off);
+            const float4 o1 = *(const float4*)(p.o32 + off + 4);
+            del = bf_lo(dw.x) * o0.x;
+            del = fmaf(bf_hi(dw.x), o0.y, del);
+            del = fmaf(bf_lo(dw.y), o0.z, del); del = fmaf(bf_hi(dw.y), o0.w, del);
+            del = fmaf(bf_lo(dw.z), o1.x, del); del = fmaf(bf_hi(dw.z), o1.y, del);
+            del = fmaf(bf_lo(dw.w), o1.z, del); del = fmaf(bf_hi(dw.w), o1.w, del);
+        }
     }
     del += __shfl_xor(del, 1, 64);
     del += __shfl_xor(del, 2, 64);
@@ -203,9 +210,15 @@ struct BwdSplit {
 // qlen = Lq): query i sees key j iff i + shift - wl <= j <= i + shift + wr, shift = klen - Lq, a side < 0 unbounded.  The
 // workgroup loops over the key tiles that meet the band of its live rows only and masks every score against its row's
 // band (key_lo, key_hi) — a separate instantiation: the full-attention kernel keeps its instruction stream.  Never split.
-template <bool PRE, bool WIN>
+// VLEN (with WIN; omh_flash_attn_bwd_varlen_d128): the forward's qlen = clamp(q_lens[b], 0, Lq) in place of Lq — it sets
+// the live rows of the workgroup, the shift and with them the key tiles of the loop.  Rows at or past qlen do not exist:
+// their q / dO / lse / delta are not read and their dQ is stored as zeros.  A third instantiation: the band kernels
+// keep their instruction streams too.
+template <bool PRE, bool WIN, bool VLEN = false>
 __global__ __launch_bounds__(256, 2)
-void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk, const int wl, const int wr) {
+void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk, const int wl, const int wr,
+                         const int32_t* __restrict__ q_lens) {
+    static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][K tile | V tile]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
     const bool worker = (int)blockIdx.x >= wk.n_regular;
@@ -230,14 +243,16 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     const uint16_t* K = (const uint16_t*)p.k + (int64_t)b * p.k_bs + head * D;
     const uint16_t* V = (const uint16_t*)p.v + (int64_t)b * p.k_bs + head * D;
     const int q_row = qb * 128 + wave * 32 + li;
-    const bool q_ok = q_row < p.Lq;
+    int qlen = p.Lq;
+    if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
+    const bool q_ok = q_row < qlen;
     int key_lo = 0, key_hi = klen - 1;                               // WIN: this lane's (query row's) band of keys
     if constexpr (WIN) {
-        const int shift = klen - p.Lq;
-        const int q0 = qb * 128, q1 = min(q0 + 128, p.Lq) - 1;      // live query rows of this workgroup
+        const int shift = klen - qlen;
+        const int q0 = qb * 128, q1 = min(q0 + 128, qlen) - 1;      // live query rows of this workgroup
         const int lo = wl < 0 ? 0 : max(0, q0 + shift - wl);
         const int hi = wr < 0 ? klen - 1 : min(klen - 1, q1 + shift + wr);
-        if (hi < lo) {
+        if (hi < lo || (VLEN && q1 < q0)) {
             n_tiles = 0;
         } else {
             t_first = lo / TB;
@@ -350,7 +365,13 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
                     make_float4(dq[db][4 * g], dq[db][4 * g + 1], dq[db][4 * g + 2], dq[db][4 * g + 3]);
         return;
     }
-    if (q_ok) {
+    if constexpr (VLEN) {                                            // (a select: rows past qlen are exact zeros)
+#pragma unroll
+        for (int db = 0; db < 4; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dq[db][r] = q_ok ? dq[db][r] : 0.f;
+    }
+    if (VLEN ? q_row < p.Lq : q_ok) {
         const int64_t eo = (int64_t)b * p.dq_bs + (int64_t)q_row * p.dq_rs + head * D;
         if (p.out_bf16) {
             uint16_t* DQ = (uint16_t*)p.dq + eo;
@@ -434,9 +455,14 @@ __device__ __forceinline__ void dkdv_store(const omh_attn_bwd_args& p, const Bwd
 //
 // WIN: the band (see attn_bwd2_dq_kernel).  Key j is reached by queries [j - shift - wr, j - shift + wl]: the workgroup loops over
 // the query tiles that meet the union of its live keys' ranges, and every score is masked against its key's range.
-template <int WAVES, int KPW, bool PRE, bool WIN>
+// VLEN (see attn_bwd2_dq_kernel): the ranges end at qlen - 1.  The Q / dO tiles come through buffer descriptors that end
+// at row qlen, so rows past it arrive in LDS as zeros whatever memory holds (NaN included); their lse / delta are not
+// read (parked as -inf / 0).
+template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false>
 __global__ __launch_bounds__(64 * WAVES, 1)
-void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk, const int wl, const int wr) {
+void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk, const int wl, const int wr,
+                           const int32_t* __restrict__ q_lens) {
+    static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
     constexpr int THREADS = 64 * WAVES;
     static_assert(WAVES * KPW == 4, "a workgroup covers 128 keys");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][Q tile | dO tile] + lse/delta
@@ -457,12 +483,14 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         n_tiles = min(t_first + per, n_tiles_all) - t_first;
     }
     int q_lo = 0, q_hi = 0;                                          // WIN: this lane's (key's) range of queries
+    int qlen = p.Lq;
+    if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
     if constexpr (WIN) {
         static_assert(KPW == 1, "one key per lane");
-        const int shift = klen - p.Lq;
+        const int shift = klen - qlen;
         const int k0 = kb * 128, k1 = min(k0 + 128, klen) - 1;      // live keys of this workgroup
         const int lo = wr < 0 ? 0 : max(0, k0 - shift - wr);
-        const int hi = wl < 0 ? p.Lq - 1 : min(p.Lq - 1, k1 - shift + wl);
+        const int hi = wl < 0 ? qlen - 1 : min(qlen - 1, k1 - shift + wl);
         if (k1 < k0 || hi < lo) {
             n_tiles = 0;
         } else {
@@ -472,7 +500,9 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         const int key = kb * 128 + wave * 32 + li;
         q_lo = wr < 0 ? -(1 << 30) : key - shift - wr;
         q_hi = wl < 0 ? (1 << 30) : key - shift + wl;
+        if constexpr (VLEN) q_hi = min(q_hi, qlen - 1);
     }
+    const int q_rows = VLEN ? max(qlen, 1) : p.Lq;                   // rows the Q / dO / lse / delta reads may touch
 
     const uint16_t* Q = (const uint16_t*)p.q + (int64_t)b * p.q_bs + head * D;
     const uint16_t* DO = (const uint16_t*)p.dout + (int64_t)b * p.o_bs + head * D;
@@ -497,7 +527,7 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     const float ds_scale = PRE ? (1.0f / LOG2E) : p.scale;               // dK = dS^T q' / log2(e) on a pre-scaled q
 
     const FragAddr fa = frag_addr(lane);
-    const TileSrc qs = tile_src<THREADS>(Q, p.Lq, p.q_rs, tid), dos = tile_src<THREADS>(DO, p.Lq, p.o_rs, tid);
+    const TileSrc qs = tile_src<THREADS>(Q, q_rows, p.q_rs, tid), dos = tile_src<THREADS>(DO, q_rows, p.o_rs, tid);
     const uint32_t wave_lds = __builtin_amdgcn_readfirstlane(lds_addr(smem) + wave * 1024);   // stage 0, Q tile, this wave's rows
 
     f32x16 dv[KPW][4], dk[KPW][4];
@@ -513,20 +543,22 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     // branch, no arithmetic on the result — either would put the wait for them right here); stat_value turns the raw
     // numbers into the parked ones when they are stored, a tile later.
     auto stat_load = [&](int tile, float& lraw, float& draw) {
-        const int q = min(tile * TB + lane, p.Lq - 1);
+        const int q = min(tile * TB + lane, q_rows - 1);
         lraw = LSE[q];
         draw = DEL[q];
     };
     auto stat_store = [&](int tile, float lraw, float draw, float* dst) {
-        const bool in = tile * TB + lane < p.Lq;
+        const bool in = tile * TB + lane < qlen;
         dst[lane] = (in && lraw > -INFINITY) ? lraw * neg_inv_sc : -INFINITY;   // no keys / past the end: P = exp2(-inf) = 0
         dst[64 + lane] = in ? -draw : 0.f;
     };
     float gl = 0.f, gd = 0.f;
-    tile_dma<THREADS>(qs, t_first, wave_lds);                        // (a tile index past the end arrives as zeros)
-    tile_dma<THREADS>(dos, t_first, wave_lds + TILE_BYTES);
-    stat_load(t_first, gl, gd);
-    if (tid < 64) stat_store(t_first, gl, gd, stat);
+    if (!VLEN || n_tiles > 0) {                                      // VLEN: a sample with qlen = 0 has no row to fetch
+        tile_dma<THREADS>(qs, t_first, wave_lds);                    // (a tile index past the end arrives as zeros)
+        tile_dma<THREADS>(dos, t_first, wave_lds + TILE_BYTES);
+        stat_load(t_first, gl, gd);
+        if (tid < 64) stat_store(t_first, gl, gd, stat);
+    }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     for (int t = 0; t < n_tiles; ++t) {
         const unsigned char* qt = smem + (t & 1) * 2 * TILE_BYTES;
@@ -968,7 +1000,7 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
     const int64_t pairs = (int64_t)a.B * a.Lq * a.H;
     if (pairs >= 0x7fffffffLL) return OMH_E_SHAPE;
     if (a.phase == 0 || a.phase == 1) {                              // phase 0 = delta, then dQ, then dK / dV
-        hipLaunchKernelGGL(attn_bwd2_delta_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(attn_bwd2_delta_kernel<false>, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, s, a, nullptr);
         if (a.phase == 1) return 0;
     }
     // workspace: [dQ slabs | dK, dV slabs]; without (enough of) it the kernels run unsplit
@@ -986,8 +1018,8 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (bwd2_dq_stream()) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
             else hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
-        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1);
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1);
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr);
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr);
         if (wq.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<1>, dim3((wq.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, q_blocks, wq);
     }
@@ -997,18 +1029,19 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (!(e && e[0] == '0')) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
             else hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
-        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1);
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1);
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr);
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr);
         if (wkv.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<2>, dim3((wkv.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, k_blocks, wkv);
     }
     return 0;
 }
 
-// called by omh_flash_attn_bwd_band_d128 (attention_bwd.hip) with validated arguments and o32 set: the same phases as
-// omh_launch_attn_bwd2, on the WIN instantiations of the HIP kernels (the w64 streams are full-attention only); never
-// split (the entry declines the workspace).
-int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, hipStream_t s) {
+// called by omh_flash_attn_bwd_band_d128 and omh_flash_attn_bwd_varlen_d128 (attention_bwd.hip) with validated arguments
+// and o32 set: the same phases as omh_launch_attn_bwd2, on the WIN instantiations of the HIP kernels (the w64 streams are
+// full-attention only); never split (the entries decline the workspace).  VLEN: the q_lens instantiations.
+template <bool VLEN>
+static int launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, hipStream_t s) {
     if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
         ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
         return OMH_E_SHAPE;
@@ -1021,28 +1054,32 @@ int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, hipStr
     wl = wl < 0 ? -1 : (wl > wmax ? wmax : wl);
     wr = wr < 0 ? -1 : (wr > wmax ? wmax : wr);
     constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
-    static bool attr_set = false;
+    static bool attr_set = false;                                    // (one flag per instantiation of this function)
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
         attr_set = true;
     }
     if (a.phase == 0 || a.phase == 1) {
-        hipLaunchKernelGGL(attn_bwd2_delta_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(attn_bwd2_delta_kernel<VLEN>, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, s, a, q_lens);
         if (a.phase == 1) return 0;
     }
     const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
     if (a.phase == 0 || a.phase == 2) {
         const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr);
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr);
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens);
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens);
     }
     if (a.phase == 0 || a.phase == 3) {
         const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr);
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr);
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens);
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens);
     }
     return 0;
+}
+// q_lens == nullptr: the band kernels themselves (qlen = Lq), so that call is omh_flash_attn_bwd_band_d128 bit for bit
+int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, hipStream_t s) {
+    return q_lens ? launch_attn_bwd2_band<true>(a, wl, wr, q_lens, s) : launch_attn_bwd2_band<false>(a, wl, wr, nullptr, s);
 }

@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import (ATTN_ALLOW_SPLIT, ATTN_SHORT_KERNEL, BIAS_M, BIAS_N, BIAS_NONE, EPI_BF16, EPI_BF16_SPLIT_T, EPI_F32, EPI_F32_ACCUM, EPI_GELU_BF16,
                    EPI_GELU_BWD_BF16, EPI_GELU_ERF_BF16, EPI_RESID, AttnArgs, GemmArgs, OmhError, check, lib)
 
-__all__ = ["gemm", "flash_attn", "layernorm_modulate", "rmsnorm_rope", "cast_bf16", "patchify", "unpatchify",
+__all__ = ["gemm", "flash_attn", "flash_attn_func", "layernorm_modulate", "rmsnorm_rope", "cast_bf16", "patchify", "unpatchify",
            "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw",
            "softmax_rows", "OmhError",
            "EPI_BF16", "EPI_F32", "EPI_GELU_BF16", "EPI_GELU_ERF_BF16", "EPI_RESID", "EPI_F32_ACCUM", "BIAS_NONE", "BIAS_N", "BIAS_M"]
@@ -203,7 +203,7 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
 
 
 def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_prescaled=False, out=None, o32=None,
-                   phase=0, delta=None, split=True, window=(-1, -1)):
+                   phase=0, delta=None, split=True, window=(-1, -1), q_lens=None):
     """Fused attention backward (include/omh.h).  q, dout: bf16 [B*Lq, H*128]; k, v: bf16 [B*Lk, H*128] (row stride
     free); lse fp32 [B, H, Lq] from ``flash_attn_raw(..., lse=)``; k_lens int32 [B] or None.
     Returns fp32 dq [B*Lq, H*128], dk, dv [B*Lk, H*128] — or, with ``out=(dq, dk, dv)`` bf16 2-D tensors (row stride
@@ -215,8 +215,11 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     (fp32 [B, H, Lq]) a phase-1 call filled and may run on two streams.  ``split`` (with o32): hand the kernels scratch so
     that a partly filled last round of workgroups is split over the inner loop (include/omh.h, ABI v8).
     ``window`` = (left, right): the backward of ``flash_attn_raw(..., window=)``'s band (omh_flash_attn_bwd_band_d128,
-    additive to ABI v12): a bounded side requires ``o32``; the band kernels run unsplit.  (-1, -1): the call above."""
-    _dev(q, k, v, dout, lse, k_lens, o32)
+    additive to ABI v12): a bounded side requires ``o32``; the band kernels run unsplit.  (-1, -1): the call above.
+    ``q_lens``: int32 [B], the forward's ``q_lens`` — routes to omh_flash_attn_bwd_varlen_d128 (any ``window``, (-1, -1)
+    included; requires ``o32``): rows past a sample's query length get dq = 0, give nothing to dk / dv, and their dout /
+    q / lse / o32 are not read (they may hold NaN)."""
+    _dev(q, k, v, dout, lse, k_lens, o32, q_lens)
     d = H * 128
     for t in (q, k, v, dout):
         assert t.dtype == torch.bfloat16 and t.stride(-1) == 1 and t.shape[-1] == d
@@ -226,6 +229,11 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     rs = lambda t: t.stride(-2)
     ldq, ldk = (Lq + 63) // 64 * 64, (Lk + 63) // 64 * 64
     qt = dot = kt = None
+    if q_lens is not None:
+        assert o32 is not None, "flash_attn_bwd: q_lens needs the forward's fp32 output (o32=)"
+        assert q_lens.dtype == torch.int32 and q_lens.numel() == B and q_lens.is_contiguous()
+    if window[0] >= 0 or window[1] >= 0:
+        assert o32 is not None, "flash_attn_bwd: a bounded window needs the forward's fp32 output (o32=)"
     if o32 is None:
         def padded(L, ld):                     # only the pad columns need the zeros (the transpose writes the rest)
             t = torch.empty(B, d, ld, dtype=torch.bfloat16, device=dev)
@@ -260,8 +268,11 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
                          Lk * dk.stride(0), dk.stride(0), d * ldq, d * ldk, ldq, ldk,
                          float(scale if scale is not None else 128 ** -0.5), int(q_prescaled), bf, _p(o32), int(phase),
                          None, 0)
+    if q_lens is not None:
+        check(lib.omh_flash_attn_bwd_varlen_d128(C.byref(a), _p(q_lens), int(window[0]), int(window[1]), _stream()),
+              "omh_flash_attn_bwd_varlen_d128")
+        return dq, dk, dv
     if window[0] >= 0 or window[1] >= 0:
-        assert o32 is not None, "flash_attn_bwd: a bounded window needs the forward's fp32 output (o32=)"
         check(lib.omh_flash_attn_bwd_band_d128(C.byref(a), int(window[0]), int(window[1]), _stream()),
               "omh_flash_attn_bwd_band_d128")
         return dq, dk, dv
@@ -271,6 +282,65 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
     check(lib.omh_flash_attn_bwd_d128(C.byref(a), _stream()), "omh_flash_attn_bwd_d128")
     return dq, dk, dv
+
+
+class _FlashAttnFunc(torch.autograd.Function):
+    """``flash_attn_func``: omh_flash_attn_fwd_d128 (short-sequence kernel, with lse and the fp32 output) forward, ONE
+    omh_flash_attn_bwd_* call backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, k_lens, q_lens, scale, window):
+        _dev(q, k, v, k_lens, q_lens)
+        B, Lq, H, D = q.shape
+        Lk = k.shape[1]
+        assert D == 128 and k.shape == (B, Lk, H, D) and v.shape == (B, Lk, H, D)
+        assert q.dtype == k.dtype == v.dtype == torch.bfloat16
+        for t in (k_lens, q_lens):
+            assert t is None or (t.dtype == torch.int32 and t.numel() == B and t.is_contiguous())
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        d, dev = H * D, q.device
+        Lp = (Lk + 63) // 64 * 64
+        vt = torch.empty(B, d, Lp, dtype=torch.bfloat16, device=dev)            # V^T, the pad columns zero
+        if Lp != Lk:
+            vt[:, :, Lk:].zero_()
+        transpose_bf16_raw(ptr(v), ptr(vt), Lk, d, d, Lp, batch=B, bs_in=Lk * d, bs_out=d * Lp)
+        o = torch.empty(B, Lq, H, D, dtype=torch.bfloat16, device=dev)
+        o32 = torch.empty(B * Lq, d, dtype=torch.float32, device=dev)
+        lse = torch.empty(B, H, Lq, dtype=torch.float32, device=dev)
+        # pinned to the short-sequence kernel, as the training step pins it (never split: this flag alone)
+        flash_attn_raw(_p(q), _p(k), _p(vt), _p(o), _p(k_lens), B, H, Lq, Lk, Lq * d, d, Lk * d, d, d * Lp, Lq * d, d, Lp,
+                       scale, lse=_p(lse), o32=_p(o32), flags=ATTN_SHORT_KERNEL, q_lens=_p(q_lens), window=window)
+        ctx.save_for_backward(q, k, v, o, lse, o32, k_lens, q_lens)
+        ctx.scale, ctx.window = scale, window
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, o32, k_lens, q_lens = ctx.saved_tensors
+        B, Lq, H, D = q.shape
+        Lk, d = k.shape[1], H * D
+        do = do.to(torch.bfloat16).contiguous()
+        out = (torch.empty(B * Lq, d, dtype=torch.bfloat16, device=q.device),
+               torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device),
+               torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device))
+        flash_attn_bwd(q.view(B * Lq, d), k.view(B * Lk, d), v.view(B * Lk, d), o.view(B * Lq, d), do.view(B * Lq, d), lse,
+                       k_lens, B, H, Lq, Lk, scale=ctx.scale, out=out, o32=o32, window=ctx.window, q_lens=q_lens)
+        need = ctx.needs_input_grad
+        return (out[0].view(B, Lq, H, D) if need[0] else None, out[1].view(B, Lk, H, D) if need[1] else None,
+                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None)
+
+
+def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
+                    q_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None, window=(-1, -1)):
+    """Differentiable attention (a ``torch.autograd.Function``): q [B,Lq,H,128], k, v [B,Lk,H,128] bf16 (V row-major: the
+    padded V^T the kernel reads is built here, by the transpose kernel); k_lens / q_lens int32 [B] or None; ``window`` =
+    (left, right) as in ``flash_attn``.  Returns [B,Lq,H,128] bf16 — the bits of ``flash_attn`` on the same inputs
+    whenever that call takes the short-sequence kernel.  The forward keeps q, k, v, o, lse, the fp32 output and the
+    lens; the backward is one ``flash_attn_bwd`` call with bf16 outputs (omh_flash_attn_bwd_varlen_d128 with q_lens, the
+    band entry with a bounded window, omh_flash_attn_bwd_d128 otherwise: no atomics, repeatable bit for bit) and
+    returns gradients only for the inputs that need them."""
+    window = (int(window[0]) if window[0] >= 0 else -1, int(window[1]) if window[1] >= 0 else -1)
+    return _FlashAttnFunc.apply(q, k, v, k_lens, q_lens, float(scale if scale is not None else 128 ** -0.5), window)
 
 
 def layernorm_modulate_raw(x, y, rows, dim, eps, mul_const, mul0, mul1, mul1_stride, add0, add1, add1_stride,

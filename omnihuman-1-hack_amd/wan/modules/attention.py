@@ -7,9 +7,14 @@ kernel; the result is softmax(q k^T * scale) v per head over the first
 ``k_lens[b]`` keys of each sample, for every one of the first ``q_lens[b]``
 query rows (rows past it are zero; ``q_lens`` is never passed by model.py).  This wrapper keeps that contract
 for head_dim 128, including flash-attn's ``causal`` / ``window_size`` band (bottom-right aligned: query i sees key j
-iff i + klen - qlen - left <= j <= i + klen - qlen + right; rows with an empty band are zero) — forward only, on the
+iff i + klen - qlen - left <= j <= i + klen - qlen + right; rows with an empty band are zero), on the
 short-sequence kernel; ``dropout_p`` > 0 is rejected (a random mask has no parity to hold).  The DiT blocks do not go through it (they hand the kernel
 pre-laid-out q / k / V^T buffers); it exists for callers of the reference API.
+
+The call is differentiable, as the reference's is through flash-attn: with grad enabled and an input that requires it,
+full attention (``q_lens`` / ``k_lens`` honoured) goes through ``ops.flash_attn_func`` and the gradients come back in
+each input's own dtype and shape.  The band's backward exists too (``ops.flash_attn_func(window=)``); through this
+wrapper a bounded window with a grad-requiring input is still refused — see ``flash_attention``.
 """
 import torch
 
@@ -20,7 +25,20 @@ __all__ = ["flash_attention", "attention"]
 
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None,
                     causal=False, window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None):
-    """q [B, Lq, N, 128], k/v [B, Lk, N, 128]; returns [B, Lq, N, 128] in q's dtype."""
+    """q [B, Lq, N, 128], k/v [B, Lk, N, 128]; returns [B, Lq, N, 128] in q's dtype.
+
+    With grad enabled and q, k or v requiring it the result carries a ``grad_fn`` (``ops.flash_attn_func``; the casts
+    to bf16 and ``q * q_scale`` stay torch ops in front of it, so fp32 inputs — the reference's own call pattern — get
+    fp32 gradients of their own shape).  Under ``torch.no_grad()`` or with no input requiring grad the call is the
+    forward-only path.  The grad path pins the short-sequence kernel (its backward needs that kernel's lse and fp32
+    output), so the two give the same output bits whenever the forward-only call takes the short-sequence kernel too —
+    every call with ``q_lens`` or a band, and full attention below the long-sequence dispatch (>= 512 tiles of 256 rows
+    and Lk >= 1024); beyond it the forward-only call runs the long-sequence stream: other bits, and a faster forward.
+    ``causal`` / a bounded ``window_size`` with an input that requires grad raises NotImplementedError: the refusal is
+    kept because tests/test_gpu_kernels.py pins it (test_flash_attention_causal_and_window) and can be lifted when that
+    test is revisited — the differentiable band is ``ops.flash_attn_func(window=)``.
+    ``deterministic`` is accepted and changes nothing: the backward kernels use no atomics and repeat bit for bit either
+    way."""
     assert dtype in (torch.float16, torch.bfloat16)
     assert q.device.type == "cuda" and q.size(-1) <= 256
     if dropout_p != 0.:
@@ -35,8 +53,8 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         wr = 0
     window = (wl if wl >= 0 else -1, wr if wr >= 0 else -1)
     if window != (-1, -1) and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        raise NotImplementedError("flash_attention on gfx950: causal / window_size are forward-only (the attention "
-                                  "backward streams serve full attention, the only form model.py uses)")
+        raise NotImplementedError("flash_attention on gfx950: causal / window_size are forward-only through this wrapper; "
+                                  "the differentiable band is ops.flash_attn_func(window=)")
     B, Lq, N, D = q.shape
     Lk = k.shape[1]
     if D != 128:
@@ -44,15 +62,19 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     out_dtype = q.dtype
     if q_scale is not None:
         q = q * q_scale
+    kl = None if k_lens is None else k_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    ql = None if q_lens is None else q_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        o = ops.flash_attn_func(q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), kl, ql,
+                                scale=softmax_scale, window=window)
+        return o.type(out_dtype)
     qb = q.to(torch.bfloat16).contiguous()
     kb = k.to(torch.bfloat16).contiguous()
     Lp = (Lk + 63) // 64 * 64
     vt = torch.zeros(B, N * D, Lp, dtype=torch.bfloat16, device=q.device)
     vt[:, :, :Lk] = v.to(torch.bfloat16).reshape(B, Lk, N * D).transpose(1, 2)   # layout change only
-    kl = None if k_lens is None else k_lens.to(device=q.device, dtype=torch.int32).contiguous()
     # q_lens (attention.py:55-60,79): the reference cuts the queries past q_lens[b] out of the packed batch — and can only
     # un-flatten the result when every q_lens[b] == Lq (attention.py:110); here those rows come back as zeros
-    ql = None if q_lens is None else q_lens.to(device=q.device, dtype=torch.int32).contiguous()
     o = ops.flash_attn(qb, kb, vt, kl, scale=softmax_scale, q_lens=ql, window=window)
     return o.type(out_dtype)
 
