@@ -698,6 +698,42 @@ int omh_ema_update(float* ema, const float* p, int64_t n, float decay, omh_strea
  * Same arithmetic per element as omh_ema_update. */
 int omh_ema_update_multi(const int64_t* table, int32_t n_entries, int64_t total_chunks, float decay, omh_stream_t stream);
 
+/* Additive to ABI v12 (OMH_ABI_VERSION unchanged): global gradient-norm clipping on the device.  The OmniHuman trainer
+ * clips before every optimizer step (Omnihuman/omnihuman_trainer.py:349-356: torch.nn.utils.clip_grad_norm_(
+ * model.parameters(), max_grad_norm), then optimizer.step(); omni_config.yaml:44 max_grad_norm 1.0) — with torch that is
+ * ~825 tensors through foreach kernels, one read of every gradient for the norm and a read and a write for the scale.
+ *
+ * Elements per workgroup of omh_grad_norm_multi / omh_scale_multi: the caller sizes the table and the workspace by it. */
+#define OMH_NORM_CHUNK 16384
+/* L2 norm over n_entries fp32 tensors and the clip coefficient derived from it (omnihuman_trainer.py:349-353).
+ * table: DEVICE array of n_entries x 3 int64 {grad ptr (fp32, contiguous), numel (> 0), first_chunk}, first_chunk =
+ * running sum of ceil(numel / OMH_NORM_CHUNK), total_chunks = its final value (omh_ema_update_multi's addressing).
+ * workspace: DEVICE fp32 [total_chunks], owned by the caller, overwritten.  out: DEVICE fp32 [2]:
+ *   out[0] = || g / grad_scale ||_2 over all tensors,
+ *   out[1] = min(1, max_norm / (out[0] + 1e-6)), NaN for a NaN norm and 0 for an infinite one — what
+ *            torch.clamp(max_norm / (norm + 1e-6), max=1.0) gives.
+ * Two launches on `stream` and nothing else: one workgroup per chunk writes sum((g / grad_scale)^2) of its chunk in
+ * fp32 (float4 loads when the tensor's base is 16-byte aligned), one workgroup then adds the partials in a fixed order
+ * in fp64.  No atomics: the result repeats bit for bit and does not depend on the order in which workgroups run.  An
+ * element passes through at most 27 chained fp32 additions before the fp64 stage (16 into one of a thread's four
+ * accumulators, 1 for the up to three elements behind a chunk's last float4, 2 to fold the four, 6 across the wave,
+ * 2 across the workgroup's four waves).  Nothing is read back: the host learns neither value. */
+int omh_grad_norm_multi(const int64_t* table, int32_t n_entries, int64_t total_chunks, float* workspace, float* out,
+                        float max_norm, float grad_scale, omh_stream_t stream);
+/* g *= *coef in place over the same table (omnihuman_trainer.py:349-353, the scaling half of clip_grad_norm_); coef is a
+ * DEVICE pointer (out + 1 of omh_grad_norm_multi).  A coefficient of exactly 1.0f changes no bit, so every workgroup
+ * returns before it reads a gradient: an unclipped step costs the launch and nothing else. */
+int omh_scale_multi(const int64_t* table, int32_t n_entries, int64_t total_chunks, const float* coef, omh_stream_t stream);
+/* omh_adamw_multi / omh_adamw_pack_multi with the clip coefficient applied where the gradient is read anyway
+ * (omnihuman_trainer.py:349-356 in one pass: clip, then optimizer.step()): the gradient is (g / grad_scale) * *coef, in
+ * that association; coef is a DEVICE pointer.  The gradients themselves are not written.  Tables, layouts and every other
+ * argument as for the entries without _dev, which keep their kernels. */
+int omh_adamw_multi_dev(const int64_t* table, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int32_t step, float grad_scale, const float* coef, omh_stream_t stream);
+int omh_adamw_pack_multi_dev(const int64_t* table, int32_t n_entries, int64_t total_tiles, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const float* coef,
+                             omh_stream_t stream);
+
 /* ========================================================================
  * Prompt-side encoders (run once per prompt): the umT5 text encoder of seaweed_apt/wan/modules/t5.py:272-322 and
  * the CLIP vision tower of seaweed_apt/wan/modules/clip.py:209-301.  Their Linear layers run on omh_gemm_bf16;

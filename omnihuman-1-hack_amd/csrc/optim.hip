@@ -22,19 +22,29 @@ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __r
     }
 }
 
-// one launch for many tensors: table[t] = {p, g, m, v, numel} (device int64 x 5), blockIdx.y = tensor
+// the clip coefficient of the _dev entries: a pointer more at the end of the kernel's arguments, none without DEV (the
+// instantiation without it is the kernel as it was, argument layout included)
+__device__ __forceinline__ float clip_coef() { return 1.0f; }
+__device__ __forceinline__ float clip_coef(const float* __restrict__ coef) { return *coef; }
+
+// one launch for many tensors: table[t] = {p, g, m, v, numel} (device int64 x 5), blockIdx.y = tensor.  DEV: the gradient
+// is also multiplied by the clip coefficient that omh_grad_norm_multi left on the device (one scalar load and one
+// multiply more; omnihuman_trainer.py:349-356 clips in a pass of its own before optimizer.step())
+template <bool DEV, typename... Coef>
 __global__ __launch_bounds__(256)
 void adamw_multi_kernel(const int64_t* __restrict__ table, float lr, float beta1, float beta2, float eps, float wd,
-                        float bc1, float bc2, float inv_scale) {
+                        float bc1, float bc2, float inv_scale, Coef... coef) {
     const int64_t* e = table + 5 * (int64_t)blockIdx.y;
     float* p = (float*)e[0];
     const float* g = (const float*)e[1];
     float* m = (float*)e[2];
     float* v = (float*)e[3];
     const int64_t n = e[4];
+    const float c = clip_coef(coef...);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float gi = g[i] * inv_scale;
+        float gi = g[i] * inv_scale;
+        if (DEV) gi *= c;
         const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
         const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
         m[i] = mi;
@@ -177,9 +187,12 @@ void pack_weights_kernel(const int64_t* __restrict__ table, int n_entries) {
 // pack_weights_kernel's images of the parameters just written.
 constexpr int AP_COLS = 12;
 
+// DEV: the gradient is (g * inv_scale) * coef, the clip coefficient read from device memory by the caller
+template <bool DEV>
 __device__ __forceinline__ float adamw_one(float p, float g, float& m, float& v, float lr, float beta1, float beta2, float eps,
-                                           float wd, float bc1, float bc2, float inv_scale) {
-    const float gi = g * inv_scale;
+                                           float wd, float bc1, float bc2, float inv_scale, float coef) {
+    float gi = g * inv_scale;
+    if (DEV) gi *= coef;
     const float mi = beta1 * m + (1.0f - beta1) * gi;
     const float vi = beta2 * v + (1.0f - beta2) * gi * gi;
     m = mi;
@@ -187,10 +200,12 @@ __device__ __forceinline__ float adamw_one(float p, float g, float& m, float& v,
     return p * (1.0f - lr * wd) - (lr / bc1) * (mi / (sqrtf(vi) / bc2 + eps));
 }
 
+template <bool DEV, typename... Coef>
 __global__ __launch_bounds__(256)
 void adamw_pack_kernel(const int64_t* __restrict__ table, int n_entries, float lr, float beta1, float beta2, float eps,
-                       float wd, float bc1, float bc2, float inv_scale) {
+                       float wd, float bc1, float bc2, float inv_scale, Coef... coef_p) {
     __shared__ uint16_t tile[64][66];
+    const float coef = clip_coef(coef_p...);
     const int64_t t = blockIdx.x;
     int lo = 0, hi = n_entries - 1;                               // last entry whose first tile is <= t
     while (lo < hi) {
@@ -211,7 +226,7 @@ void adamw_pack_kernel(const int64_t* __restrict__ table, int n_entries, float l
         const int64_t n = rows * cols, i0 = local * 4096;
         for (int64_t i = i0 + tid; i < min(n, i0 + 4096); i += 256) {
             float m = M[i], v = V[i];
-            const float pn = adamw_one(P[i], G[i], m, v, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale);
+            const float pn = adamw_one<DEV>(P[i], G[i], m, v, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale, coef);
             M[i] = m; V[i] = v; P[i] = pn;
             if (dst) dst[i] = pn;
         }
@@ -233,10 +248,10 @@ void adamw_pack_kernel(const int64_t* __restrict__ table, int n_entries, float l
             if (vec && c + 3 < cols) {
                 const float4 p4 = *(const float4*)(P + o), g4 = *(const float4*)(G + o);
                 float4 m4 = *(const float4*)(M + o), v4 = *(const float4*)(V + o);
-                pv[0] = adamw_one(p4.x, g4.x, m4.x, v4.x, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale);
-                pv[1] = adamw_one(p4.y, g4.y, m4.y, v4.y, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale);
-                pv[2] = adamw_one(p4.z, g4.z, m4.z, v4.z, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale);
-                pv[3] = adamw_one(p4.w, g4.w, m4.w, v4.w, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale);
+                pv[0] = adamw_one<DEV>(p4.x, g4.x, m4.x, v4.x, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale, coef);
+                pv[1] = adamw_one<DEV>(p4.y, g4.y, m4.y, v4.y, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale, coef);
+                pv[2] = adamw_one<DEV>(p4.z, g4.z, m4.z, v4.z, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale, coef);
+                pv[3] = adamw_one<DEV>(p4.w, g4.w, m4.w, v4.w, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale, coef);
                 *(float4*)(M + o) = m4;
                 *(float4*)(V + o) = v4;
                 *(float4*)(P + o) = make_float4(pv[0], pv[1], pv[2], pv[3]);
@@ -244,7 +259,7 @@ void adamw_pack_kernel(const int64_t* __restrict__ table, int n_entries, float l
                 for (int k = 0; k < 4; ++k)
                     if (c + k < cols) {
                         float m = M[o + k], v = V[o + k];
-                        pv[k] = adamw_one(P[o + k], G[o + k], m, v, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale);
+                        pv[k] = adamw_one<DEV>(P[o + k], G[o + k], m, v, lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale, coef);
                         M[o + k] = m; V[o + k] = v; P[o + k] = pv[k];
                     }
             }
@@ -281,6 +296,108 @@ void adamw_pack_kernel(const int64_t* __restrict__ table, int n_entries, float l
     }
 }
 
+// ---------------------------------------------------------------------------------------------- global gradient norm
+// omnihuman_trainer.py:349-356 clips the global L2 norm of the gradients before every optimizer.step() (torch's
+// clip_grad_norm_: foreach norms over ~825 tensors, a stack, and an in-place scale).  Here: ONE launch over all
+// gradients, table[t] = {g, numel, first chunk} (device int64 x 3), one workgroup per OMH_NORM_CHUNK-element chunk
+// (ema_multi_kernel's addressing), one fp32 partial per chunk; a one-workgroup launch adds the partials in fp64 in a
+// fixed order and leaves the norm and the clip coefficient on the device.  No atomics: the bits do not depend on the
+// order in which workgroups run.  Longest chain of fp32 additions an element passes through: OMH_NORM_CHUNK / 1024 = 16
+// into one of a thread's four accumulators, 1 for a vector chunk's last (numel % 4) elements, 2 to fold the four, 6
+// across the wave, 2 across the four waves = 27 (omh.h quotes it).
+constexpr int NORM_CHUNK = OMH_NORM_CHUNK;
+static_assert(NORM_CHUNK % 1024 == 0 && NORM_CHUNK / 1024 + 1 + 2 + 6 + 2 <= 64, "chain of fp32 additions (omh.h)");
+
+__device__ __forceinline__ int chunk_entry(const int64_t* __restrict__ table, int n_entries, int64_t t) {
+    int lo = 0, hi = n_entries - 1;                               // last entry whose first chunk is <= t
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[(int64_t)mid * 3 + 2] <= t) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256)
+void grad_sumsq_kernel(const int64_t* __restrict__ table, int n_entries, float inv_scale, float* __restrict__ partial) {
+    __shared__ float wsum[4];
+    const int64_t t = blockIdx.x;
+    const int64_t* e = table + (int64_t)chunk_entry(table, n_entries, t) * 3;
+    const float* g = (const float*)e[0];
+    const int64_t n = e[1], i0 = (t - e[2]) * NORM_CHUNK;
+    const int64_t i1 = i0 + NORM_CHUNK < n ? i0 + NORM_CHUNK : n;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if ((((uintptr_t)g) & 15) == 0) {
+        for (int64_t i = i0 + 4 * (int64_t)threadIdx.x; i + 3 < i1; i += 1024) {
+            const float4 x = *(const float4*)(g + i);
+            const float x0 = x.x * inv_scale, x1 = x.y * inv_scale, x2 = x.z * inv_scale, x3 = x.w * inv_scale;
+            a0 += x0 * x0; a1 += x1 * x1; a2 += x2 * x2; a3 += x3 * x3;
+        }
+        const int64_t i = i0 + ((i1 - i0) & ~(int64_t)3) + threadIdx.x;      // at most three elements are left
+        if (i < i1) { const float x0 = g[i] * inv_scale; a0 += x0 * x0; }
+    } else {
+        for (int64_t i = i0 + threadIdx.x; i < i1; i += 1024) {                // four accumulators here as well
+            const float x0 = g[i] * inv_scale;
+            a0 += x0 * x0;
+            if (i + 256 < i1) { const float x1 = g[i + 256] * inv_scale; a1 += x1 * x1; }
+            if (i + 512 < i1) { const float x2 = g[i + 512] * inv_scale; a2 += x2 * x2; }
+            if (i + 768 < i1) { const float x3 = g[i + 768] * inv_scale; a3 += x3 * x3; }
+        }
+    }
+    float s = (a0 + a1) + (a2 + a3);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[t] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// one workgroup: thread i adds partials i, i + 256, ... in fp64, then a fixed tree over the 256 sums.
+// out[0] = norm, out[1] = min(1, max_norm / (norm + 1e-6)) as torch.clamp(max_norm / (norm + 1e-6), max=1.0) gives it:
+// NaN for a NaN norm (the comparison is false), 0 for an infinite one
+__global__ __launch_bounds__(256)
+void grad_norm_finish_kernel(const float* __restrict__ partial, int64_t n_partials, float max_norm,
+                             float* __restrict__ out) {
+    __shared__ double acc[256];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n_partials; i += 256) s += (double)partial[i];
+    acc[threadIdx.x] = s;
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) acc[threadIdx.x] += acc[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(acc[0]);
+        const float c = max_norm / (norm + 1e-6f);
+        out[0] = norm;
+        out[1] = c > 1.0f ? 1.0f : c;
+    }
+}
+
+// g *= *coef over the table of grad_sumsq_kernel.  A coefficient of exactly 1 (nothing to clip: the common case) leaves
+// every bit as it is, so the workgroup returns before it reads a gradient
+__global__ __launch_bounds__(256)
+void scale_multi_kernel(const int64_t* __restrict__ table, int n_entries, const float* __restrict__ coef) {
+    const float c = *coef;
+    if (c == 1.0f) return;                                        // workgroup-uniform
+    const int64_t t = blockIdx.x;
+    const int64_t* e = table + (int64_t)chunk_entry(table, n_entries, t) * 3;
+    float* g = (float*)e[0];
+    const int64_t n = e[1], i0 = (t - e[2]) * NORM_CHUNK;
+    const int64_t i1 = i0 + NORM_CHUNK < n ? i0 + NORM_CHUNK : n;
+    if ((((uintptr_t)g) & 15) == 0) {
+        for (int64_t i = i0 + 4 * (int64_t)threadIdx.x; i + 3 < i1; i += 1024) {
+            float4 x = *(const float4*)(g + i);
+            x.x *= c; x.y *= c; x.z *= c; x.w *= c;
+            *(float4*)(g + i) = x;
+        }
+        for (int64_t i = i0 + ((i1 - i0) & ~(int64_t)3) + threadIdx.x; i < i1; i += 256) g[i] *= c;
+    } else {
+        for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) g[i] *= c;
+    }
+}
+
 inline int grid_for(int64_t n) {
     int64_t g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
@@ -306,7 +423,7 @@ extern "C" int omh_adamw_multi(const int64_t* table, int32_t n_tensors, float lr
     const float bc1 = 1.0f - powf(beta1, (float)step);
     const float bc2 = sqrtf(1.0f - powf(beta2, (float)step));
     omh_clear_status();
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3(64, n_tensors), dim3(256), 0, (hipStream_t)stream, table, lr, beta1,
+    hipLaunchKernelGGL((adamw_multi_kernel<false>), dim3(64, n_tensors), dim3(256), 0, (hipStream_t)stream, table, lr, beta1,
                        beta2, eps, weight_decay, bc1, bc2, 1.0f / grad_scale);
     return omh_launch_status();
 }
@@ -319,8 +436,56 @@ extern "C" int omh_adamw_pack_multi(const int64_t* table, int32_t n_entries, int
     const float bc1 = 1.0f - powf(beta1, (float)step);
     const float bc2 = sqrtf(1.0f - powf(beta2, (float)step));
     omh_clear_status();
-    hipLaunchKernelGGL(adamw_pack_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, table, n_entries,
+    hipLaunchKernelGGL((adamw_pack_kernel<false>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, table, n_entries,
                        lr, beta1, beta2, eps, weight_decay, bc1, bc2, 1.0f / grad_scale);
+    return omh_launch_status();
+}
+
+extern "C" int omh_adamw_multi_dev(const int64_t* table, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay, int32_t step, float grad_scale, const float* coef,
+                                   omh_stream_t stream) {
+    if (!table || !coef || n_tensors <= 0 || step <= 0 || grad_scale == 0.f) return OMH_E_BADARG;
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2 = sqrtf(1.0f - powf(beta2, (float)step));
+    omh_clear_status();
+    hipLaunchKernelGGL((adamw_multi_kernel<true, const float*>), dim3(64, n_tensors), dim3(256), 0, (hipStream_t)stream, table, lr, beta1,
+                       beta2, eps, weight_decay, bc1, bc2, 1.0f / grad_scale, coef);
+    return omh_launch_status();
+}
+
+extern "C" int omh_adamw_pack_multi_dev(const int64_t* table, int32_t n_entries, int64_t total_tiles, float lr, float beta1,
+                                        float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                                        const float* coef, omh_stream_t stream) {
+    if (!table || !coef || n_entries <= 0 || total_tiles <= 0 || total_tiles > 0x7fffffffLL || step <= 0 ||
+        grad_scale == 0.f)
+        return OMH_E_BADARG;
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2 = sqrtf(1.0f - powf(beta2, (float)step));
+    omh_clear_status();
+    hipLaunchKernelGGL((adamw_pack_kernel<true, const float*>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, table,
+                       n_entries, lr, beta1, beta2, eps, weight_decay, bc1, bc2, 1.0f / grad_scale, coef);
+    return omh_launch_status();
+}
+
+extern "C" int omh_grad_norm_multi(const int64_t* table, int32_t n_entries, int64_t total_chunks, float* workspace,
+                                   float* out, float max_norm, float grad_scale, omh_stream_t stream) {
+    if (!table || !workspace || !out || n_entries <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffLL ||
+        grad_scale == 0.f || max_norm != max_norm)
+        return OMH_E_BADARG;
+    omh_clear_status();
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table,
+                       n_entries, 1.0f / grad_scale, workspace);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, total_chunks,
+                       max_norm, out);
+    return omh_launch_status();
+}
+
+extern "C" int omh_scale_multi(const int64_t* table, int32_t n_entries, int64_t total_chunks, const float* coef,
+                               omh_stream_t stream) {
+    if (!table || !coef || n_entries <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffffLL) return OMH_E_BADARG;
+    omh_clear_status();
+    hipLaunchKernelGGL(scale_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table,
+                       n_entries, coef);
     return omh_launch_status();
 }
 

@@ -900,6 +900,52 @@ def adamw_pack_multi(table, n_entries, total_tiles, lr, beta1, beta2, eps, weigh
                                    _stream()), "omh_adamw_pack_multi")
 
 
+def _coef(coef):
+    _dev(coef)
+    assert coef.dtype == torch.float32 and coef.numel() >= 1
+    return _p(coef)
+
+
+def adamw_multi_dev(table, n, lr, beta1, beta2, eps, weight_decay, step, coef, grad_scale=1.0):
+    """``adamw_multi`` with the gradient multiplied by ``coef[0]``, an fp32 DEVICE scalar (``grad_norm_multi``'s clip
+    coefficient): omnihuman_trainer.py:349-356 without the clipping pass over the gradients."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous()
+    check(lib.omh_adamw_multi_dev(_p(table), n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, _coef(coef),
+                                  _stream()), "omh_adamw_multi_dev")
+
+
+def adamw_pack_multi_dev(table, n_entries, total_tiles, lr, beta1, beta2, eps, weight_decay, step, coef, grad_scale=1.0):
+    """``adamw_pack_multi`` with the gradient multiplied by ``coef[0]``, an fp32 DEVICE scalar."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 12)
+    check(lib.omh_adamw_pack_multi_dev(_p(table), n_entries, total_tiles, lr, beta1, beta2, eps, weight_decay, step,
+                                       grad_scale, _coef(coef), _stream()), "omh_adamw_pack_multi_dev")
+
+
+NORM_CHUNK = 16384                                              # OMH_NORM_CHUNK (include/omh.h)
+
+
+def grad_norm_multi(table, n_entries, total_chunks, workspace, out, max_norm, grad_scale=1.0):
+    """L2 norm of ``n_entries`` fp32 tensors and the clip coefficient, both left on the device: ``table`` int64 device
+    tensor [n_entries, 3] = {grad pointer, numel, first NORM_CHUNK-element chunk}, ``workspace`` fp32 [>= total_chunks],
+    ``out`` fp32 [2] = {norm of g / grad_scale, min(1, max_norm / (norm + 1e-6))} (include/omh.h: omh_grad_norm_multi)."""
+    _dev(table, workspace, out)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 3)
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() >= total_chunks
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 2
+    check(lib.omh_grad_norm_multi(_p(table), int(n_entries), int(total_chunks), _p(workspace), _p(out), float(max_norm),
+                                  float(grad_scale), _stream()), "omh_grad_norm_multi")
+
+
+def scale_multi(table, n_entries, total_chunks, coef):
+    """g *= coef[0] in place over ``grad_norm_multi``'s table; ``coef`` an fp32 DEVICE scalar (a coefficient of exactly 1
+    reads and writes nothing)."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 3)
+    check(lib.omh_scale_multi(_p(table), int(n_entries), int(total_chunks), _coef(coef), _stream()), "omh_scale_multi")
+
+
 def pack_weights_multi(table, n_entries, total_tiles):
     """One launch for every bf16 operand copy (and transposed copy) of the fp32 master weights; ``table``: int64 device
     tensor [n_entries, 9] (include/omh.h)."""

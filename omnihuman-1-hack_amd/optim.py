@@ -1,6 +1,8 @@
 """Optimizer side of the training step on gfx950 kernels: AdamW with the
-constructor of ``torch.optim.AdamW`` (seaweed_apt/distilled_trainer.py:69-75)
-and the EMA update of distilled_trainer.py:319-334 kept on the GPU."""
+constructor of ``torch.optim.AdamW`` (seaweed_apt/distilled_trainer.py:69-75),
+the EMA update of distilled_trainer.py:319-334 kept on the GPU, and the global
+gradient-norm clip of Omnihuman/omnihuman_trainer.py:349-356, on its own
+(``clip_grad_norm_``) or inside the optimizer step (``AdamW(max_grad_norm=)``)."""
 import os
 import weakref
 
@@ -16,15 +18,119 @@ except Exception:  # pragma: no cover
     pack_entry_of = None
 
 
-class AdamW(torch.optim.Optimizer):
-    """``torch.optim.AdamW``-compatible (lr, betas, eps, weight_decay); one fused kernel per parameter."""
+def _norm_plan(cache, key, rows, dev):
+    """The device table {grad, numel, first chunk} of omh_grad_norm_multi / omh_scale_multi for ``rows`` = [(grad address,
+    numel)] and the workspace of one fp32 partial per chunk: (rows, table, total chunks, workspace), rebuilt and
+    re-uploaded only when an address or a size changed."""
+    ent = cache.get(key)
+    if ent is None or ent[0] != rows:
+        full, chunk0 = [], 0
+        for g_, n_ in rows:
+            full.append([g_, n_, chunk0])
+            chunk0 += (n_ + ops.NORM_CHUNK - 1) // ops.NORM_CHUNK
+        ws = ent[3] if ent is not None and ent[3].numel() >= chunk0 else torch.empty(chunk0, dtype=torch.float32, device=dev)
+        ent = cache[key] = (rows, torch.tensor(full, dtype=torch.int64).to(dev, non_blocking=False), chunk0, ws)
+    return ent
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+
+_CLIP_TABLES = {}
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """``torch.nn.utils.clip_grad_norm_`` (omnihuman_trainer.py:349-353) in two launches for all gradients together:
+    omh_grad_norm_multi leaves the global L2 norm and min(1, max_norm / (norm + 1e-6)) on the device, omh_scale_multi
+    multiplies every gradient by that coefficient in place (and touches nothing when it is 1).  Returns the norm before
+    clipping as a 0-d fp32 tensor on the gradients' device; nothing is read back to the host unless
+    ``error_if_nonfinite`` asks for the check.  Gradients must be fp32, contiguous and on one device; only the L2 norm is
+    built; ``foreach`` is accepted for torch's signature and ignored."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    if float(norm_type) != 2.0:
+        raise NotImplementedError(f"clip_grad_norm_: only the L2 norm is implemented on the device, got norm_type={norm_type!r}")
+    max_norm = float(max_norm)
+    rows, grads = [], []
+    for i, p in enumerate(parameters):
+        g = p.grad
+        if g is None:
+            continue
+        what = f"the gradient of parameter {i} (shape {tuple(g.shape)}, {g.dtype}, {g.device})"
+        ops._dev(g)
+        if g.dtype != torch.float32:
+            raise ValueError(f"clip_grad_norm_: {what} must be float32")
+        if not g.is_contiguous():
+            raise ValueError(f"clip_grad_norm_: {what} must be contiguous (strides {tuple(g.stride())})")
+        if grads and g.device != grads[0].device:
+            raise ValueError(f"clip_grad_norm_: {what} is not on {grads[0].device} with the gradients before it")
+        if g.numel():
+            grads.append(g)
+            rows.append((g.data_ptr(), g.numel()))
+    if not rows:
+        return torch.tensor(0.0)
+    dev = grads[0].device
+    _, table, chunks, ws = _norm_plan(_CLIP_TABLES, (dev, len(rows)), rows, dev)
+    if len(_CLIP_TABLES) > 8:
+        _CLIP_TABLES.pop(next(iter(_CLIP_TABLES)))
+    out = torch.empty(2, dtype=torch.float32, device=dev)       # a fresh pair per call: the caller keeps the norm
+    with torch.cuda.device(dev):
+        ops.grad_norm_multi(table, len(rows), chunks, ws, out, max_norm)
+        if error_if_nonfinite and not bool(torch.isfinite(out[0])):
+            raise RuntimeError(
+                f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be "
+                "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                "`error_if_nonfinite=False`")
+        ops.scale_multi(table, len(rows), chunks, out[1:])
+    torch.autograd.graph.increment_version(grads)
+    return out[0]
+
+
+class AdamW(torch.optim.Optimizer):
+    """``torch.optim.AdamW``-compatible (lr, betas, eps, weight_decay); one fused kernel per parameter.
+
+    ``max_grad_norm`` (omnihuman_trainer.py:349-356, omni_config.yaml:44): ``step()`` clips the global L2 norm of the
+    gradients of all parameter groups to it, as ``clip_grad_norm_(model.parameters(), max_grad_norm)`` before the step
+    would — one omh_grad_norm_multi launch, then the AdamW kernels multiply the gradients they read by the coefficient
+    that launch left on the device.  ``p.grad`` itself is NOT scaled: that is the one visible difference from
+    clip-then-step.  ``grad_norm`` holds the norm before clipping of the last such step as a 0-d device tensor (for
+    logging without a synchronisation).  ``max_grad_norm`` is an attribute of the optimizer, not a hyper-parameter of
+    the groups: ``state_dict()`` is what it is without it, and a ``torch.optim.AdamW`` state dict loads."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None
+
+    def _global_norm(self, grad_scale):
+        """One norm launch over the gradients of every group; returns ({id(p): the gradient the step reads}, coef)."""
+        grads, rows = {}, []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None or id(p) in grads:
+                    continue
+                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                assert g.dtype == torch.float32, "max_grad_norm: gradients must be float32"
+                if rows and g.device != dev:
+                    raise ValueError(f"AdamW(max_grad_norm=): gradients on {dev} and {g.device}; the global norm is "
+                                     "built on one device")
+                dev = g.device
+                grads[id(p)] = g
+                if g.numel():
+                    rows.append((g.data_ptr(), g.numel()))
+        if not rows:
+            return grads, None
+        _, table, chunks, ws = _norm_plan(self.__dict__.setdefault("_tables", {}), (dev, len(rows), "norm"), rows, dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)   # fresh per step: grad_norm stays valid for the caller
+        with torch.cuda.device(dev):
+            ops.grad_norm_multi(table, len(rows), chunks, ws, out, self.max_grad_norm, grad_scale)
+        self.grad_norm = out[0]
+        return grads, out[1:]
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
         loss = closure() if closure is not None else None
+        clipped, coef = None, None
+        if getattr(self, "max_grad_norm", None) is not None:
+            clipped, coef = self._global_norm(grad_scale)
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             by_step = {}
@@ -46,7 +152,10 @@ class AdamW(torch.optim.Optimizer):
                 # a state dict saved by torch.optim.AdamW (the 'optimizer' entry of the reference's checkpoints,
                 # distilled_trainer.py:153-178) holds the step as a 0-d tensor: normalise to a Python int
                 st["step"] = int(st["step"]) + 1
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                if clipped is not None:
+                    g = clipped[id(p)]                          # the very tensor the norm was taken of
+                else:
+                    g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 keep.append(g)
                 touched.append(p)
                 assert p.dtype == torch.float32 and p.is_contiguous() and g.dtype == torch.float32
@@ -84,16 +193,24 @@ class AdamW(torch.optim.Optimizer):
                                 tile0 += (r[4] + 4095) // 4096
                             full.append(e_)
                         ent = cache[key] = (rows, torch.tensor(full, dtype=torch.int64).to(dev, non_blocking=False), tile0)
-                    ops.adamw_pack_multi(ent[1], len(rows), ent[2], group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                         step, grad_scale)
+                    if coef is not None:
+                        ops.adamw_pack_multi_dev(ent[1], len(rows), ent[2], group["lr"], b1, b2, group["eps"],
+                                                 group["weight_decay"], step, coef, grad_scale)
+                    else:
+                        ops.adamw_pack_multi(ent[1], len(rows), ent[2], group["lr"], b1, b2, group["eps"],
+                                             group["weight_decay"], step, grad_scale)
                     continue
                 key = (gi, dev, len(rows))
                 ent = cache.get(key)
                 if ent is None or ent[0] != rows:
                     ent = cache[key] = (rows, torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=False))
                 table = ent[1]
-                ops.adamw_multi(table, len(rows), group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
-                                grad_scale)
+                if coef is not None:
+                    ops.adamw_multi_dev(table, len(rows), group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
+                                        coef, grad_scale)
+                else:
+                    ops.adamw_multi(table, len(rows), group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
+                                    grad_scale)
             # the kernel writes through raw pointers: tell autograd (and the packed bf16 weight copies keyed on
             # ``_version``, model.py:_Packed) that these parameters changed
             if touched:
