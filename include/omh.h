@@ -734,6 +734,49 @@ int omh_adamw_pack_multi_dev(const int64_t* table, int32_t n_entries, int64_t to
                              float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const float* coef,
                              omh_stream_t stream);
 
+/* Additive to ABI v12 (OMH_ABI_VERSION unchanged, no existing struct or entry changed): low-rank adapters (LoRA) on the
+ * block Linears.  The reference has no adapters (its trainers update whole backbones, distilled_trainer.py:69-75), so
+ * there is no reference line to follow; the definition is the published one (Hu et al. 2021): an adapted Linear
+ * computes with W_eff = W + s B A, A fp32 [rank, cols], B fp32 [rows, rank], s = alpha / rank, 1 <= rank <= 128.
+ * Here W_eff is formed where the bf16 operand copies are made, so every GEMM of the forward and backward is unchanged.
+ *
+ * omh_pack_weights_multi with adapters: table = DEVICE array of n_entries x 13 int64, the nine columns of
+ * omh_pack_weights_multi followed by {A, B, rank, scale}; scale = the fp32 bit pattern of s in the low 32 bits.  A == 0:
+ * the entry is written exactly as omh_pack_weights_multi writes it.  Otherwise dst = bf16(W + s B A) and dstT its
+ * transpose: same 64 x 64 tiles, ragged edges, destination layouts and first_tile addressing.  The rank sum is one
+ * fused multiply-add per rank in ascending order, in fp32; s and W enter with one more fused multiply-add; one rounding
+ * to bf16. */
+int omh_pack_weights_lora_multi(const int64_t* table, int32_t n_entries, int64_t total_tiles, omh_stream_t stream);
+/* W += s B A in place in fp32 over the same table (kind 0 entries with an adapter; dst / dstT ignored, other entries
+ * untouched).  The same kernel body and the same device function as omh_pack_weights_lora_multi: a plain
+ * omh_pack_weights_multi of the merged weight gives the bits of the fused pack. */
+int omh_lora_merge(const int64_t* table, int32_t n_entries, int64_t total_tiles, omh_stream_t stream);
+/* Adapter gradients of one Linear without forming dW.  x bf16 [M, in] (row pitch ldx) the layer's input, dy bf16
+ * [M, out] (row pitch lddy) its output gradient:
+ *   U = x A^T, T = dy B     (bf16 [M, rank]: A and B rounded to bf16 as MFMA operands, fp32 accumulation, one rounding)
+ *   dB (+)= s dy^T U  [out, rank],   dA (+)= s T^T x  [rank, in]      (fp32, contiguous)
+ * accumulate: bit 0 adds into dA, bit 1 into dB (gradient accumulation); otherwise they are overwritten.  The
+ * contraction over M is cut into a number of slices that depends on the shapes alone; each slice's partial sum goes to
+ * the workspace and one more launch adds them in ascending order: no atomics, the result repeats bit for bit.
+ * in, out, ldx, lddy multiples of 8; x, dy, workspace 16-byte aligned; workspace_bytes >= omh_lora_grads_workspace_bytes.
+ * Three launches on `stream`. */
+typedef struct {
+    const void* x;
+    const void* dy;
+    const float* A;
+    const float* B;
+    float* dA;
+    float* dB;
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t ldx, lddy;
+    int32_t M, in_features, out_features, rank;
+    float scale;
+    int32_t accumulate;
+} omh_lora_grad_args;
+int64_t omh_lora_grads_workspace_bytes(const omh_lora_grad_args* args);
+int omh_lora_grads(const omh_lora_grad_args* args, omh_stream_t stream);
+
 /* ========================================================================
  * Prompt-side encoders (run once per prompt): the umT5 text encoder of seaweed_apt/wan/modules/t5.py:272-322 and
  * the CLIP vision tower of seaweed_apt/wan/modules/clip.py:209-301.  Their Linear layers run on omh_gemm_bf16;

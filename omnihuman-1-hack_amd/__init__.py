@@ -18,3 +18,6 @@ from . import _lib  # noqa: F401  (loads libomh.so; raises if unavailable)
 from . import ops  # noqa: F401
 
 __version__ = "0.1.0"
+from . import lora  # noqa: F401
+from .lora import (DEFAULT_TARGETS, add_lora, load_lora_state_dict, lora_state_dict, merge_lora,  # noqa: F401
+                   remove_lora, set_lora_scale)

@@ -66,6 +66,13 @@ class GemmArgs(C.Structure):
                 ("workspace", vp), ("workspace_bytes", i64), ("n_split", i32)]
 
 
+class LoraGradArgs(C.Structure):
+    _fields_ = [("x", vp), ("dy", vp), ("A", vp), ("B", vp), ("dA", vp), ("dB", vp),
+                ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("lddy", i64),
+                ("M", i32), ("in_features", i32), ("out_features", i32), ("rank", i32),
+                ("scale", f32), ("accumulate", i32)]
+
+
 COLSUM_MAX = 16
 
 
@@ -239,6 +246,10 @@ _SIGS = {
     "omh_ema_update": (i32, [vp, vp, i64, f32, vp]),
     "omh_ema_update_multi": (i32, [vp, i32, i64, f32, vp]),
     "omh_pack_weights_multi": (i32, [vp, i32, i64, vp]),
+    "omh_pack_weights_lora_multi": (i32, [vp, i32, i64, vp]),
+    "omh_lora_merge": (i32, [vp, i32, i64, vp]),
+    "omh_lora_grads_workspace_bytes": (i64, [C.POINTER(LoraGradArgs)]),
+    "omh_lora_grads": (i32, [C.POINTER(LoraGradArgs), vp]),
     "omh_gather_rows_f32": (i32, [vp, vp, vp, i64, i32, i64, vp]),
     "omh_gather_rows_bf16": (i32, [vp, vp, vp, i64, i32, i64, vp]),
     "omh_rmsnorm_f32": (i32, [vp, vp, f32, vp, vp, i64, i32, vp]),

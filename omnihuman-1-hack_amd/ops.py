@@ -954,6 +954,59 @@ def pack_weights_multi(table, n_entries, total_tiles):
     check(lib.omh_pack_weights_multi(_p(table), n_entries, total_tiles, _stream()), "omh_pack_weights_multi")
 
 
+def pack_weights_lora_multi(table, n_entries, total_tiles):
+    """``pack_weights_multi`` over a table whose entries may carry a low-rank adapter: int64 device tensor
+    [n_entries, 13] = the nine columns + {A, B, rank, scale bits} (include/omh.h); dst = bf16(W + s B A)."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 13)
+    check(lib.omh_pack_weights_lora_multi(_p(table), n_entries, total_tiles, _stream()), "omh_pack_weights_lora_multi")
+
+
+def lora_merge(table, n_entries, total_tiles):
+    """W += s B A in place (fp32) for every entry of a ``pack_weights_lora_multi`` table that has an adapter."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 13)
+    check(lib.omh_lora_merge(_p(table), n_entries, total_tiles, _stream()), "omh_lora_merge")
+
+
+def f32_bits(v: float) -> int:
+    """The bit pattern of fp32(v) as a non-negative integer (the scale column of the adapter pack table)."""
+    return C.c_uint32.from_buffer(C.c_float(v)).value
+
+
+def lora_grads(x, dy, A, B, scale, dA=None, dB=None, acc_a=False, acc_b=False):
+    """Adapter gradients of one Linear (include/omh.h: omh_lora_grads): x bf16 [M, in], dy bf16 [M, out] (row stride
+    free, multiple of 8), A fp32 [rank, in], B fp32 [out, rank].  dA / dB fp32 contiguous: written, or added to with
+    ``acc_a`` / ``acc_b``.  Returns (dA, dB, workspace) — the workspace so that a caller on a second stream can
+    record it there."""
+    _dev(x, dy, A, B, dA, dB)
+    assert x.dtype == dy.dtype == torch.bfloat16 and x.dim() == 2 and dy.dim() == 2 and x.shape[0] == dy.shape[0]
+    assert x.stride(1) == 1 and dy.stride(1) == 1
+    assert A.dtype == B.dtype == torch.float32 and A.is_contiguous() and B.is_contiguous()
+    M, n_in = x.shape
+    n_out = dy.shape[1]
+    rank = A.shape[0]
+    assert A.shape == (rank, n_in) and B.shape == (n_out, rank)
+    if dA is None:
+        assert not acc_a
+        dA = torch.empty(rank, n_in, dtype=torch.float32, device=x.device)
+    if dB is None:
+        assert not acc_b
+        dB = torch.empty(n_out, rank, dtype=torch.float32, device=x.device)
+    assert dA.dtype == dB.dtype == torch.float32 and dA.is_contiguous() and dB.is_contiguous()
+    assert dA.shape == A.shape and dB.shape == B.shape
+    a = _lib.LoraGradArgs(_p(x), _p(dy), _p(A), _p(B), _p(dA), _p(dB), None, 0, x.stride(0), dy.stride(0), M, n_in, n_out,
+                          rank, float(scale), int(bool(acc_a)) | (int(bool(acc_b)) << 1))
+    need = lib.omh_lora_grads_workspace_bytes(C.byref(a))
+    if need <= 0:
+        raise OmhError(f"omh_lora_grads: unsupported shapes M={M} in={n_in} out={n_out} rank={rank} "
+                       f"(in, out and the row strides must be multiples of 8, 1 <= rank <= 128)")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    check(lib.omh_lora_grads(C.byref(a), _stream()), "omh_lora_grads")
+    return dA, dB, ws
+
+
 def ema_update(ema, p, decay):
     _dev(ema, p)
     assert ema.dtype == p.dtype == torch.float32 and ema.is_contiguous() and p.is_contiguous()

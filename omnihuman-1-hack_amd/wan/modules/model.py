@@ -65,8 +65,9 @@ class _Packed:
     def __init__(self):
         self.store = {}
 
-    def get(self, key, params, builder):
-        sig = tuple((p.data_ptr(), p._version, str(p.device)) for p in params)
+    def get(self, key, params, builder, extra=()):
+        """``extra``: what else the copy depends on (the adapters of ``_lora_sig``); () leaves the signature as it was."""
+        sig = tuple((p.data_ptr(), p._version, str(p.device)) for p in params) + extra
         ent = self.store.get(key)
         if ent is None or ent[0] != sig:
             with torch.no_grad():
@@ -83,6 +84,65 @@ def _bf16(w: torch.Tensor) -> torch.Tensor:
     if w.dtype == torch.bfloat16:
         return w.contiguous()
     return ops.cast_bf16(w.float().contiguous())
+
+
+def lora_of(lin):
+    """(A, B, scale) of a Linear that carries a low-rank adapter (lora.add_lora: parameters ``lora_A`` [rank, in] and
+    ``lora_B`` [out, rank], scale = alpha / rank unless lora.set_lora_scale overrode it), else None."""
+    A = lin._parameters.get("lora_A")
+    if A is None:
+        return None
+    ov = lin.__dict__.get("lora_scale_override")
+    return A, lin._parameters["lora_B"], float(ov) if ov is not None else float(lin.lora_alpha) / A.shape[0]
+
+
+def _lora_sig(*lins):
+    """Signature of the adapters of ``lins`` for _Packed.get: () when there is none."""
+    out = ()
+    for lin in lins:
+        lo = lora_of(lin)
+        if lo is not None:
+            A, B, s = lo
+            out += ((A.data_ptr(), A._version, B.data_ptr(), B._version, s),)
+    return out
+
+
+def lora_pack_row(w, dst, dstT, ld_dst, ld_t, lo):
+    """One entry of the adapter pack table (include/omh.h: omh_pack_weights_lora_multi) for the fp32 weight ``w``;
+    ``lo``: lora_of()'s triple or None.  Column 7 (first tile) is filled by the caller."""
+    r, c = w.shape
+    row = [w.data_ptr(), dst.data_ptr() if dst is not None else 0, dstT.data_ptr() if dstT is not None else 0, r, c,
+           ld_dst, ld_t, 0, 0]
+    if lo is None:
+        return row + [0, 0, 0, 0]
+    A, B, s = lo
+    if not (A.dtype == B.dtype == w.dtype == torch.float32 and A.is_contiguous() and B.is_contiguous()
+            and w.is_contiguous() and A.device == B.device == w.device):
+        raise ops.OmhError("a low-rank adapter needs contiguous fp32 weight, lora_A and lora_B on one device")
+    if A.shape[1] != c or B.shape[0] != r or B.shape[1] != A.shape[0] or not 1 <= A.shape[0] <= 128:
+        raise ops.OmhError(f"adapter shapes {tuple(A.shape)}, {tuple(B.shape)} do not fit the weight {tuple(w.shape)}")
+    return row + [A.data_ptr(), B.data_ptr(), A.shape[0], ops.f32_bits(s)]
+
+
+def _weight_bf16(lin):
+    """bf16 operand copy of a Linear's weight: bf16(W), or bf16(W + s B A) with an adapter (one launch of the fused
+    pack kernel — the training step's, so both paths read the same bits)."""
+    lo = lora_of(lin)
+    if lo is None:
+        return _bf16(lin.weight)
+    w = lin.weight.detach()
+    out = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
+    row = lora_pack_row(w, out, None, w.shape[1], 0, (lo[0].detach(), lo[1].detach(), lo[2]))
+    table = torch.tensor([row], dtype=torch.int64).to(w.device)
+    ops.pack_weights_lora_multi(table, 1, ((w.shape[0] + 63) // 64) * ((w.shape[1] + 63) // 64))
+    return out
+
+
+def _cat_bf16(*lins):
+    """bf16 copy of the row-wise concatenation of the Linears' (effective) weights."""
+    if not any(lora_of(lin) is not None for lin in lins):
+        return _bf16(torch.cat([lin.weight.detach() for lin in lins], 0))
+    return torch.cat([_weight_bf16(lin) for lin in lins], 0)
 
 
 def _round_up(a, b):
@@ -168,20 +228,19 @@ class WanSelfAttention(nn.Module):
     # packed weights ---------------------------------------------------------
     def _w_qk(self):
         return self._packed.get("qk", (self.q.weight, self.k.weight, self.q.bias, self.k.bias), lambda: (
-            _bf16(torch.cat([self.q.weight.detach(), self.k.weight.detach()], 0)),
-            torch.cat([self.q.bias.detach(), self.k.bias.detach()], 0).float().contiguous()))
+            _cat_bf16(self.q, self.k),
+            torch.cat([self.q.bias.detach(), self.k.bias.detach()], 0).float().contiguous()), _lora_sig(self.q, self.k))
 
     def _w_qkv(self):
         return self._packed.get("qkv", (self.q.weight, self.k.weight, self.v.weight, self.q.bias, self.k.bias, self.v.bias),
-                                lambda: (_bf16(torch.cat([self.q.weight.detach(), self.k.weight.detach(),
-                                                          self.v.weight.detach()], 0)),
+                                lambda: (_cat_bf16(self.q, self.k, self.v),
                                          torch.cat([self.q.bias.detach(), self.k.bias.detach(), self.v.bias.detach()],
-                                                   0).float().contiguous()))
+                                                   0).float().contiguous()), _lora_sig(self.q, self.k, self.v))
 
     def _w(self, name):
         lin = getattr(self, name)
         return self._packed.get(name, (lin.weight, lin.bias),
-                                lambda: (_bf16(lin.weight), lin.bias.detach().float().contiguous()))
+                                lambda: (_weight_bf16(lin), lin.bias.detach().float().contiguous()), _lora_sig(lin))
 
     def _norm_w(self, name):
         m = getattr(self, name)
@@ -359,7 +418,7 @@ class WanAttentionBlock(nn.Module):
     def _ffn_w(self, i):
         lin = self.ffn[i]
         return self._packed.get(f"ffn{i}", (lin.weight, lin.bias),
-                                lambda: (_bf16(lin.weight), lin.bias.detach().float().contiguous()))
+                                lambda: (_weight_bf16(lin), lin.bias.detach().float().contiguous()), _lora_sig(lin))
 
     def forward(self, x, e, seq_lens, grid_sizes, freqs, context, context_lens, block_idx=0,
                 _fc: Optional["_FwdCtx"] = None, _part: str = "all"):
@@ -766,13 +825,16 @@ class WanModel(nn.Module):
         if hasattr(self, "img_emb"):
             mods.append(self.img_emb)
         ps = [p for m in mods for p in m.parameters()]
+        scales = ()
         for blk in self.blocks:
             ca = blk.cross_attn
             for name in ("k", "v", "norm_k", "k_img", "v_img", "norm_k_img"):
                 m = getattr(ca, name, None)
                 if isinstance(m, nn.Module):
-                    ps.extend(m.parameters())
-        return tuple((p.data_ptr(), p._version) for p in ps)
+                    ps.extend(m.parameters())            # (an adapter's lora_A / lora_B are parameters of the Linear)
+                    if isinstance(m, nn.Linear) and lora_of(m) is not None:
+                        scales += (lora_of(m)[2],)      # ... and its strength may be overridden without touching them
+        return tuple((p.data_ptr(), p._version) for p in ps) + scales
 
     @torch.no_grad()
     def encode_context(self, context, clip_fea=None, extra_conditions=None) -> "ContextState":

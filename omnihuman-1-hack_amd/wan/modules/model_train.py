@@ -97,6 +97,7 @@ class _State:
 # re-pack launch.  Keyed by the parameter OBJECT, never by its address: a storage that was freed or moved (offload, a
 # .to() without a refresh()) can be handed to an unrelated tensor by the caching allocator.
 import weakref
+from . import model as _model_mod
 _PACK_REGISTRY = {}
 
 
@@ -114,6 +115,8 @@ def pack_entry_of(param):
         return None
     packs, ri = ent[0](), ent[1]
     if packs is None or ent[2]() is not param or packs.table is None or ri >= len(packs.rows):
+        return None
+    if ri in packs.lora:                # its copies are bf16(W + s B A): rebuilt by refresh(), never by the optimizer pass
         return None
     row = packs.rows[ri]
     if packs.params[ri] is not param or row[0] != param.data_ptr() or param.numel() != row[3] * row[4] \
@@ -135,6 +138,10 @@ class TrainPacks:
         self.table = None
         self.blocks = []
         self.key = None
+        self.lora, self.lora_ptrs = {}, []
+
+    def __deepcopy__(self, memo):
+        return TrainPacks(None)                               # a copied model packs its own weights on first use
 
     @staticmethod
     def of(model):
@@ -147,10 +154,14 @@ class TrainPacks:
         dev = model.patch_embedding.weight.device
         freeze = bool(getattr(model, "reference_ffn_freeze", True))
         rows, self.blocks, self.params = [], [], []
+        self.lora = {}                                       # row index -> the Linear whose adapter that row folds in
         bf = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
 
-        def entry(src, dst, dstT, r, c, ld_dst, ld_t, kind=0):
+        def entry(src, dst, dstT, r, c, ld_dst, ld_t, kind=0, lin=None):
             assert src.dtype == torch.float32 and src.is_contiguous(), "training packs expect fp32 master weights"
+            if lin is not None and _model_mod.lora_of(lin) is not None:
+                self.lora[len(rows)] = lin
+                P.setdefault("lora", {})[names[id(lin)]] = lin
             self.params.append(src)
             rows.append([src.data_ptr(), dst.data_ptr() if dst is not None else 0,
                          dstT.data_ptr() if dstT is not None else 0, r, c, ld_dst, ld_t, 0, kind])
@@ -159,32 +170,33 @@ class TrainPacks:
             sa, ca = blk.self_attn, blk.cross_attn
             d, f = blk.dim, blk.ffn_dim
             P = {}
+            names = {id(m): n for n, m in blk.named_modules() if isinstance(m, torch.nn.Linear)}
             P["wqkv"], P["wqkvT"] = bf(3 * d, d), bf(d, 3 * d)
             P["bqkv"] = torch.empty(3 * d, dtype=torch.float32, device=dev)
             for j, lin in enumerate((sa.q, sa.k, sa.v)):
-                entry(lin.weight, P["wqkv"][j * d:], P["wqkvT"][:, j * d:], d, d, d, 3 * d)
+                entry(lin.weight, P["wqkv"][j * d:], P["wqkvT"][:, j * d:], d, d, d, 3 * d, lin=lin)
                 entry(lin.bias, P["bqkv"][j * d:], None, 1, d, d, 0, kind=1)
             P["wo"], P["woT"] = bf(d, d), bf(d, d)
-            entry(sa.o.weight, P["wo"], P["woT"], d, d, d, d)
+            entry(sa.o.weight, P["wo"], P["woT"], d, d, d, d, lin=sa.o)
             P["wq_c"], P["wq_cT"] = bf(d, d), bf(d, d)
-            entry(ca.q.weight, P["wq_c"], P["wq_cT"], d, d, d, d)
+            entry(ca.q.weight, P["wq_c"], P["wq_cT"], d, d, d, d, lin=ca.q)
             P["wkv_c"], P["wkv_cT"] = bf(2 * d, d), bf(d, 2 * d)
             for j, lin in enumerate((ca.k, ca.v)):
-                entry(lin.weight, P["wkv_c"][j * d:], P["wkv_cT"][:, j * d:], d, d, d, 2 * d)
+                entry(lin.weight, P["wkv_c"][j * d:], P["wkv_cT"][:, j * d:], d, d, d, 2 * d, lin=lin)
             if hasattr(ca, "k_img"):
                 P["wkv_i"], P["wkv_iT"] = bf(2 * d, d), bf(d, 2 * d)
                 for j, lin in enumerate((ca.k_img, ca.v_img)):
-                    entry(lin.weight, P["wkv_i"][j * d:], P["wkv_iT"][:, j * d:], d, d, d, 2 * d)
+                    entry(lin.weight, P["wkv_i"][j * d:], P["wkv_iT"][:, j * d:], d, d, d, 2 * d, lin=lin)
             P["wo_c"], P["wo_cT"] = bf(d, d), bf(d, d)
-            entry(ca.o.weight, P["wo_c"], P["wo_cT"], d, d, d, d)
+            entry(ca.o.weight, P["wo_c"], P["wo_cT"], d, d, d, d, lin=ca.o)
             frozen = freeze and idx > 10
             P["w1"], P["w2"] = bf(f, d), bf(d, f)
             P["w1T"], P["w2T"] = (None, None) if frozen else (bf(d, f), bf(f, d))
-            entry(blk.ffn[0].weight, P["w1"], P["w1T"], f, d, d, f)
-            entry(blk.ffn[2].weight, P["w2"], P["w2T"], d, f, f, d)
+            entry(blk.ffn[0].weight, P["w1"], P["w1T"], f, d, d, f, lin=blk.ffn[0])
+            entry(blk.ffn[2].weight, P["w2"], P["w2T"], d, f, f, d, lin=blk.ffn[2])
             self.blocks.append(P)
         self.rows, self.subsets = rows, {}
-        self.table, self.total_tiles = self._table(range(len(rows)), dev)
+        self.table, self.total_tiles, self.table_lora = self._table(range(len(rows)), dev)
         self.n = len(rows)
         _purge_pack_entries(self.__dict__.get("_registry_keys", ()))      # a re-layout drops the rows it replaces
         ref = weakref.ref(self)
@@ -203,37 +215,66 @@ class TrainPacks:
                 self.sig[i] = self.params[i]._version
 
     def _table(self, idx, dev):
-        """Device table of the entries ``idx`` (each with the first tile it owns in the launch) and the tile count."""
+        """Device table of the entries ``idx`` (each with the first tile it owns in the launch), the tile count, and
+        whether it is an adapter table (13 columns, omh_pack_weights_lora_multi: some entry folds an adapter in)."""
+        idx = list(idx)
+        with_lora = any(i in self.lora for i in idx)
         sel, tile0 = [], 0
         for i in idx:
             r = list(self.rows[i])
             r[7] = tile0
             tile0 += (r[3] * r[4] + 4095) // 4096 if r[8] == 1 else ((r[3] + 63) // 64) * ((r[4] + 63) // 64)
+            if with_lora:
+                lin = self.lora.get(i)
+                if lin is None:
+                    r += [0, 0, 0, 0]
+                else:
+                    r += _model_mod.lora_pack_row(self.params[i], None, None, 0, 0, _model_mod.lora_of(lin))[9:]
             sel.append(r)
-        return torch.tensor(sel, dtype=torch.int64).to(dev), tile0
+        return torch.tensor(sel, dtype=torch.int64).to(dev), tile0, with_lora
+
+    def _launch(self, tab, n):
+        (ops.pack_weights_lora_multi if tab[2] else ops.pack_weights_multi)(tab[0], n, tab[1])
+
+    def _lora_state(self):
+        """(pointers, versions + scales) of the adapters folded into the copies."""
+        ptrs, sig = [], []
+        for i, lin in self.lora.items():
+            A, B, s = _model_mod.lora_of(lin) or (None, None, None)
+            if A is None:                                    # removed behind our back: the epoch check re-lays out
+                continue
+            ptrs += [A.data_ptr(), B.data_ptr()]
+            sig.append((i, A._version, B._version, s))
+        return ptrs, sig
 
     def refresh(self, model):
         """Make the copies current; returns the per-block dicts."""
-        from . import model as _model_mod
         freeze = bool(getattr(model, "reference_ffn_freeze", True))
         dev = model.patch_embedding.weight.device
-        if self.table is None or self.key != (freeze, str(dev)) or \
-                any(p.data_ptr() != r for p, r in zip(self.params, self.ptrs)):
+        # (adapters added, removed or reloaded bump the model's adapter epoch: lora.py)
+        key = (freeze, str(dev), model.__dict__.get("_lora_epoch", 0))
+        lptrs, lsig = self._lora_state() if self.table is not None and self.lora else ([], [])
+        if self.table is None or self.key != key or \
+                any(p.data_ptr() != r for p, r in zip(self.params, self.ptrs)) or lptrs != self.lora_ptrs:
             self._layout(model)
-            self.key, self.ptrs, self.sig = (freeze, str(dev)), [p.data_ptr() for p in self.params], None
+            self.key, self.ptrs, self.sig = key, [p.data_ptr() for p in self.params], None
+            self.lora_ptrs, lsig = self._lora_state()
         sig = [p._version for p in self.params]
+        for i, av, bv, s in lsig:                            # a row with an adapter: the weight's, A's and B's versions
+            sig[i] = (sig[i], av, bv, s)                     # and the scale (a tuple: mark_current's int never equals it)
         if self.sig is None:
-            ops.pack_weights_multi(self.table, self.n, self.total_tiles)
+            self._launch((self.table, self.total_tiles, self.table_lora), self.n)
         elif sig != self.sig:
             # only what the optimizer touched: the FFNs the reference's quirk freezes (523 M of the 1.3B model's
             # 1 419 M packed parameters) keep their copies
             changed = tuple(i for i, (a, b) in enumerate(zip(sig, self.sig)) if a != b)
-            sub = self.subsets.get(changed)
+            skey = (changed, tuple(x[3] for x in lsig))      # (the adapters' scales sit in the table)
+            sub = self.subsets.get(skey)
             if sub is None:
                 if len(self.subsets) > 8:
                     self.subsets.clear()
-                sub = self.subsets[changed] = self._table(changed, dev)
-            ops.pack_weights_multi(sub[0], len(changed), sub[1])
+                sub = self.subsets[skey] = self._table(changed, dev)
+            self._launch(sub, len(changed))
         self.sig = sig
         return self.blocks
 
@@ -804,8 +845,42 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     # a block without a trainable parameter (a frozen backbone differentiated w.r.t. its input) only carries dx — and, when
     # someone upstream reads it, the context gradient: no weight-gradient products, no bias sums, nothing for the second
     # stream to do on their behalf
-    train = any(p.requires_grad for _, p in _block_params(model, idx))
+    bp = dict(_block_params(model, idx))
+    train = any(p.requires_grad for p in bp.values())
     need_ctx = train or getattr(st, "need_ctx", True)
+    lora = P.get("lora") or {}                                        # {"self_attn.q": its Linear, ...}: low-rank adapters
+    wants = lambda n: bp[n].requires_grad
+
+    def lora_grad(dy_, x_, n):
+        """The adapter gradients of the Linear whose weight is ``n``: dB = s dy^T (x A^T), dA = s (dy B)^T x, without
+        forming dW (omh_lora_grads), on the weight-gradient stream in launch order with that stream's other work.  Into
+        the parameter's own .grad (gradient accumulation), a reducer's bucket slice, a tensor an earlier product of this
+        block made (the i2v o-projection has two inputs) or a fresh one."""
+        lin = lora.get(n[:-7])
+        if lin is None:
+            return
+        nA, nB = n[:-6] + "lora_A", n[:-6] + "lora_B"
+        A, B, s_ = _model_mod.lora_of(lin)
+        if not (A.requires_grad or B.requires_grad):
+            return
+
+        def dest(nm):
+            if nm in tgt:
+                return tgt[nm].grad, True
+            if nm in slots:
+                return slots[nm], nm in g
+            return g.get(nm), nm in g
+        (dA, acc_a), (dB, acc_b) = dest(nA), dest(nB)
+        if dA is None:
+            dA = torch.empty(A.shape, dtype=torch.float32, device=dev)
+        if dB is None:
+            dB = torch.empty(B.shape, dtype=torch.float32, device=dev)
+        g[nA], g[nB] = dA, dB
+        keep = []
+        _on_side(dev, lambda: keep.append(ops.lora_grads(x_, dy_, A.detach(), B.detach(), s_, dA, dB, acc_a, acc_b)[2]),
+                 (dy_, x_, dA, dB))
+        if _WGRAD_STREAM:
+            keep[0].record_stream(_side_stream(dev))
 
     def acc1(name, n):
         """The fp32 accumulator of a 1-D gradient: the parameter's own .grad (added to) or a zeroed arena slice."""
@@ -816,7 +891,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
         """Bias gradients = column sums of dy, deferred to arena.flush() at the end of the block (``now``: launched here,
         on the current stream); ``names``: the parameters stacked along dy's columns, each ``d`` wide when there are
         several.  One pair for the whole width unless a parameter accumulates into its own .grad."""
-        if not train:
+        if not train or not any(wants(n) for n in names):
             return
         if len(names) == 1 or not any(n in tgt for n in names):
             out = acc1(names[0], dy.shape[1]) if len(names) == 1 else arena.take(dy.shape[1])
@@ -838,6 +913,12 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
         or one per parameter — same tiles, same launch — when a parameter accumulates into its own .grad."""
         if not train:
             return
+        if lora:                                                     # adapters: independent of the base weight's flag
+            for j, n in enumerate(names):
+                lora_grad(dy if len(names) == 1 else dy[:, j * d:(j + 1) * d], x, n)
+        want = [wants(n) for n in names]
+        if not any(want):                                            # frozen base weights: no product for them
+            return
 
         def one(dy_, n):
             p = tgt.get(n)
@@ -848,13 +929,14 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
             return wg.add(dy_, x)
         if len(names) == 1:
             g[names[0]] = one(dy, names[0])
-        elif not any(n in tgt or n in slots for n in names):
+        elif all(want) and not any(n in tgt or n in slots for n in names):
             out = wg.add(dy, x)
             for j, n in enumerate(names):
                 g[n] = out[j * d:(j + 1) * d]
         else:
             for j, n in enumerate(names):
-                g[n] = one(dy[:, j * d:(j + 1) * d], n)
+                if want[j]:
+                    g[n] = one(dy[:, j * d:(j + 1) * d], n)
 
     def ln_bwd(xin, dh, shift_i, scale_i, nxt=None):
         """dx += LN+modulate backward of dh; ``nxt = (y, gate_i)``: also the next branch's gated-residual backward on
@@ -925,9 +1007,11 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
                   (dqc, dkv[:, :d], dkv[:, d:]), S["o32_ca"], False)
     else:                                                             # the image-token branch: same q, same dO
         oi, ki = S["oi"], S["ki"]
-        if train:
+        if train and "cross_attn.o.weight" in g:
             wg.launch()                                              # (the second product ADDS to the first one's result)
             wg.add(dy2, oi, out=g["cross_attn.o.weight"])
+        if train and lora:
+            lora_grad(dy2, oi, "cross_attn.o.weight")               # (adds to the adapter gradients of the first input)
         dq32, dk32, dv32 = ops.flash_attn_bwd(qc, kc, vc, oc, doc, S["lse_ca"], fc.ctx_lens32, B, N, Sq, Lt, D ** -0.5)
         vi = ops.transpose_bf16_batched(S["vti"], n_img)
         dqi, dki, dvi = ops.flash_attn_bwd(qc, ki, vi, oi, doc, S["lse_ci"], None, B, N, Sq, n_img, D ** -0.5)
