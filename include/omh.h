@@ -54,6 +54,7 @@ int omh_set_deterministic(int on);
 /* Process options (ABI v10).  Every dispatch switch of the library — kernel-family overrides used by the parity tests
  * (one product on every kernel that can take it) and by A/B timing — is an entry of one table:
  *   ATTN_KERNEL ("w64" / "base")   ATTN_SPLIT ("0" / "tail")   W64_SPLIT ("0")   W64_VARIANT (ablation builds only)
+ *   ATTN_BOUNDED ("0": omh_flash_attn_fwd_d128_bounded runs exactly omh_flash_attn_fwd_d128)
  *   GEMM_KERNEL ("w64" / "8w")   GEMM_TILE ("big" / "small" / "tiny")   GEMM_RULE   GEMM_GROUP_M   GEMM_SPLITK ("0")
  *   GEMM_QKV ("0" / "1")   GEMM_W64_R192 / N192 / BF16M / GBWD / GAUX ("0" / "1")   GEMM_W64_P256 (experiment builds only)
  *   RMS_PAIR_ROW ("0" / "1": omh_rmsnorm_rope_bf16_pair's two-workgroup / one-wave-per-row form)
@@ -233,6 +234,19 @@ typedef struct omh_attn_args {
 int omh_flash_attn_fwd_d128(const omh_attn_args* args, omh_stream_t stream);
 /* Scratch size omh_flash_attn_fwd_d128 can use for these shapes (0: none needed). */
 int64_t omh_flash_attn_workspace_bytes(const omh_attn_args* args);
+/* Additive to ABI v12: the long-sequence stream without a running max.  qk_norm2_max: float [B][H][2] (16 B aligned not
+ * needed, 4 B is), for every (sample, head) the maximum over rows of |q_row|^2 and of |k_row|^2 as
+ * omh_rmsnorm_rope_bf16_pair_bound emitted them for THESE q and k (q with its scale * log2(e) when q_prescaled).  By
+ * Cauchy-Schwarz m = ceil(|q|max |k|max (1 + 2^-6)) bounds every score of that (sample, head); where the long-sequence
+ * kernel runs without a split tail, a workgroup with m <= 48 computes p = 2^(s - m) against this fixed m: no row maxima, no
+ * rescale (p >= 2^-96 stays a normal bf16 / fp32 number).  A workgroup with a larger m, a NaN, an infinity or a negative
+ * word in the buffer runs the stream of omh_flash_attn_fwd_d128, bit for bit; so do the short-sequence kernels, split
+ * launches, a NULL buffer and option ATTN_BOUNDED = "0".  Results of the bounded stream differ from the plain one in the
+ * last bits (another power-of-two-like factor on P per row), inside the same error bounds.
+ * omh_flash_attn_takes_bounded: 1 when a call with these arguments would look at the buffer at all (the caller then runs
+ * the norm entry that fills it), else 0. */
+int omh_flash_attn_fwd_d128_bounded(const omh_attn_args* args, const float* qk_norm2_max, omh_stream_t stream);
+int omh_flash_attn_takes_bounded(const omh_attn_args* args);
 
 /* ------------------------------------------------------------------------
  * Flash attention backward, head_dim 128 (training step: the autograd of
@@ -356,6 +370,16 @@ int omh_rmsnorm_rope_bf16_pair(const void* x_bf16, int64_t ldx, int64_t seg_x, v
                                int32_t dim, const float* weight0, const float* weight1, float eps, int32_t do_norm,
                                const float* rope_cos, const float* rope_sin, int32_t rope_len, int32_t head_dim,
                                const int32_t* grid, int32_t seq_len, float out_scale0, float out_scale1, omh_stream_t stream);
+/* Additive to ABI v12: the same q and k, bit for bit (always in the one-wave-per-row form; rotary table required, head_dim
+ * 128, dim <= 5120), plus norm2_max float [rows / seq_len][dim / 128][2]: per (sample, head) the maximum over the sample's
+ * rows of the squared norm of that head's slice of y0 (index 0) and of y1 (index 1), taken on the values as stored (after
+ * gain, RoPE, out_scale and the rounding to bf16).  The CALLER zeroes the buffer before the launch; the kernel
+ * folds into it with an order-independent maximum (bitwise repeatable).  Feeds omh_flash_attn_fwd_d128_bounded. */
+int omh_rmsnorm_rope_bf16_pair_bound(const void* x_bf16, int64_t ldx, int64_t seg_x, void* y0_bf16, void* y1_bf16,
+                                     int64_t rows, int32_t dim, const float* weight0, const float* weight1, float eps,
+                                     int32_t do_norm, const float* rope_cos, const float* rope_sin, int32_t rope_len,
+                                     int32_t head_dim, const int32_t* grid, int32_t seq_len, float out_scale0,
+                                     float out_scale1, float* norm2_max, omh_stream_t stream);
 
 /* fp32 -> bf16 cast (round to nearest even) of a contiguous buffer. */
 int omh_cast_f32_bf16(const float* x, void* y_bf16, int64_t n, omh_stream_t stream);

@@ -185,6 +185,8 @@ _SIGS = {
     "omh_gemm_bf16_tn_grouped": (i32, [C.POINTER(GemmTnGroup), vp]),
     "omh_flash_attn_fwd_d128": (i32, [C.POINTER(AttnArgs), vp]),
     "omh_flash_attn_workspace_bytes": (i64, [C.POINTER(AttnArgs)]),
+    "omh_flash_attn_fwd_d128_bounded": (i32, [C.POINTER(AttnArgs), vp, vp]),
+    "omh_flash_attn_takes_bounded": (i32, [C.POINTER(AttnArgs)]),
     "omh_flash_attn_bwd_d128": (i32, [C.POINTER(AttnBwdArgs), vp]),
     "omh_flash_attn_bwd_workspace_bytes": (i64, [C.POINTER(AttnBwdArgs)]),
     "omh_flash_attn_bwd_band_d128": (i32, [C.POINTER(AttnBwdArgs), i32, i32, vp]),
@@ -193,6 +195,8 @@ _SIGS = {
     "omh_rmsnorm_rope": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, vp]),
     "omh_rmsnorm_rope_bf16": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, f32, vp]),
     "omh_rmsnorm_rope_bf16_pair": (i32, [vp, i64, i64, vp, vp, i64, i32, vp, vp, f32, i32, vp, vp, i32, i32, vp, i32, f32, f32, vp]),
+    "omh_rmsnorm_rope_bf16_pair_bound": (i32, [vp, i64, i64, vp, vp, i64, i32, vp, vp, f32, i32, vp, vp, i32, i32, vp, i32, f32, f32,
+                                               vp, vp]),
     "omh_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "omh_patchify": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "omh_unpatchify": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),

@@ -396,7 +396,7 @@ void attn_split_combine_kernel(const omh_attn_args p, const int q_tiles, const A
 }  // namespace
 
 // attention_w64.hip: 4 waves x 64 query rows, asm-owned register file (long sequences)
-int omh_launch_attn_w64(const omh_attn_args& a, hipStream_t stream);
+int omh_launch_attn_w64(const omh_attn_args& a, const float* qk_norm2_max, hipStream_t stream);
 
 static inline bool omh_attn_windowed(const omh_attn_args& a) { return a.window_left >= 0 || a.window_right >= 0; }
 
@@ -437,7 +437,7 @@ int64_t omh_attn_base_workspace_bytes(const omh_attn_args& a) {
 }
 bool omh_attn_takes_w64(const omh_attn_args& a) { return attn_choice(a).w64; }
 
-extern "C" int omh_flash_attn_fwd_d128(const omh_attn_args* args, omh_stream_t stream) {
+static int flash_attn_fwd_d128(const omh_attn_args* args, const float* qk_norm2_max, omh_stream_t stream) {
     if (!args || !args->q || !args->k || !args->vt || !args->o) return OMH_E_BADARG;
     const omh_attn_args& a = *args;
     if (a.B <= 0 || a.H <= 0 || a.Lq <= 0 || a.Lk <= 0) return OMH_E_BADARG;
@@ -454,7 +454,7 @@ extern "C" int omh_flash_attn_fwd_d128(const omh_attn_args* args, omh_stream_t s
     const bool w64 = ch.w64;
     omh_clear_status();
     if (w64) {
-        omh_launch_attn_w64(a, (hipStream_t)stream);
+        omh_launch_attn_w64(a, qk_norm2_max, (hipStream_t)stream);
     } else {
         const int q_tiles = (a.Lq + QB - 1) / QB;
         OmhSplitPlan pl = base_split_plan(a);
@@ -477,4 +477,17 @@ extern "C" int omh_flash_attn_fwd_d128(const omh_attn_args* args, omh_stream_t s
                                a, q_tiles, wk);
     }
     return omh_launch_status();
+}
+
+extern "C" int omh_flash_attn_fwd_d128(const omh_attn_args* args, omh_stream_t stream) {
+    return flash_attn_fwd_d128(args, nullptr, stream);
+}
+
+// Additive to ABI v12: the same call with the per-(sample, head) maxima of |q|^2 and |k|^2 that
+// omh_rmsnorm_rope_bf16_pair_bound emitted for THESE q and k (float [B][H][2]).  Where the long-sequence kernel runs unsplit,
+// each workgroup whose bound on the scores is small enough takes the stream without a running max (attention_w64.hip); every
+// other call, and option ATTN_BOUNDED = "0", is exactly omh_flash_attn_fwd_d128.
+extern "C" int omh_flash_attn_fwd_d128_bounded(const omh_attn_args* args, const float* qk_norm2_max, omh_stream_t stream) {
+    if (qk_norm2_max && ((uintptr_t)qk_norm2_max & 3)) return OMH_E_ALIGN;
+    return flash_attn_fwd_d128(args, qk_norm2_max, stream);
 }

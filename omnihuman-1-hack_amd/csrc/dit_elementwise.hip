@@ -321,6 +321,166 @@ void rmsnorm_rope_pair_row_kernel(const uint16_t* __restrict__ x, int64_t ldx, i
     finish(hb, y1, w1, scale1);
 }
 
+// The same kernel for head_dim 128 (a COPY: the kernel above stays as it is, instruction for instruction) that also folds the
+// maximum over rows of the per-head |q|^2 and |k|^2 into norm2_max[b][head][0 / 1] — the bound on the scores that lets the
+// long-sequence attention stream run without a running max (attention_w64.hip).  The sums are taken on the FINAL values
+// (after gain, RoPE, out_scale and the rounding to bf16: what the attention kernel reads).  Vector i of a lane covers columns
+// 256 i + 4 lane ..: lanes 0-31 hold head 2 i, lanes 32-63 head 2 i + 1, so a head's sum is a 32-lane reduction.  The values
+// are non-negative: an unsigned maximum on the bit pattern is the exact float maximum whatever the order, and the buffer is
+// bitwise repeatable.  Each wave first READS the current maxima (one L1-bypassing load instruction per segment for all heads:
+// a stale value only costs a redundant atomic) and issues an atomic only where its own value is larger — a running maximum
+// over n rows moves about ln n times, so the 24 addresses see a few hundred atomics per launch, not 32 760 x 24.  The q and k
+// bits are those of the kernel above.
+template <int MAXV>
+__global__ __launch_bounds__(256)
+void rmsnorm_rope_pair_row_bound_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t seg_x, uint16_t* __restrict__ y0,
+                                        uint16_t* __restrict__ y1, int64_t rows, int dim, const float* __restrict__ w0,
+                                        const float* __restrict__ w1, float eps, int do_norm,
+                                        const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, int rope_len,
+                                        int head_dim, const int* __restrict__ grid, int seq_len, float scale0, float scale1,
+                                        float* __restrict__ norm2_max) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nv = dim >> 2;
+    const uint2* xa = (const uint2*)(x + row * ldx);
+    const uint2* xb = (const uint2*)(x + seg_x + row * ldx);
+    uint2 ha[MAXV], hb[MAXV];
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        ha[i] = c < nv ? xa[c] : make_uint2(0u, 0u);
+    }
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        hb[i] = c < nv ? xb[c] : make_uint2(0u, 0u);
+    }
+    // token position and the lane's two complex pairs (the same for every vector of the lane and for both segments)
+    const int hc = head_dim >> 1, c3 = hc / 3, cf = hc - 2 * c3;
+    bool rot = false;
+    float cs2[2] = {1.f, 1.f}, sn2[2] = {0.f, 0.f};
+    const int b = (int)(row / seq_len);
+    {
+        const int sidx = (int)(row % seq_len);
+        const int gf = grid[3 * b], gh = grid[3 * b + 1], gw = grid[3 * b + 2];
+        if (sidx < gf * gh * gw) {
+            rot = true;
+            const int pf = sidx / (gh * gw), ph = (sidx / gw) % gh, pw = sidx % gw;
+            const int p0 = ((4 * lane) % head_dim) >> 1;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int pc = p0 + e;
+                const int pos = pc < cf ? pf : (pc < cf + c3 ? ph : pw);
+                const int idx = min(pos, rope_len - 1) * hc + pc;
+                cs2[e] = rope_cos[idx]; sn2[e] = rope_sin[idx];
+            }
+        }
+    }
+    const int heads = dim >> 7;
+    auto finish = [&](uint2 (&h)[MAXV], uint16_t* __restrict__ y, const float* __restrict__ weight, float out_scale, int seg) {
+        float4 v[MAXV];
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nv) {
+                v[i] = make_float4(bf2f((uint16_t)(h[i].x & 0xffff)), bf2f((uint16_t)(h[i].x >> 16)),
+                                   bf2f((uint16_t)(h[i].y & 0xffff)), bf2f((uint16_t)(h[i].y >> 16)));
+                q += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
+            }
+        }
+        const float rinv = (do_norm ? rsqrtf(wave_sum(q) / dim + eps) : 1.0f) * out_scale;
+        const float4* wv = (const float4*)weight;
+        uint2* yr = (uint2*)(y + row * dim);
+        // per-vector sums of squares of the stored values, padded to a power of two for the exchange below
+        constexpr int P = MAXV <= 8 ? 8 : 32;                          // (P = 32: plain butterflies, see below)
+        float r[P];
+#pragma unroll
+        for (int i = 0; i < P; ++i) r[i] = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nv) {
+                float4 t = v[i];
+                t.x *= rinv; t.y *= rinv; t.z *= rinv; t.w *= rinv;
+                if (wv) { const float4 g = wv[c]; t.x *= g.x; t.y *= g.y; t.z *= g.z; t.w *= g.w; }
+                if (rot) {
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const float cs = cs2[e], sn = sn2[e];
+                        float& re = e == 0 ? t.x : t.z;
+                        float& im = e == 0 ? t.y : t.w;
+                        const float nr = re * cs - im * sn;
+                        const float ni = re * sn + im * cs;
+                        re = nr; im = ni;
+                    }
+                }
+                uint2 o;
+                o.x = pack_bf2(t.x, t.y);
+                o.y = pack_bf2(t.z, t.w);
+                yr[c] = o;
+                {
+                    // from the STORED bf16 values, behind a compiler barrier: the fp32 arithmetic above then has exactly the
+                    // uses it has in the kernel without the bound, and the compiler forms the same (packed, contracted)
+                    // instructions for it — the q and k bits must not depend on whether the bound is taken
+                    uint32_t px = o.x, py = o.y;
+                    asm volatile("" : "+v"(px), "+v"(py));
+                    const float a0 = __uint_as_float(px << 16), a1 = __uint_as_float(px & 0xffff0000u);
+                    const float a2 = __uint_as_float(py << 16), a3 = __uint_as_float(py & 0xffff0000u);
+                    r[i] = a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
+                }
+            }
+        }
+        {
+            // P sums over the 32 lanes of each half-wave (one head each) by exchanging halves: at lane distance 16, 8, ... a
+            // lane keeps one half of its values and adds the partner's copies of them (P - 1 permutes in all instead of 5 P),
+            // then the distances that are left add the one remaining value across.  The lane ends up with vector `vi`
+            // (the wide kernel, P = 32, would spill 32 values per lane: it runs a plain butterfly per vector instead and lane
+            // i / 32 + i keeps vector i's sum)
+            int vi = 0;
+            float mine = 0.f;
+            if constexpr (P == 32) {
+#pragma unroll
+                for (int i = 0; i < MAXV; ++i) {
+#pragma unroll
+                    for (int o = 16; o > 0; o >>= 1) r[i] += __shfl_xor(r[i], o, 64);
+                    if ((lane & 31) == i) mine = r[i];
+                }
+                vi = lane & 31;
+            } else {
+                int n = P;
+#pragma unroll
+                for (int o = 16; o > 0; o >>= 1) {
+                    if (n > 1) {
+                        n >>= 1;
+                        const bool up = (lane & o) != 0;
+#pragma unroll
+                        for (int j = 0; j < n; ++j) {
+                            const float keep = up ? r[j + n] : r[j], send = up ? r[j] : r[j + n];
+                            r[j] = keep + __shfl_xor(send, o, 64);
+                        }
+                        vi += up ? n : 0;
+                    } else {
+                        r[0] += __shfl_xor(r[0], o, 64);
+                    }
+                }
+                mine = r[0];
+            }
+            // ONE load instruction per wave and segment reads the current maxima (the lanes of a half-wave that hold the
+            // same vector's sum: the first of them), and only the lanes that exceed theirs issue an atomic
+            const int head = 2 * vi + (lane >> 5);
+            if ((lane & (32 / P - 1)) == 0 && vi < MAXV && head < heads) {
+                unsigned int* slot = (unsigned int*)norm2_max + ((int64_t)b * heads + head) * 2 + seg;
+                const unsigned int bits = __float_as_uint(mine);
+                if (bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
+            }
+        }
+    };
+    finish(ha, y0, w0, scale0, 0);
+    finish(hb, y1, w1, scale1, 1);
+}
+
 // ------------------------------------------------------------------ cast
 __global__ __launch_bounds__(256)
 void cast_f32_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int64_t n) {
@@ -537,6 +697,25 @@ extern "C" int omh_rmsnorm_rope_bf16_pair(const void* x_bf16, int64_t ldx, int64
     hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4), 2), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t*)x_bf16, ldx, seg_x, (uint16_t*)y0, (uint16_t*)y1, rows, dim, weight0, weight1, eps,
                        do_norm, rope_cos, rope_sin, rope_len, head_dim, grid, seq_len, out_scale0, out_scale1);
+    return omh_launch_status();
+}
+
+// omh_rmsnorm_rope_bf16_pair in its one-wave-per-row form (whatever the row count) that also emits the per-(sample, head)
+// maxima of |q|^2 and |k|^2: norm2_max float [rows / seq_len][dim / 128][2], zeroed by the caller before the launch.
+extern "C" int omh_rmsnorm_rope_bf16_pair_bound(const void* x_bf16, int64_t ldx, int64_t seg_x, void* y0, void* y1,
+                                                int64_t rows, int32_t dim, const float* weight0, const float* weight1,
+                                                float eps, int32_t do_norm, const float* rope_cos, const float* rope_sin,
+                                                int32_t rope_len, int32_t head_dim, const int32_t* grid, int32_t seq_len,
+                                                float out_scale0, float out_scale1, float* norm2_max, omh_stream_t stream) {
+    if (!x_bf16 || !y0 || !y1 || !norm2_max || rows <= 0 || dim <= 0) return OMH_E_BADARG;
+    if (!rope_cos || !rope_sin || !grid || seq_len <= 0) return OMH_E_BADARG;
+    if ((dim & 3) || (ldx & 3) || (seg_x & 3) || head_dim != 128 || dim % 128 || dim > 20 * 256) return OMH_E_SHAPE;
+    if (((uintptr_t)x_bf16 & 7) || ((uintptr_t)y0 & 7) || ((uintptr_t)y1 & 7) || ((uintptr_t)norm2_max & 3)) return OMH_E_ALIGN;
+    omh_clear_status();
+    auto k2 = dim <= 6 * 256 ? rmsnorm_rope_pair_row_bound_kernel<6> : rmsnorm_rope_pair_row_bound_kernel<20>;
+    hipLaunchKernelGGL(k2, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x_bf16, ldx,
+                       seg_x, (uint16_t*)y0, (uint16_t*)y1, rows, dim, weight0, weight1, eps, do_norm, rope_cos, rope_sin,
+                       rope_len, head_dim, grid, seq_len, out_scale0, out_scale1, norm2_max);
     return omh_launch_status();
 }
 

@@ -33,6 +33,11 @@ Variants (selected at launch, OMH_W64_VARIANT; kept side by side for A/B timing 
   V2  = V1 with a K ring of THREE slots filled three tiles ahead, so that the first K fragments of the next tile are
       read under the last MFMAs of phase 2 (no phase starts by waiting for the LDS);
   V3  = V2 storing its normalised result in fp32: the split-KV workers of the tail (attention_w64.hip).
+  V4  = V2 WITHOUT a running max: the caller supplies m >= every score of the workgroup's (sample, head) as an SGPR operand
+      (%[sm], from the norms of q and k: attention_w64.hip); MI holds -m from the prologue on and is never touched, so
+      p = exp2(s - m) <= 1 with no row maxima, no rescale check, no slow path and no first-tile special case; the log-sum-exp
+      is (m + log2 l) ln 2.  Row sums, exp2 + packing, masks, DMA schedule, K ring and barriers are V2's.  Not a launch
+      variant: the kernel of V2 picks it per workgroup.
 
 Register map (asm-owned; the thirteen per-lane inputs stay in the compiler's operand registers v0..v11):
   a[0:127]    O^T accumulators   [qb][db] 16 each
@@ -373,13 +378,17 @@ def generate(variant):
     abl_salu = ABL == "1" and variant == 1
     abl_traffic = ABL == "2" and variant == 1
     # OMH_ATTN_ABL=3 (round 5): variant 0 = V2 without the row maxima and the rescale check, variant 1 = without the row sums
-    # as well.  Measured: 4.707 -> 4.555 -> 4.411 ms per launch (-3.2 %, -6.3 %).  A stream without the running max would
-    # need an a-priori bound on the scores; the model's RMS norm runs over all 1 536 channels, not per head, so the
-    # worst-case bound is 196 (log2 units) instead of 16 — not usable (p would underflow), not built.
+    # as well.  Measured: 4.707 -> 4.555 -> 4.411 ms per launch (-3.2 %, -6.3 %).  The first of the two is built as V4.  A
+    # stream without the running max needs a bound on the scores; the a-priori one is useless (the model's RMS norm runs over
+    # all 1 536 channels, not per head: 196 log2 units, p would underflow), but the stream does not need the worst case, it
+    # needs a bound for THIS launch's q and k: s_ij <= |q_i| |k_j| per head (Cauchy-Schwarz), and the norm kernel that writes
+    # q and k emits max |q|^2 and max |k|^2 per (sample, head) on the way (dit_elementwise.hip).  The kernel takes V4 only
+    # where that bound is <= 48, so that p >= 2^-96 stays a normal number; above it the workgroup runs V2.
     abl_nomax = ABL == "3" and variant in (0, 1)
     abl_nosum = ABL == "3" and variant == 1
     global M16
     M16 = ABL == "4" and variant == 0
+    bounded = variant == 4
     base = 2 if (abl_poly or abl_salu or abl_traffic or abl_nomax or M16) else min(variant, 2)
     dma_spread = base >= 1
     vpre = base >= 1
@@ -439,11 +448,14 @@ def generate(variant):
         e(f"v_lshl_add_u32 {vr(VA[j])}, {vr(T0)}, 5, %[vab]")
     e(f"v_mov_b32 {vr(NEGINF)}, 0xff800000")
     for qb in range(2):
-        e(f"v_mov_b32 {vr(M_RUN[qb])}, 0")
+        e(f"v_mov_b32 {vr(M_RUN[qb])}, " + ("%[sm]" if bounded else "0"))      # V4: the fixed bound m, for the log-sum-exp
         e(f"v_mov_b32 {vr(L_A[qb])}, 0")
         e(f"v_mov_b32 {vr(L_B[qb])}, 0")
         for r in range(16):
-            e(f"v_mov_b32 {vr(MI(qb) + r)}, 0")
+            if bounded:
+                e(f"v_xor_b32 {vr(MI(qb) + r)}, 0x80000000, {vr(M_RUN[qb])}")  # -m: the C operand of every tile's first MFMAs
+            else:
+                e(f"v_mov_b32 {vr(MI(qb) + r)}, 0")
     for i in range(128):
         e(f"v_accvgpr_write_b32 {ar(i)}, 0")
     # first tiles: K(0), V(0), K(1) (and K(2) with the three-slot ring)
@@ -463,8 +475,8 @@ def generate(variant):
     e("s_waitcnt vmcnt(0)")
     e("s_barrier")
     e("s_nop 7")
-    # ---------------- scores of tile 0 -> set 0 (C = 0)
-    ops = weave(qk_mfmas(0, c_zero=True), [qk_read_plan(0)], pre=kread_ops(0, 0) + kread_ops(1, 0))
+    # ---------------- scores of tile 0 -> set 0 (C = 0; V4: C = -m like every other tile)
+    ops = weave(qk_mfmas(0, c_zero=not bounded), [qk_read_plan(0)], pre=kread_ops(0, 0) + kread_ops(1, 0))
     pending = linearize(e, ops, [])
     assert not pending
     if k3:
@@ -483,9 +495,10 @@ def generate(variant):
     e(f"s_cbranch_scc1 {nomask0}")
     mask_block(e, 0)
     e.label(nomask0)
-    for ln in rowmax_lines(0):
-        e(ln)
-    check_and_rescale(e, 0, "first", first=True)
+    if not bounded:
+        for ln in rowmax_lines(0):
+            e(ln)
+        check_and_rescale(e, 0, "first", first=True)
     e("s_mov_b32 s94, 0")                                      # t
     LOOP_PENDING = list(pending)
 
@@ -527,7 +540,7 @@ def generate(variant):
         # ---- phase 2
         mf2 = pv_mfmas(cur)
         plans = [pv_read_plan(vbase)]
-        tail = ([] if abl_nosum else rowsum_lines(cur)) + ([] if abl_nomax else rowmax_lines(nxt))
+        tail = ([] if abl_nosum else rowsum_lines(cur)) + ([] if abl_nomax or bounded else rowmax_lines(nxt))
         if k3:
             # the K addresses step to the next slot once the reads of phase 1 are all issued; the first fragments of
             # the next tile's K are read under the last MFMAs
@@ -541,7 +554,7 @@ def generate(variant):
         pre = [] if vpre else [vread_op(0, vbase), vread_op(1, vbase), vread_op(2, vbase)]
         pend = linearize(e, weave(mf2, plans, pre=pre), pend)
         assert pend == LOOP_PENDING, (pend, LOOP_PENDING)
-        if not abl_nomax:
+        if not (abl_nomax or bounded):
             check_and_rescale(e, nxt, f"b{p}")
         e("s_add_u32 s94, s94, 1")
 
@@ -618,7 +631,7 @@ def generate(variant):
 
 
 N_VARIANTS = 4
-LDS_BYTES = {0: 5 * KSLOT if ABL else 4 * KSLOT, 1: 5 * KSLOT if ABL else 4 * KSLOT, 2: 5 * KSLOT, 3: 5 * KSLOT}
+LDS_BYTES = {0: 5 * KSLOT if ABL else 4 * KSLOT, 1: 5 * KSLOT if ABL else 4 * KSLOT, 2: 5 * KSLOT, 3: 5 * KSLOT, 4: 5 * KSLOT}
 CLOBBER_V = range(12, 256)
 CLOBBER_A = range(0, 256)
 CLOBBER_S = range(91, 100)
@@ -628,8 +641,8 @@ def main():
     print("// GENERATED by gen_attn_w64.py — do not edit; edit the generator.")
     # Round 5: the shipped library carries the default stream (V2) and the split-KV workers' stream (V3) only; V0 / V1
     # (the steps that led to V2, kept side by side for A/B timing in rounds 2-4) are emitted for the timing-only ablation
-    # builds (OMH_ATTN_ABL), which re-use their slots.
-    for v in (range(N_VARIANTS) if ABL else (2, 3)):
+    # builds (OMH_ATTN_ABL), which re-use their slots.  V4 (the bounded stream) is not a launch variant: V2's kernel holds it.
+    for v in ((0, 1, 2, 3, 4) if ABL else (2, 3, 4)):
         e = generate(v)
         print(f"#define OMH_ATTN_W64_ASM_V{v} \\")
         print(" \\\n".join(e.text().split("\n")))

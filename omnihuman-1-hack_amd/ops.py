@@ -161,13 +161,23 @@ class options:
         return False
 
 
+def flash_attn_takes_bounded(B, H, Lq, Lk, q_rs, k_rs, o_rs, ldv, window=(-1, -1)):
+    """Would ``flash_attn_raw(..., qk_norm2_max=buf)`` with these shapes look at the buffer (include/omh.h,
+    omh_flash_attn_takes_bounded)?  The caller then produces q and k with ``rmsnorm_rope_bf16_pair_bound_raw``."""
+    a = AttnArgs(None, None, None, None, None, B, H, Lq, Lk, 0, q_rs, 0, k_rs, 0, 0, o_rs, ldv, 1.0, None, 1, None, 0, None, 0,
+                 None, int(window[0]), int(window[1]))
+    return bool(lib.omh_flash_attn_takes_bounded(C.byref(a)))
+
+
 def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale,
-                   lse=None, q_prescaled=0, o32=None, flags=0, q_lens=None, window=(-1, -1)):
+                   lse=None, q_prescaled=0, o32=None, flags=0, q_lens=None, window=(-1, -1), qk_norm2_max=None):
     """``flags``: ATTN_SHORT_KERNEL | ATTN_ALLOW_SPLIT (include/omh.h, ABI v8): the training step pins the short-sequence
     kernel (forward and re-run take the same one) and lets it split its last round of workgroups over the keys.
     ``q_lens`` (ABI v10): int32 [B] device pointer; output rows past a sample's query length are written as zero.
     ``window`` (ABI v12): (left, right) band around the bottom-right aligned diagonal, a side < 0 unbounded (causal =
-    (left, 0)); a bounded side runs the short-sequence kernel."""
+    (left, 0)); a bounded side runs the short-sequence kernel.
+    ``qk_norm2_max``: float [B, H, 2] device pointer from ``rmsnorm_rope_bf16_pair_bound_raw`` for these q and k: the
+    long-sequence stream then runs without a running max where the bound allows (omh_flash_attn_fwd_d128_bounded)."""
     a = AttnArgs(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale, lse,
                  int(q_prescaled), None, 0, o32, int(flags), q_lens, int(window[0]), int(window[1]))
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
@@ -175,6 +185,9 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
     if need > 0:
         ws = torch.empty(need, dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    if qk_norm2_max is not None:
+        check(lib.omh_flash_attn_fwd_d128_bounded(C.byref(a), qk_norm2_max, _stream()), "omh_flash_attn_fwd_d128_bounded")
+        return
     check(lib.omh_flash_attn_fwd_d128(C.byref(a), _stream()), "omh_flash_attn_fwd_d128")
 
 
@@ -390,6 +403,15 @@ def rmsnorm_rope_bf16_pair_raw(x, ldx, seg_x, y0, y1, rows, dim, weight0, weight
     check(lib.omh_rmsnorm_rope_bf16_pair(x, ldx, seg_x, y0, y1, rows, dim, weight0, weight1, eps, do_norm, rope_cos, rope_sin,
                                          rope_len, head_dim, grid, seq_len, float(out_scale0), float(out_scale1), _stream()),
           "omh_rmsnorm_rope_bf16_pair")
+
+
+def rmsnorm_rope_bf16_pair_bound_raw(x, ldx, seg_x, y0, y1, rows, dim, weight0, weight1, eps, do_norm, rope_cos, rope_sin,
+                                     rope_len, head_dim, grid, seq_len, norm2_max, out_scale0=1.0, out_scale1=1.0):
+    """``rmsnorm_rope_bf16_pair_raw`` (same bits) that also folds max |y0 row|^2 / |y1 row|^2 per (sample, head) into
+    ``norm2_max`` (float [rows / seq_len, dim / 128, 2], zeroed by the caller): include/omh.h."""
+    check(lib.omh_rmsnorm_rope_bf16_pair_bound(x, ldx, seg_x, y0, y1, rows, dim, weight0, weight1, eps, do_norm, rope_cos,
+                                               rope_sin, rope_len, head_dim, grid, seq_len, float(out_scale0),
+                                               float(out_scale1), norm2_max, _stream()), "omh_rmsnorm_rope_bf16_pair_bound")
 
 
 def rmsnorm_rope(x: torch.Tensor, weight: Optional[torch.Tensor], eps: float, do_norm: bool = True,

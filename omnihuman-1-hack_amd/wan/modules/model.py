@@ -280,10 +280,20 @@ class WanSelfAttention(nn.Module):
         # before its one rounding to bf16: the attention kernel's exponentials then need no per-score multiply
         q_scale = D ** -0.5 * 1.4426950408889634
         wq, wk = self._norm_w("norm_q"), self._norm_w("norm_k")          # q and k: one launch (two column segments)
-        ops.rmsnorm_rope_bf16_pair_raw(ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(wq) if wq is not None else None,
-                                       ptr(wk) if wk is not None else None, self.eps, int(self.qk_norm), ptr(fc.rope_cos),
-                                       ptr(fc.rope_sin), fc.rope_cos.shape[0], D, ptr(fc.grid32), S, out_scale0=q_scale,
-                                       out_scale1=1.0)
+        # where the long-sequence attention stream runs, the norm kernel also emits max |q|^2, |k|^2 per (sample, head): the
+        # stream then needs no running max (a bound on this call's scores: ops.flash_attn_raw, qk_norm2_max)
+        window = tuple(self.window_size)
+        nmax = None
+        if D == 128 and d <= 5120 and ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
+            nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
+        self.last_qk_norm2_max = nmax                                    # (read by tools/attn_bound_values.py)
+        norm_args = (ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(wq) if wq is not None else None,
+                     ptr(wk) if wk is not None else None, self.eps, int(self.qk_norm), ptr(fc.rope_cos), ptr(fc.rope_sin),
+                     fc.rope_cos.shape[0], D, ptr(fc.grid32), S)
+        if nmax is not None:
+            ops.rmsnorm_rope_bf16_pair_bound_raw(*norm_args, ptr(nmax), out_scale0=q_scale, out_scale1=1.0)
+        else:
+            ops.rmsnorm_rope_bf16_pair_raw(*norm_args, out_scale0=q_scale, out_scale1=1.0)
         del qk
         if not fused:
             # V^T[b] = Wv h_b^T + bv  ->  [B, dim, Sp]   (pad columns stay zero)
@@ -293,7 +303,8 @@ class WanSelfAttention(nn.Module):
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
-                           d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1, window=tuple(self.window_size))
+                           d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1, window=window,
+                           qk_norm2_max=ptr(nmax) if nmax is not None else None)
         return o
 
     def forward(self, x, seq_lens, grid_sizes, freqs, _fc: Optional["_FwdCtx"] = None):
