@@ -324,6 +324,39 @@ int omh_flash_attn_bwd_varlen_d128(const omh_attn_bwd_args* args, const int32_t*
                                    int32_t window_right, omh_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Block-sparse attention, additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout changed).
+ * The reference has no counterpart: flash_attn_varlen_func takes no mask (attention.py:96-127 passes causal / window_size
+ * only).  These entries generalise that call's "contiguous range of key tiles per query tile" (the band) to "list of
+ * 128-key blocks per 128-query block".  With nQb = ceil(Lq / 128), nKb = ceil(Lk / 128) and a bool mask M[heads][nQb][nKb]
+ * (heads = 1: shared by all heads; heads = H: one per head; always shared by the samples of a batch), query i of sample
+ * b, head h sees key j iff  M[h][i / 128][j / 128]  and  j < klen  and  i < qlen   (klen = k_lens[b] or Lk, qlen =
+ * q_lens[b] or Lq).  Indices are absolute positions of the padded sequence: no bottom-right shift.
+ * The mask is handed over as four device int32 tables:
+ *   row_cnt [heads][q_blocks], row_idx [heads][q_blocks][k_blocks]: the kept key blocks of each query block, ASCENDING;
+ *                                                                   only the first row_cnt entries of a list are read
+ *   col_cnt [heads][k_blocks], col_idx [heads][k_blocks][q_blocks]: the transposed lists (query blocks of a key block)
+ * A live row that sees no key gets o = 0, lse = -inf, dq = 0 (written); a key no live query sees gets dk = dv = 0
+ * (written); rows at or past qlen as in the varlen entries (zero output / gradient, their memory never used).
+ * Served by the short-sequence kernels only, never split, no atomics: repeatable bit for bit.
+ * A mask together with a band is an error, not an intersection: OMH_E_BADARG.  Because a zero-initialised omh_attn_args
+ * holds window_left = window_right = 0, these entries read (0, 0) as "no band set" (NOT as the one-key band it is in
+ * omh_flash_attn_fwd_d128) and both sides < 0 as unbounded; every other pair is refused.
+ * OMH_E_BADARG also for heads not in {1, H}, block counts that do not match Lq / Lk, and null tables.  The kernels are
+ * head_dim 128 only, like every entry of this family (the structs carry no other head_dim).
+ * mask == NULL: exactly omh_flash_attn_fwd_d128 / omh_flash_attn_bwd_varlen_d128(args, q_lens, -1, -1).
+ * omh_flash_attn_bwd_sparse_d128: the o32 / lse / delta / phase / out_bf16 / q_prescaled contract of
+ * omh_flash_attn_bwd_varlen_d128 (o32 REQUIRED, the workspace is declined).
+ * ---------------------------------------------------------------------- */
+typedef struct omh_block_mask {
+    int32_t heads, q_blocks, k_blocks;
+    const int32_t* row_cnt; const int32_t* row_idx;
+    const int32_t* col_cnt; const int32_t* col_idx;
+} omh_block_mask;
+int omh_flash_attn_fwd_sparse_d128(const omh_attn_args* args, const omh_block_mask* mask, omh_stream_t stream);
+int omh_flash_attn_bwd_sparse_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_block_mask* mask,
+                                   omh_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * LayerNorm (no affine) fused with adaLN modulation, fp32 in -> bf16 out.
  * Replaces WanLayerNorm + "x*(1+scale)+shift" (model.py:91-104,292-293,
  * 314-315,358) and the affine norm3 (model.py:263-265,313).

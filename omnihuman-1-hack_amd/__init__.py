@@ -16,6 +16,7 @@ libomh.so and fails loudly when it is missing and cannot be built.
 """
 from . import _lib  # noqa: F401  (loads libomh.so; raises if unavailable)
 from . import ops  # noqa: F401
+from . import sparse  # noqa: F401  (block masks of the block-sparse attention)
 
 __version__ = "0.1.0"
 from . import lora  # noqa: F401

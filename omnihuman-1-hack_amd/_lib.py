@@ -127,6 +127,12 @@ class AttnBwdArgs(C.Structure):
                 ("phase", i32), ("workspace", vp), ("workspace_bytes", i64)]
 
 
+class BlockMaskArgs(C.Structure):
+    """omh_block_mask (additive to ABI v12): the int32 tables of sparse.BlockMask."""
+    _fields_ = [("heads", i32), ("q_blocks", i32), ("k_blocks", i32),
+                ("row_cnt", vp), ("row_idx", vp), ("col_cnt", vp), ("col_idx", vp)]
+
+
 class PartialReduce(C.Structure):
     _fields_ = [("part", vp), ("nj", i32), ("np", i32), ("nb", i32), ("dim", i32), ("grid_y", i32),
                 ("out", vp * 3), ("stride", i64 * 3)]
@@ -191,6 +197,8 @@ _SIGS = {
     "omh_flash_attn_bwd_workspace_bytes": (i64, [C.POINTER(AttnBwdArgs)]),
     "omh_flash_attn_bwd_band_d128": (i32, [C.POINTER(AttnBwdArgs), i32, i32, vp]),
     "omh_flash_attn_bwd_varlen_d128": (i32, [C.POINTER(AttnBwdArgs), vp, i32, i32, vp]),
+    "omh_flash_attn_fwd_sparse_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(BlockMaskArgs), vp]),
+    "omh_flash_attn_bwd_sparse_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(BlockMaskArgs), vp]),
     "omh_layernorm_modulate": (i32, [vp, vp, i64, i32, f32, f32, vp, vp, i64, vp, vp, i64, i64, vp]),
     "omh_rmsnorm_rope": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, vp]),
     "omh_rmsnorm_rope_bf16": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, f32, vp]),

@@ -77,9 +77,15 @@ struct AttnSplit {
 //   i + (klen - qlen) - left <= j <= i + (klen - qlen) + right     (a side < 0: unbounded; causal: right = 0);
 // a row with no key in its band is written as zero.  The band limits the workgroup's key-tile range and masks the
 // tiles on its edges; a separate instantiation, so the unlimited kernel keeps its instruction stream.
-template <bool WIN>
+// BLK: a block mask (include/omh.h omh_block_mask) — query block qt of head h runs the key tiles 2j, 2j + 1 of the blocks j
+// in its list, in ascending order, with the body of the unlimited kernel: inside a kept block every key below klen is
+// visible.  The list is cut at the first block at or past klen and the last block loses its second tile when that holds
+// no live key, so no tile of the loop is all -inf.  The next tile's index is a scalar read one tile before its loads are
+// issued.  q_lens as in the unlimited kernel, and a workgroup with no live row runs no tile.  Never split.
+template <bool WIN, bool BLK = false>
 __global__ __launch_bounds__(256, 2)
-void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk) {
+void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk, const BlkList bl) {
+    static_assert(!(WIN && BLK), "a block mask excludes the band");
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (KT_BYTES + VT_BYTES)];
 
     const int tid = threadIdx.x;
@@ -123,6 +129,25 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         t_first = min(split * per, n_tiles_all);
         n_tiles = min(t_first + per, n_tiles_all) - t_first;
     }
+    const int32_t* __restrict__ bl_idx = nullptr;         // BLK: this workgroup's list
+    if constexpr (BLK) {
+        int qlen = p.q_lens ? p.q_lens[b] : p.Lq;
+        qlen = min(max(qlen, 0), p.Lq);
+        const int64_t list = (int64_t)(bl.heads == 1 ? 0 : head) * bl.lists + qt;
+        bl_idx = bl.idx + list * bl.stride;
+        // ascending: the live blocks are the entries below ceil(klen / 128) — a binary search over scalars
+        const int live_blocks = (klen + 2 * KB - 1) / (2 * KB);
+        int lo = 0, hi = min(max(bl.cnt[list], 0), bl.stride);
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (bl_idx[mid] < live_blocks) lo = mid + 1; else hi = mid;
+        }
+        n_tiles = 2 * lo;
+        if (lo > 0 && bl_idx[lo - 1] * (2 * KB) + KB >= klen) --n_tiles;
+        if (qt * QB >= qlen) n_tiles = 0;
+    }
+    // BLK: tile x of the loop (wave-uniform: scalar loads)
+    auto blk_tile = [&](int x) { return __builtin_amdgcn_readfirstlane(2 * bl_idx[x >> 1] + (x & 1)); };
 
     const __bf16* __restrict__ Q = (const __bf16*)p.q + (int64_t)b * p.q_bs + head * D;
     const __bf16* __restrict__ K = (const __bf16*)p.k + (int64_t)b * p.k_bs + head * D;
@@ -192,8 +217,15 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     float m_run = -INFINITY, l_run = 0.f;
     const float sc = p.q_prescaled ? 1.0f : p.scale * 1.4426950408889634f;   // scores -> log2 domain
 
+    int t_cur = 0, t_nxt = 0;                             // BLK: the tile in LDS and the one to fetch next
     if (n_tiles > 0) {
-        OMH_GLOAD(t_first)
+        if constexpr (BLK) {
+            t_cur = blk_tile(0);
+            t_nxt = blk_tile(min(1, n_tiles - 1));
+            OMH_GLOAD(t_cur)
+        } else {
+            OMH_GLOAD(t_first)
+        }
         OMH_LSTORE(0)
     }
     __syncthreads();
@@ -201,8 +233,15 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     const int krow_l = swap_bits23(li);
     for (int tt = 0; tt < n_tiles; ++tt) {
         const int buf = tt & 1;
-        const int t = t_first + tt;
+        int t = t_first + tt;
+        if constexpr (BLK) {
+            t = t_cur;
+            OMH_GLOAD(t_nxt)
+            t_cur = t_nxt;
+            t_nxt = blk_tile(min(tt + 2, n_tiles - 1));   // a tile ahead of its loads
+        } else {
         OMH_GLOAD(t_first + min(tt + 1, n_tiles - 1))   // unconditional: keeps the staging registers out of scratch
+        }
         const unsigned char* kt = smem + buf * (KT_BYTES + VT_BYTES);
         const unsigned char* vt = kt + KT_BYTES;
 
@@ -437,7 +476,8 @@ int64_t omh_attn_base_workspace_bytes(const omh_attn_args& a) {
 }
 bool omh_attn_takes_w64(const omh_attn_args& a) { return attn_choice(a).w64; }
 
-static int flash_attn_fwd_d128(const omh_attn_args* args, const float* qk_norm2_max, omh_stream_t stream) {
+// the argument rules of every forward entry: 0 or the error code
+static int attn_fwd_check(const omh_attn_args* args) {
     if (!args || !args->q || !args->k || !args->vt || !args->o) return OMH_E_BADARG;
     const omh_attn_args& a = *args;
     if (a.B <= 0 || a.H <= 0 || a.Lq <= 0 || a.Lk <= 0) return OMH_E_BADARG;
@@ -450,6 +490,13 @@ static int flash_attn_fwd_d128(const omh_attn_args* args, const float* qk_norm2_
     // 32-bit buffer offsets inside one (batch, head) slice of K / V^T (both kernels)
     if ((int64_t)a.Lk * a.k_rs * 2 >= 0x7fffffffLL || (int64_t)D * a.ldv * 2 >= 0x7fffffffLL) return OMH_E_SHAPE;
     if (a.o32 && (((uintptr_t)a.o32 & 15) || (a.o_rs & 3) || (a.o_bs & 3))) return OMH_E_ALIGN;
+    return 0;
+}
+
+static int flash_attn_fwd_d128(const omh_attn_args* args, const float* qk_norm2_max, omh_stream_t stream) {
+    const int rc0 = attn_fwd_check(args);
+    if (rc0) return rc0;
+    const omh_attn_args& a = *args;
     const AttnChoice ch = attn_choice(a);
     const bool w64 = ch.w64;
     omh_clear_status();
@@ -468,10 +515,10 @@ static int flash_attn_fwd_d128(const omh_attn_args* args, const float* qk_norm2_
         wk.ws_lse = pl.n_tail ? wk.ws_o + (int64_t)pl.n_tail * pl.splits * QB * D : nullptr;
         if (omh_attn_windowed(a))
             hipLaunchKernelGGL(flash_attn_fwd_d128_kernel<true>, dim3(pl.n_regular), dim3(256), 0, (hipStream_t)stream, a,
-                               q_tiles, wk);
+                               q_tiles, wk, BlkList{});
         else
             hipLaunchKernelGGL(flash_attn_fwd_d128_kernel<false>, dim3(pl.n_regular + pl.n_tail * pl.splits), dim3(256), 0,
-                               (hipStream_t)stream, a, q_tiles, wk);
+                               (hipStream_t)stream, a, q_tiles, wk, BlkList{});
         if (pl.n_tail)
             hipLaunchKernelGGL(attn_split_combine_kernel, dim3((pl.n_tail * QB + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                                a, q_tiles, wk);
@@ -490,4 +537,24 @@ extern "C" int omh_flash_attn_fwd_d128(const omh_attn_args* args, omh_stream_t s
 extern "C" int omh_flash_attn_fwd_d128_bounded(const omh_attn_args* args, const float* qk_norm2_max, omh_stream_t stream) {
     if (qk_norm2_max && ((uintptr_t)qk_norm2_max & 3)) return OMH_E_ALIGN;
     return flash_attn_fwd_d128(args, qk_norm2_max, stream);
+}
+
+// Additive to ABI v12: the forward under a block mask (include/omh.h).  The short-sequence kernel's BLK instantiation,
+// whatever the shape: no long-sequence stream, no split, no bounded stream.  A NULL mask is the plain entry.
+extern "C" int omh_flash_attn_fwd_sparse_d128(const omh_attn_args* args, const omh_block_mask* mask, omh_stream_t stream) {
+    if (!mask) return omh_flash_attn_fwd_d128(args, stream);
+    const int rc0 = attn_fwd_check(args);
+    if (rc0) return rc0;
+    const omh_attn_args& a = *args;
+    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
+    const int rc1 = omh_block_mask_check(mask, a.H, a.Lq, a.Lk);
+    if (rc1) return rc1;
+    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
+    const int q_tiles = (a.Lq + QB - 1) / QB;
+    const int nwg = q_tiles * a.H * a.B;
+    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
+    const BlkList bl = {mask->row_cnt, mask->row_idx, mask->heads, mask->q_blocks, mask->k_blocks};
+    omh_clear_status();
+    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles, wk, bl);
+    return omh_launch_status();
 }

@@ -391,6 +391,7 @@ void attn_bwd_dq_kernel(const omh_attn_bwd_args p, const int q_blocks) {
 // attention_bwd2.hip: the round-3 kernel pair (needs the forward's fp32 output for delta), and its band form
 int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s);
 int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, hipStream_t s);
+int omh_launch_attn_bwd2_sparse(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_block_mask& m, hipStream_t s);
 
 static bool bwd_ptrs_set(const omh_attn_bwd_args& a) {
     return a.q && a.k && a.v && a.dout && a.lse && a.delta && a.dq && a.dk && a.dv;
@@ -427,6 +428,22 @@ extern "C" int omh_flash_attn_bwd_varlen_d128(const omh_attn_bwd_args* args, con
     if (rc0) return rc0;
     omh_clear_status();
     const int rc = omh_launch_attn_bwd2_band(*args, window_left, window_right, q_lens, (hipStream_t)stream);
+    return rc ? rc : omh_launch_status();
+}
+
+// the backward under a block mask (include/omh.h): the varlen entry's argument rules plus the mask's; a NULL mask IS the
+// varlen entry with the unbounded band
+extern "C" int omh_flash_attn_bwd_sparse_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_block_mask* mask,
+                                              omh_stream_t stream) {
+    if (!mask) return omh_flash_attn_bwd_varlen_d128(args, q_lens, -1, -1, stream);
+    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
+    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
+    const int rc0 = bwd2_check(*args);
+    if (rc0) return rc0;
+    const int rc1 = omh_block_mask_check(mask, args->H, args->Lq, args->Lk);
+    if (rc1) return rc1;
+    omh_clear_status();
+    const int rc = omh_launch_attn_bwd2_sparse(*args, q_lens, *mask, (hipStream_t)stream);
     return rc ? rc : omh_launch_status();
 }
 

@@ -214,11 +214,16 @@ struct BwdSplit {
 // the live rows of the workgroup, the shift and with them the key tiles of the loop.  Rows at or past qlen do not exist:
 // their q / dO / lse / delta are not read and their dQ is stored as zeros.  A third instantiation: the band kernels
 // keep their instruction streams too.
-template <bool PRE, bool WIN, bool VLEN = false>
+// BLK (omh_flash_attn_bwd_sparse_d128): the key tiles come from the query block's ROW list of a block mask (omh_common.h
+// BlkList; the forward's flash_attn_fwd_d128_kernel<false, true> documents the cut of the list) and run the body of the
+// full-attention kernel — only the last tile of the list can reach past klen.  The next tile's index is a scalar read a
+// tile before its LDS-DMA is issued.  q_lens may be NULL (= Lq); rows at or past it as under VLEN.  Never split.
+template <bool PRE, bool WIN, bool VLEN = false, bool BLK = false>
 __global__ __launch_bounds__(256, 2)
 void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk, const int wl, const int wr,
-                         const int32_t* __restrict__ q_lens) {
+                         const int32_t* __restrict__ q_lens, const BlkList bl) {
     static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
+    static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][K tile | V tile]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
     const bool worker = (int)blockIdx.x >= wk.n_regular;
@@ -245,6 +250,7 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     const int q_row = qb * 128 + wave * 32 + li;
     int qlen = p.Lq;
     if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
+    if constexpr (BLK) { if (q_lens) qlen = min(max(q_lens[b], 0), p.Lq); }
     const bool q_ok = q_row < qlen;
     int key_lo = 0, key_hi = klen - 1;                               // WIN: this lane's (query row's) band of keys
     if constexpr (WIN) {
@@ -260,6 +266,28 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
         }
         if (wl >= 0) key_lo = max(0, q_row + shift - wl);
         if (wr >= 0) key_hi = min(klen - 1, q_row + shift + wr);
+    }
+    const int32_t* __restrict__ bl_idx = nullptr;                    // BLK: this workgroup's list
+    if constexpr (BLK) {
+        const int64_t list = (int64_t)(bl.heads == 1 ? 0 : head) * bl.lists + qb;
+        bl_idx = bl.idx + list * bl.stride;
+        const int live_blocks = (klen + 127) >> 7;                   // ascending: the live blocks are the entries below it
+        int lo = 0, hi = min(max(bl.cnt[list], 0), bl.stride);
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (bl_idx[mid] < live_blocks) lo = mid + 1; else hi = mid;
+        }
+        n_tiles = 2 * lo;
+        if (lo > 0 && bl_idx[lo - 1] * 128 + TB >= klen) --n_tiles;  // the last block's second tile holds no live key
+        if (qb * 128 >= qlen) n_tiles = 0;
+    }
+    auto blk_tile = [&](int x) { return __builtin_amdgcn_readfirstlane(2 * bl_idx[x >> 1] + (x & 1)); };   // (scalar loads)
+    int t_cur = 0, t_nxt = 0;                                        // BLK: the tile in LDS and the one to fetch next
+    if constexpr (BLK) {
+        if (n_tiles > 0) {
+            t_cur = blk_tile(0);
+            t_nxt = blk_tile(min(1, n_tiles - 1));
+        }
     }
     bf16x8 qf[8], dof[8];
 #pragma unroll
@@ -287,8 +315,8 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
         for (int r = 0; r < 16; ++r) dq[i][r] = 0.f;
 
     if (n_tiles > 0) {
-        tile_dma(ks, t_first, wave_lds);
-        tile_dma(vs, t_first, wave_lds + TILE_BYTES);
+        tile_dma(ks, BLK ? t_cur : t_first, wave_lds);
+        tile_dma(vs, BLK ? t_cur : t_first, wave_lds + TILE_BYTES);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     // one tile of 64 keys; `masked`: the tile reaches past klen (the last one at most — every other tile skips the
@@ -331,6 +359,26 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
             tile_body(kt, kt + TILE_BYTES, (t_first + t) * TB, std::integral_constant<int, 2>());
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
+    } else if constexpr (BLK) {                                      // the loop below, the tiles taken from the list
+        const bool edge = n_tiles > 0 && (blk_tile(n_tiles - 1) + 1) * TB > klen;
+        const int n_plain = n_tiles - (edge ? 1 : 0);
+        for (int t = 0; t < n_plain; ++t) {
+            const unsigned char* kt = smem + (t & 1) * 2 * TILE_BYTES;
+            if (t + 1 < n_tiles) {
+                const uint32_t nk = wave_lds + ((t + 1) & 1) * 2 * TILE_BYTES;
+                tile_dma(ks, t_nxt, nk);
+                tile_dma(vs, t_nxt, nk + TILE_BYTES);
+            }
+            const int k0 = t_cur * TB;
+            t_cur = t_nxt;
+            t_nxt = blk_tile(min(t + 2, n_tiles - 1));               // a tile ahead of its loads
+            tile_body(kt, kt + TILE_BYTES, k0, std::integral_constant<int, 0>());
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
+        if (edge) {
+            const unsigned char* kt = smem + (n_plain & 1) * 2 * TILE_BYTES;
+            tile_body(kt, kt + TILE_BYTES, t_cur * TB, std::integral_constant<int, 1>());
+        }
     } else {
     // the tile that reaches past klen (the last one of the sequence, if any) is peeled off the loop: two bodies inside
     // one loop keep both sets of hoisted addresses live and spill
@@ -365,13 +413,13 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
                     make_float4(dq[db][4 * g], dq[db][4 * g + 1], dq[db][4 * g + 2], dq[db][4 * g + 3]);
         return;
     }
-    if constexpr (VLEN) {                                            // (a select: rows past qlen are exact zeros)
+    if constexpr (VLEN || BLK) {                                     // (a select: rows past qlen are exact zeros)
 #pragma unroll
         for (int db = 0; db < 4; ++db)
 #pragma unroll
             for (int r = 0; r < 16; ++r) dq[db][r] = q_ok ? dq[db][r] : 0.f;
     }
-    if (VLEN ? q_row < p.Lq : q_ok) {
+    if ((VLEN || BLK) ? q_row < p.Lq : q_ok) {
         const int64_t eo = (int64_t)b * p.dq_bs + (int64_t)q_row * p.dq_rs + head * D;
         if (p.out_bf16) {
             uint16_t* DQ = (uint16_t*)p.dq + eo;
@@ -458,11 +506,16 @@ __device__ __forceinline__ void dkdv_store(const omh_attn_bwd_args& p, const Bwd
 // VLEN (see attn_bwd2_dq_kernel): the ranges end at qlen - 1.  The Q / dO tiles come through buffer descriptors that end
 // at row qlen, so rows past it arrive in LDS as zeros whatever memory holds (NaN included); their lse / delta are not
 // read (parked as -inf / 0).
-template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false>
+// BLK (see attn_bwd2_dq_kernel): the workgroup's 128 keys are ONE block of the mask; it walks the query tiles of the
+// blocks in that block's COLUMN list, cut at the first block at or past qlen (the last block's second tile dropped when
+// it holds no live row), with the unmasked body: inside a kept block every live row sees every live key.  A key block
+// at or past klen runs no tile.  Q / dO / lse / delta of rows past qlen as under VLEN.
+template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false, bool BLK = false>
 __global__ __launch_bounds__(64 * WAVES, 1)
 void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk, const int wl, const int wr,
-                           const int32_t* __restrict__ q_lens) {
+                           const int32_t* __restrict__ q_lens, const BlkList bl) {
     static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
+    static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
     constexpr int THREADS = 64 * WAVES;
     static_assert(WAVES * KPW == 4, "a workgroup covers 128 keys");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][Q tile | dO tile] + lse/delta
@@ -485,6 +538,29 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     int q_lo = 0, q_hi = 0;                                          // WIN: this lane's (key's) range of queries
     int qlen = p.Lq;
     if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
+    if constexpr (BLK) { if (q_lens) qlen = min(max(q_lens[b], 0), p.Lq); }
+    const int32_t* __restrict__ bl_idx = nullptr;                    // BLK: this workgroup's list
+    if constexpr (BLK) {
+        const int64_t list = (int64_t)(bl.heads == 1 ? 0 : head) * bl.lists + kb;
+        bl_idx = bl.idx + list * bl.stride;
+        const int live_blocks = (qlen + 127) >> 7;                   // ascending: the live blocks are the entries below it
+        int lo = 0, hi = min(max(bl.cnt[list], 0), bl.stride);
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (bl_idx[mid] < live_blocks) lo = mid + 1; else hi = mid;
+        }
+        n_tiles = 2 * lo;
+        if (lo > 0 && bl_idx[lo - 1] * 128 + TB >= qlen) --n_tiles;  // the last block's second tile holds no live row
+        if (kb * 128 >= klen) n_tiles = 0;
+    }
+    auto blk_tile = [&](int x) { return __builtin_amdgcn_readfirstlane(2 * bl_idx[x >> 1] + (x & 1)); };   // (scalar loads)
+    int t_cur = 0, t_nxt = 0;                                        // BLK: the tile in LDS and the one to fetch next
+    if constexpr (BLK) {
+        if (n_tiles > 0) {
+            t_cur = blk_tile(0);
+            t_nxt = blk_tile(min(1, n_tiles - 1));
+        }
+    }
     if constexpr (WIN) {
         static_assert(KPW == 1, "one key per lane");
         const int shift = klen - qlen;
@@ -502,7 +578,7 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         q_hi = wl < 0 ? (1 << 30) : key - shift + wl;
         if constexpr (VLEN) q_hi = min(q_hi, qlen - 1);
     }
-    const int q_rows = VLEN ? max(qlen, 1) : p.Lq;                   // rows the Q / dO / lse / delta reads may touch
+    const int q_rows = (VLEN || BLK) ? max(qlen, 1) : p.Lq;                   // rows the Q / dO / lse / delta reads may touch
 
     const uint16_t* Q = (const uint16_t*)p.q + (int64_t)b * p.q_bs + head * D;
     const uint16_t* DO = (const uint16_t*)p.dout + (int64_t)b * p.o_bs + head * D;
@@ -553,11 +629,11 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         dst[64 + lane] = in ? -draw : 0.f;
     };
     float gl = 0.f, gd = 0.f;
-    if (!VLEN || n_tiles > 0) {                                      // VLEN: a sample with qlen = 0 has no row to fetch
-        tile_dma<THREADS>(qs, t_first, wave_lds);                    // (a tile index past the end arrives as zeros)
-        tile_dma<THREADS>(dos, t_first, wave_lds + TILE_BYTES);
-        stat_load(t_first, gl, gd);
-        if (tid < 64) stat_store(t_first, gl, gd, stat);
+    if (!(VLEN || BLK) || n_tiles > 0) {                             // VLEN: a sample with qlen = 0 has no row to fetch
+        tile_dma<THREADS>(qs, BLK ? t_cur : t_first, wave_lds);      // (a tile index past the end arrives as zeros)
+        tile_dma<THREADS>(dos, BLK ? t_cur : t_first, wave_lds + TILE_BYTES);
+        stat_load(BLK ? t_cur : t_first, gl, gd);
+        if (tid < 64) stat_store(BLK ? t_cur : t_first, gl, gd, stat);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     for (int t = 0; t < n_tiles; ++t) {
@@ -565,12 +641,14 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         const unsigned char* dot = qt + TILE_BYTES;
         const float* st = stat + (t & 1) * 128;
         const bool more = t + 1 < n_tiles;
+        const int t_sto = t_nxt;                                     // BLK: the tile being fetched during this iteration
         if (more) {
             const uint32_t nq = wave_lds + ((t + 1) & 1) * 2 * TILE_BYTES;
-            tile_dma<THREADS>(qs, t_first + t + 1, nq);
-            tile_dma<THREADS>(dos, t_first + t + 1, nq + TILE_BYTES);
-            stat_load(t_first + t + 1, gl, gd);
+            tile_dma<THREADS>(qs, BLK ? t_nxt : t_first + t + 1, nq);
+            tile_dma<THREADS>(dos, BLK ? t_nxt : t_first + t + 1, nq + TILE_BYTES);
+            stat_load(BLK ? t_nxt : t_first + t + 1, gl, gd);
         }
+        if constexpr (BLK) t_nxt = blk_tile(min(t + 2, n_tiles - 1));   // a tile ahead of its loads
         // One tile = two halves of 32 queries, each with three stages: A  S = Q K^T and dP = dO V^T (16 products,
         // [query][key], lane = key; register r <-> query 64t + 32hb + 16(r>>3) + 8lh + (r&7)); B  the softmax
         // arithmetic (VALU); C  dV^T += dO^T P, dK^T += Q^T dS (16 products, [d][key]).  With ONE wave per SIMD nothing
@@ -674,7 +752,7 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         stage_c(1, 0);
         stage_c(1, 1);
         if (more && tid < 64)                                        // the other stage's statistics: last read a tile ago
-            stat_store(t_first + t + 1, gl, gd, stat + ((t + 1) & 1) * 128);
+            stat_store(BLK ? t_sto : t_first + t + 1, gl, gd, stat + ((t + 1) & 1) * 128);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
 #pragma unroll
@@ -1018,8 +1096,8 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (bwd2_dq_stream()) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
             else hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
-        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr);
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr);
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr, BlkList{});
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr, BlkList{});
         if (wq.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<1>, dim3((wq.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, q_blocks, wq);
     }
@@ -1029,8 +1107,8 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (!(e && e[0] == '0')) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
             else hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
-        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr);
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr);
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr, BlkList{});
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr, BlkList{});
         if (wkv.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<2>, dim3((wkv.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, k_blocks, wkv);
     }
@@ -1069,17 +1147,58 @@ static int launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, con
     const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
     if (a.phase == 0 || a.phase == 2) {
         const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens);
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens);
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{});
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{});
     }
     if (a.phase == 0 || a.phase == 3) {
         const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens);
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens);
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{});
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{});
     }
     return 0;
 }
 // q_lens == nullptr: the band kernels themselves (qlen = Lq), so that call is omh_flash_attn_bwd_band_d128 bit for bit
 int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, hipStream_t s) {
     return q_lens ? launch_attn_bwd2_band<true>(a, wl, wr, q_lens, s) : launch_attn_bwd2_band<false>(a, wl, wr, nullptr, s);
+}
+
+// called by omh_flash_attn_bwd_sparse_d128 (attention_bwd.hip) with validated arguments, o32 set and a checked mask: the
+// phases of omh_launch_attn_bwd2 on the BLK instantiations of the HIP kernels; never split.
+int omh_launch_attn_bwd2_sparse(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_block_mask& m, hipStream_t s) {
+    if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
+        ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
+        return OMH_E_SHAPE;
+    if (((uintptr_t)a.o32 & 15) || (a.o_rs & 3) || (a.o_bs & 3)) return OMH_E_ALIGN;
+    if (a.phase < 0 || a.phase > 3) return OMH_E_BADARG;
+    const int64_t pairs = (int64_t)a.B * a.Lq * a.H;
+    if (pairs >= 0x7fffffffLL) return OMH_E_SHAPE;
+    constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        attr_set = true;
+    }
+    if (a.phase == 0 || a.phase == 1) {
+        const dim3 grid((unsigned)((pairs + 15) / 16));
+        if (q_lens) hipLaunchKernelGGL(attn_bwd2_delta_kernel<true>, grid, dim3(256), 0, s, a, q_lens);
+        else hipLaunchKernelGGL(attn_bwd2_delta_kernel<false>, grid, dim3(256), 0, s, a, nullptr);
+        if (a.phase == 1) return 0;
+    }
+    const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
+    if (a.phase == 0 || a.phase == 2) {
+        const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
+        const BlkList bl = {m.row_cnt, m.row_idx, m.heads, m.q_blocks, m.k_blocks};
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl);
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl);
+    }
+    if (a.phase == 0 || a.phase == 3) {
+        const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
+        const BlkList bl = {m.col_cnt, m.col_idx, m.heads, m.k_blocks, m.q_blocks};
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl);
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl);
+    }
+    return 0;
 }

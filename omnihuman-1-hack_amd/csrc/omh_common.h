@@ -140,6 +140,25 @@ static inline int omh_launch_status() {
 }
 
 
+// ---- block masks (include/omh.h omh_block_mask; attention.hip, attention_bwd2.hip) ----
+// What a BLK kernel gets: one list per (mask head, 128-row block of the workgroup's side) — `cnt` entries of `idx`,
+// ascending indices of the 128-position blocks of the other side (row lists: forward and dQ; column lists: dK / dV).
+struct BlkList {
+    const int32_t* cnt;   // [heads][lists]
+    const int32_t* idx;   // [heads][lists][stride]
+    int heads, lists, stride;
+};
+static inline int omh_block_mask_check(const omh_block_mask* m, int H, int Lq, int Lk) {
+    if (!m->row_cnt || !m->row_idx || !m->col_cnt || !m->col_idx) return OMH_E_BADARG;
+    if (m->heads != 1 && m->heads != H) return OMH_E_BADARG;
+    if (m->q_blocks != (Lq + 127) / 128 || m->k_blocks != (Lk + 127) / 128) return OMH_E_BADARG;
+    if (((uintptr_t)m->row_cnt | (uintptr_t)m->row_idx | (uintptr_t)m->col_cnt | (uintptr_t)m->col_idx) & 3) return OMH_E_ALIGN;
+    return 0;
+}
+// A mask excludes a band.  (0, 0) is what a zero-initialised omh_attn_args holds, so the sparse entries read it as "no
+// band set", not as the one-key band it is elsewhere; both sides < 0 is the unbounded band; anything else is refused.
+static inline bool omh_mask_window_unset(int wl, int wr) { return (wl < 0 && wr < 0) || (wl == 0 && wr == 0); }
+
 // ---- split of a launch's last, partly filled round of workgroups (host side; attention.hip, attention_bwd2.hip) ----
 // A launch of `nwg` equal workgroups on `slots` resident slots takes ceil(nwg / slots) rounds; its last round holds
 // r = nwg mod slots workgroups.  Those r are split into `splits` workers each over their inner loop (`loop_tiles` tiles,

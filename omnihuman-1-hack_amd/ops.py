@@ -169,17 +169,42 @@ def flash_attn_takes_bounded(B, H, Lq, Lk, q_rs, k_rs, o_rs, ldv, window=(-1, -1
     return bool(lib.omh_flash_attn_takes_bounded(C.byref(a)))
 
 
+def _block_mask(block_mask, H, Lq, Lk, window=(-1, -1)):
+    """``block_mask`` (None, a ``sparse.BlockMask`` or a bool tensor) as a BlockMask on the current device, checked
+    against this call: ValueError for a band beside it, a head count other than 1 or H, or other block counts."""
+    if block_mask is None:
+        return None
+    from .sparse import BlockMask
+    if window[0] >= 0 or window[1] >= 0:
+        raise ValueError("a block mask excludes causal / a bounded window (it is not an intersection)")
+    bm = block_mask if isinstance(block_mask, BlockMask) else BlockMask(block_mask, Lq, Lk)
+    if bm.heads not in (1, H):
+        raise ValueError(f"block mask with {bm.heads} heads on a call with {H} (1 or {H} expected)")
+    if (bm.q_blocks, bm.k_blocks) != ((Lq + 127) // 128, (Lk + 127) // 128):
+        raise ValueError(f"block mask of {bm.q_blocks} x {bm.k_blocks} blocks on a call with Lq = {Lq}, Lk = {Lk} "
+                         f"({(Lq + 127) // 128} x {(Lk + 127) // 128} expected)")
+    return bm.to(torch.device("cuda", torch.cuda.current_device()))
+
+
 def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale,
-                   lse=None, q_prescaled=0, o32=None, flags=0, q_lens=None, window=(-1, -1), qk_norm2_max=None):
+                   lse=None, q_prescaled=0, o32=None, flags=0, q_lens=None, window=(-1, -1), qk_norm2_max=None,
+                   block_mask=None):
     """``flags``: ATTN_SHORT_KERNEL | ATTN_ALLOW_SPLIT (include/omh.h, ABI v8): the training step pins the short-sequence
     kernel (forward and re-run take the same one) and lets it split its last round of workgroups over the keys.
     ``q_lens`` (ABI v10): int32 [B] device pointer; output rows past a sample's query length are written as zero.
     ``window`` (ABI v12): (left, right) band around the bottom-right aligned diagonal, a side < 0 unbounded (causal =
     (left, 0)); a bounded side runs the short-sequence kernel.
     ``qk_norm2_max``: float [B, H, 2] device pointer from ``rmsnorm_rope_bf16_pair_bound_raw`` for these q and k: the
-    long-sequence stream then runs without a running max where the bound allows (omh_flash_attn_fwd_d128_bounded)."""
+    long-sequence stream then runs without a running max where the bound allows (omh_flash_attn_fwd_d128_bounded).
+    ``block_mask``: a ``sparse.BlockMask`` / bool block tensor (omh_flash_attn_fwd_sparse_d128: the short-sequence kernel
+    over each query block's list of key blocks, never split, never the bounded stream); ValueError beside a band."""
+    bm = _block_mask(block_mask, H, Lq, Lk, window)
     a = AttnArgs(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale, lse,
                  int(q_prescaled), None, 0, o32, int(flags), q_lens, int(window[0]), int(window[1]))
+    if bm is not None:
+        m = bm.c_struct()
+        check(lib.omh_flash_attn_fwd_sparse_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_sparse_d128")
+        return
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
     ws = None
     if need > 0:
@@ -193,11 +218,14 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
                scale: Optional[float] = None, out: Optional[torch.Tensor] = None, q_lens: Optional[torch.Tensor] = None,
-               window=(-1, -1)):
+               window=(-1, -1), block_mask=None, lse: Optional[torch.Tensor] = None):
     """q [B,Lq,H,128], k [B,Lk,H,128] bf16; vt [B,H*128,ldv] bf16 (V transposed,
     ldv >= roundup(Lk,64)); k_lens / q_lens int32 [B] or None.  Returns [B,Lq,H,128] bf16 (rows past q_lens: zero).
-    ``window`` = (left, right): flash-attn's bottom-right aligned band (causal = (-1, 0)); (-1, -1): full attention."""
-    _dev(q, k, vt, k_lens, out, q_lens)
+    ``window`` = (left, right): flash-attn's bottom-right aligned band (causal = (-1, 0)); (-1, -1): full attention.
+    ``block_mask``: a ``sparse.BlockMask`` or a bool tensor [nQb, nKb] / [H, nQb, nKb] over 128 x 128 blocks — query i
+    sees key j iff its block is kept (and j < k_lens[b], i < q_lens[b]); rows that see no key are zero.  ValueError
+    together with a bounded ``window``.  ``lse``: optional fp32 [B, H, Lq] the log-sum-exp is written to."""
+    _dev(q, k, vt, k_lens, out, q_lens, lse)
     if q_lens is not None:
         assert q_lens.dtype == torch.int32 and q_lens.numel() == q.shape[0]
     B, Lq, H, D = q.shape
@@ -211,12 +239,13 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
         out = torch.empty(B, Lq, H, D, dtype=torch.bfloat16, device=q.device)
     flash_attn_raw(_p(q), _p(k), _p(vt), _p(out), _p(k_lens), B, H, Lq, Lk, q.stride(0), q.stride(1), k.stride(0),
                    k.stride(1), vt.stride(0), out.stride(0), out.stride(1), vt.stride(1),
-                   float(scale if scale is not None else D ** -0.5), q_lens=_p(q_lens), window=window)
+                   float(scale if scale is not None else D ** -0.5), q_lens=_p(q_lens), window=window,
+                   block_mask=block_mask, lse=_p(lse))
     return out
 
 
 def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_prescaled=False, out=None, o32=None,
-                   phase=0, delta=None, split=True, window=(-1, -1), q_lens=None):
+                   phase=0, delta=None, split=True, window=(-1, -1), q_lens=None, block_mask=None):
     """Fused attention backward (include/omh.h).  q, dout: bf16 [B*Lq, H*128]; k, v: bf16 [B*Lk, H*128] (row stride
     free); lse fp32 [B, H, Lq] from ``flash_attn_raw(..., lse=)``; k_lens int32 [B] or None.
     Returns fp32 dq [B*Lq, H*128], dk, dv [B*Lk, H*128] — or, with ``out=(dq, dk, dv)`` bf16 2-D tensors (row stride
@@ -231,8 +260,13 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     additive to ABI v12): a bounded side requires ``o32``; the band kernels run unsplit.  (-1, -1): the call above.
     ``q_lens``: int32 [B], the forward's ``q_lens`` — routes to omh_flash_attn_bwd_varlen_d128 (any ``window``, (-1, -1)
     included; requires ``o32``): rows past a sample's query length get dq = 0, give nothing to dk / dv, and their dout /
-    q / lse / o32 are not read (they may hold NaN)."""
+    q / lse / o32 are not read (they may hold NaN).
+    ``block_mask``: the forward's block mask (omh_flash_attn_bwd_sparse_d128; requires ``o32``, any ``q_lens``; ValueError
+    beside a bounded ``window``): keys no live query sees get dk = dv = 0, live rows that see no key dq = 0."""
     _dev(q, k, v, dout, lse, k_lens, o32, q_lens)
+    bm = _block_mask(block_mask, H, Lq, Lk, window)
+    if bm is not None:
+        assert o32 is not None, "flash_attn_bwd: a block mask needs the forward's fp32 output (o32=)"
     d = H * 128
     for t in (q, k, v, dout):
         assert t.dtype == torch.bfloat16 and t.stride(-1) == 1 and t.shape[-1] == d
@@ -281,6 +315,11 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
                          Lk * dk.stride(0), dk.stride(0), d * ldq, d * ldk, ldq, ldk,
                          float(scale if scale is not None else 128 ** -0.5), int(q_prescaled), bf, _p(o32), int(phase),
                          None, 0)
+    if bm is not None:
+        m = bm.c_struct()
+        check(lib.omh_flash_attn_bwd_sparse_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
+              "omh_flash_attn_bwd_sparse_d128")
+        return dq, dk, dv
     if q_lens is not None:
         check(lib.omh_flash_attn_bwd_varlen_d128(C.byref(a), _p(q_lens), int(window[0]), int(window[1]), _stream()),
               "omh_flash_attn_bwd_varlen_d128")
@@ -302,7 +341,7 @@ class _FlashAttnFunc(torch.autograd.Function):
     omh_flash_attn_bwd_* call backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, k_lens, q_lens, scale, window):
+    def forward(ctx, q, k, v, k_lens, q_lens, scale, window, block_mask=None):
         _dev(q, k, v, k_lens, q_lens)
         B, Lq, H, D = q.shape
         Lk = k.shape[1]
@@ -322,9 +361,10 @@ class _FlashAttnFunc(torch.autograd.Function):
         lse = torch.empty(B, H, Lq, dtype=torch.float32, device=dev)
         # pinned to the short-sequence kernel, as the training step pins it (never split: this flag alone)
         flash_attn_raw(_p(q), _p(k), _p(vt), _p(o), _p(k_lens), B, H, Lq, Lk, Lq * d, d, Lk * d, d, d * Lp, Lq * d, d, Lp,
-                       scale, lse=_p(lse), o32=_p(o32), flags=ATTN_SHORT_KERNEL, q_lens=_p(q_lens), window=window)
+                       scale, lse=_p(lse), o32=_p(o32), flags=ATTN_SHORT_KERNEL, q_lens=_p(q_lens), window=window,
+                       block_mask=block_mask)
         ctx.save_for_backward(q, k, v, o, lse, o32, k_lens, q_lens)
-        ctx.scale, ctx.window = scale, window
+        ctx.scale, ctx.window, ctx.block_mask = scale, window, block_mask
         return o
 
     @staticmethod
@@ -337,23 +377,29 @@ class _FlashAttnFunc(torch.autograd.Function):
                torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device),
                torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device))
         flash_attn_bwd(q.view(B * Lq, d), k.view(B * Lk, d), v.view(B * Lk, d), o.view(B * Lq, d), do.view(B * Lq, d), lse,
-                       k_lens, B, H, Lq, Lk, scale=ctx.scale, out=out, o32=o32, window=ctx.window, q_lens=q_lens)
+                       k_lens, B, H, Lq, Lk, scale=ctx.scale, out=out, o32=o32, window=ctx.window, q_lens=q_lens,
+                       block_mask=ctx.block_mask)
         need = ctx.needs_input_grad
         return (out[0].view(B, Lq, H, D) if need[0] else None, out[1].view(B, Lk, H, D) if need[1] else None,
-                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None)
+                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None, None)
 
 
 def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
-                    q_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None, window=(-1, -1)):
+                    q_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None, window=(-1, -1),
+                    block_mask=None):
     """Differentiable attention (a ``torch.autograd.Function``): q [B,Lq,H,128], k, v [B,Lk,H,128] bf16 (V row-major: the
     padded V^T the kernel reads is built here, by the transpose kernel); k_lens / q_lens int32 [B] or None; ``window`` =
     (left, right) as in ``flash_attn``.  Returns [B,Lq,H,128] bf16 — the bits of ``flash_attn`` on the same inputs
     whenever that call takes the short-sequence kernel.  The forward keeps q, k, v, o, lse, the fp32 output and the
     lens; the backward is one ``flash_attn_bwd`` call with bf16 outputs (omh_flash_attn_bwd_varlen_d128 with q_lens, the
     band entry with a bounded window, omh_flash_attn_bwd_d128 otherwise: no atomics, repeatable bit for bit) and
-    returns gradients only for the inputs that need them."""
+    returns gradients only for the inputs that need them.  ``block_mask`` as in ``flash_attn`` (forward and backward on
+    the block-list kernels, omh_flash_attn_*_sparse_d128; ValueError beside a bounded ``window``)."""
     window = (int(window[0]) if window[0] >= 0 else -1, int(window[1]) if window[1] >= 0 else -1)
-    return _FlashAttnFunc.apply(q, k, v, k_lens, q_lens, float(scale if scale is not None else 128 ** -0.5), window)
+    if block_mask is not None:
+        block_mask = _block_mask(block_mask, q.shape[2], q.shape[1], k.shape[1], window)
+    return _FlashAttnFunc.apply(q, k, v, k_lens, q_lens, float(scale if scale is not None else 128 ** -0.5), window,
+                                block_mask)
 
 
 def layernorm_modulate_raw(x, y, rows, dim, eps, mul_const, mul0, mul1, mul1_stride, add0, add1, add1_stride,

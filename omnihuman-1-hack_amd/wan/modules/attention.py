@@ -24,8 +24,14 @@ __all__ = ["flash_attention", "attention"]
 
 
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None,
-                    causal=False, window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None):
+                    causal=False, window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None,
+                    block_mask=None):
     """q [B, Lq, N, 128], k/v [B, Lk, N, 128]; returns [B, Lq, N, 128] in q's dtype.
+
+    ``block_mask`` (not in the reference: flash-attn takes no mask): a ``sparse.BlockMask`` or a bool tensor
+    [nQb, nKb] / [N, nQb, nKb] over 128 x 128 blocks of the padded sequence — query i sees key j iff its block is kept,
+    j < k_lens[b] and i < q_lens[b]; rows that see no key are zero.  Differentiable like the unmasked call.  Together
+    with ``causal`` or a bounded ``window_size`` it raises ValueError (a mask is not intersected with a band).
 
     With grad enabled and q, k or v requiring it the result carries a ``grad_fn`` (``ops.flash_attn_func``; the casts
     to bf16 and ``q * q_scale`` stay torch ops in front of it, so fp32 inputs — the reference's own call pattern — get
@@ -52,6 +58,8 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     if causal:
         wr = 0
     window = (wl if wl >= 0 else -1, wr if wr >= 0 else -1)
+    if block_mask is not None and window != (-1, -1):
+        raise ValueError("flash_attention: block_mask excludes causal / a bounded window_size")
     if window != (-1, -1) and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         raise NotImplementedError("flash_attention on gfx950: causal / window_size are forward-only through this wrapper; "
                                   "the differentiable band is ops.flash_attn_func(window=)")
@@ -66,7 +74,7 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     ql = None if q_lens is None else q_lens.to(device=q.device, dtype=torch.int32).contiguous()
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         o = ops.flash_attn_func(q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), kl, ql,
-                                scale=softmax_scale, window=window)
+                                scale=softmax_scale, window=window, block_mask=block_mask)
         return o.type(out_dtype)
     qb = q.to(torch.bfloat16).contiguous()
     kb = k.to(torch.bfloat16).contiguous()
@@ -75,12 +83,12 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     vt[:, :, :Lk] = v.to(torch.bfloat16).reshape(B, Lk, N * D).transpose(1, 2)   # layout change only
     # q_lens (attention.py:55-60,79): the reference cuts the queries past q_lens[b] out of the packed batch — and can only
     # un-flatten the result when every q_lens[b] == Lq (attention.py:110); here those rows come back as zeros
-    o = ops.flash_attn(qb, kb, vt, kl, scale=softmax_scale, q_lens=ql, window=window)
+    o = ops.flash_attn(qb, kb, vt, kl, scale=softmax_scale, q_lens=ql, window=window, block_mask=block_mask)
     return o.type(out_dtype)
 
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,
-              window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, fa_version=None):
+              window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, fa_version=None, block_mask=None):
     """attention.py:133-179 — same kernel; the reference's SDPA fallback is not needed here."""
     return flash_attention(q, k, v, q_lens, k_lens, dropout_p, softmax_scale, q_scale, causal, window_size,
-                           deterministic, dtype, fa_version)
+                           deterministic, dtype, fa_version, block_mask=block_mask)

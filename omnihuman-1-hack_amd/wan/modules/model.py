@@ -224,6 +224,25 @@ class WanSelfAttention(nn.Module):
         self.norm_q = WanRMSNorm(dim, eps=eps) if qk_norm else nn.Identity()
         self.norm_k = WanRMSNorm(dim, eps=eps) if qk_norm else nn.Identity()
         self._packed = _Packed()
+        # WanModel.set_attention_block_mask: a sparse.BlockMask or None — a plain attribute (no parameter, no buffer,
+        # not in the state_dict); read by the self-attention only (_attend / the training block), never by _attend_ctx
+        self._block_mask = None
+
+    def _mask_for(self, S):
+        """The block mask of a self-attention over S (padded) positions, or None; ValueError when it was built for
+        another number of blocks or the layer also has a bounded window."""
+        bm = self._block_mask
+        if bm is None:
+            return None
+        if self.window_size[0] >= 0 or self.window_size[1] >= 0:
+            raise ValueError(f"a block mask excludes window_size={tuple(self.window_size)} (it is not an intersection)")
+        nb = (S + 127) // 128
+        if bm.q_blocks != nb or bm.k_blocks != nb:
+            raise ValueError(f"the attention block mask has {bm.q_blocks} x {bm.k_blocks} blocks; seq_len = {S} needs "
+                             f"{nb} x {nb} (ceil(seq_len / 128))")
+        if bm.heads not in (1, self.num_heads):
+            raise ValueError(f"the attention block mask has {bm.heads} heads; 1 or {self.num_heads} expected")
+        return bm
 
     # packed weights ---------------------------------------------------------
     def _w_qk(self):
@@ -250,6 +269,7 @@ class WanSelfAttention(nn.Module):
         """h bf16 [B*S, dim] -> attention output bf16 [B*S, dim] (before o-proj)."""
         B, S, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
         R = B * S
+        bmask = self._mask_for(S)
         # q|k projection kept in bf16 (fp32 accumulate): the normalisation statistics are taken in fp32 from
         # it; measured effect on the 30-layer output < 1e-3 relative RMS, and it halves this step's traffic
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
@@ -284,7 +304,8 @@ class WanSelfAttention(nn.Module):
         # stream then needs no running max (a bound on this call's scores: ops.flash_attn_raw, qk_norm2_max)
         window = tuple(self.window_size)
         nmax = None
-        if D == 128 and d <= 5120 and ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
+        # (a block mask runs the short-sequence kernel over its lists: no long-sequence stream, so no bound either)
+        if bmask is None and D == 128 and d <= 5120 and ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
             nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
         self.last_qk_norm2_max = nmax                                    # (read by tools/attn_bound_values.py)
         norm_args = (ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(wq) if wq is not None else None,
@@ -304,7 +325,7 @@ class WanSelfAttention(nn.Module):
         # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
                            d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1, window=window,
-                           qk_norm2_max=ptr(nmax) if nmax is not None else None)
+                           qk_norm2_max=ptr(nmax) if nmax is not None else None, block_mask=bmask)
         return o
 
     def forward(self, x, seq_lens, grid_sizes, freqs, _fc: Optional["_FwdCtx"] = None):
@@ -692,6 +713,42 @@ class WanModel(nn.Module):
             sd.update(load_file(f))
         model.load_state_dict(sd, strict=True)
         return model
+
+    # ------------------------------------------------------------------ sparsity
+    def set_attention_block_mask(self, mask, layers=None):
+        """Restrict the SELF-attention of ``layers`` (None: every block; else an iterable of block indices) to the kept
+        128 x 128 blocks of ``mask``: a bool tensor ``[nb, nb]`` (all heads) or ``[num_heads, nb, nb]``, a
+        ``sparse.BlockMask``, or None to clear.  nb = ceil(seq_len / 128) for the ``seq_len`` later passed to ``forward``
+        (checked there: ValueError); the mask is in padded-sequence coordinates, shared by the samples of a batch, and
+        ``seq_lens`` still limits the keys.  Honoured by ``forward`` (inference and training), ``forward_cfg_pair`` and
+        the LoRA paths; cross-attention is never masked.  The mask is no parameter or buffer and is in neither ``config``
+        nor the ``state_dict``.  A model built with a bounded ``window_size`` refuses a mask (ValueError)."""
+        import importlib
+        sparse = importlib.import_module(ops.__package__ + ".sparse")
+        idx = list(range(len(self.blocks))) if layers is None else [int(i) for i in layers]
+        for i in idx:
+            if not 0 <= i < len(self.blocks):
+                raise ValueError(f"set_attention_block_mask: no block {i} (the model has {len(self.blocks)})")
+        bm = None
+        if mask is not None:
+            if self.window_size[0] >= 0 or self.window_size[1] >= 0:
+                raise ValueError(f"set_attention_block_mask: the model has window_size={tuple(self.window_size)}; a block "
+                                 "mask excludes a bounded window (it is not an intersection)")
+            if isinstance(mask, sparse.BlockMask):
+                bm = mask
+            else:
+                if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() not in (2, 3):
+                    raise ValueError("set_attention_block_mask: a bool tensor [nb, nb] or [num_heads, nb, nb] is expected")
+                if mask.shape[-1] != mask.shape[-2]:
+                    raise ValueError(f"set_attention_block_mask: self-attention needs a square mask, got {tuple(mask.shape)}")
+                L = int(mask.shape[-1]) * sparse.BLOCK
+                bm = sparse.BlockMask(mask, L, L)
+            if bm.q_blocks != bm.k_blocks:
+                raise ValueError("set_attention_block_mask: self-attention needs a square mask")
+            if bm.heads not in (1, self.num_heads):
+                raise ValueError(f"set_attention_block_mask: {bm.heads} heads in the mask, 1 or {self.num_heads} expected")
+        for i in idx:
+            self.blocks[i].self_attn._block_mask = bm
 
     # ------------------------------------------------------------------ forward
     def _rope(self, device):
