@@ -357,6 +357,64 @@ int omh_flash_attn_bwd_sparse_d128(const omh_attn_bwd_args* args, const int32_t*
                                    omh_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Block masks chosen from q and k on the device (top-p over block-pooled scores), additive to ABI v12 (OMH_ABI_VERSION
+ * unchanged, no existing struct or entry changed).  Three launches make the tables of an omh_block_mask from the bf16
+ * q and k an attention call is about to use, with no host round trip: pool, select, tables.
+ *
+ * The rule.  One call with B samples, H heads, head dim 128, Lq queries, Lk keys; nQb = ceil(Lq / 128), nKb =
+ * ceil(Lk / 128); qlen_b / klen_b = q_lens[b] / k_lens[b], or Lq / Lk without them (clamped to [0, L]); c_J =
+ * clamp(klen_b - 128 J, 0, 128) live keys of block J of sample b (c_I likewise for query blocks); a block is live iff c > 0.
+ *   pooled rows   xm[b][h][I][:] = fp32 mean over the c_I live rows of block I of the operand; zeros for a dead block
+ *   coherence     coh[b][h][I]   = |xm|^2 / ((1 / c_I) sum_i |x_i|^2) in [0, 1]; 1 where the denominator is 0
+ *   probability   for a live query block I:  s[J] = score_scale * qm_I . km_J + log2(c_J) over live J,
+ *                 p[J] = 2^(s[J] - max s) / sum_J 2^(s[J] - max s);  p[J] = 0 for dead J
+ *   top-p         mass in (0, 1]: theta = the largest value among the p[J] with  sum_{p[J] >= theta} p[J] >= mass;
+ *                 J is kept iff p[J] >= theta (ties are kept together: the set depends on the values, not on an order).
+ *                 mass = 1 keeps every live J.  The kernel bisects on the bit pattern of theta; there is no sort.
+ *   low coherence min_coherence in [0, 1], 0 = off: a live query block with coh_q < min_coherence keeps every live key
+ *                 block of its sample; a live key block with coh_k < min_coherence is kept by every live query block.
+ *   always        an optional uint8 mask [always_heads][nQb][nKb] (always_heads 1 or H, non-zero = keep) is OR-ed in; a
+ *                 query block dead in every sample keeps only these entries.
+ *   batch         a block mask is shared by the samples of a batch: the result is the OR over b of the per-sample
+ *                 selections (at B = 1 it is the per-sample mask).
+ * Deterministic: no atomics, sums in a fixed order, the same bytes every run.  Pointers are device pointers.
+ *
+ * omh_block_pool_d128: n_ops (1 or 2) operands in one launch (q and k of one call).  Operand rows [B * L, ld] bf16 with
+ * head h in columns [128 h, 128 h + 128); x 16-byte aligned, ld % 8 == 0, ld >= 128 H (OMH_E_ALIGN / OMH_E_BADARG);
+ * lens int32 [B] or NULL; mean fp32 [B][H][nb][128], coh fp32 [B][H][nb], nb = ceil(L / 128), every element written.
+ * One workgroup per (sample, block, head): 16-byte loads, fp32 sums, column sums and the sum of squares in one pass.
+ * ---------------------------------------------------------------------- */
+typedef struct omh_block_pool_operand {
+    const void* x; int64_t ld;
+    int32_t L, reserved;              /* reserved: 0 */
+    const int32_t* lens;
+    float* mean; float* coh;
+} omh_block_pool_operand;
+int omh_block_pool_d128(const omh_block_pool_operand* operands, int32_t n_ops, int32_t B, int32_t H, omh_stream_t stream);
+
+/* omh_block_select: the rule above from the pooled tensors of omh_block_pool_d128 (q_mean [B][H][nQb][128], q_coh
+ * [B][H][nQb], k_mean / k_coh likewise; lens as given to the pool) into mask uint8 [H][nQb][nKb] (0 / 1; every byte
+ * written, so nothing needs clearing; the OR over samples is taken in registers in sample order).  always may be NULL
+ * (always_heads ignored).  OMH_E_BADARG: a null pointer, sizes <= 0, mass outside (0, 1], min_coherence outside [0, 1],
+ * always_heads not in {1, H}; OMH_E_SHAPE: nKb > 1024.  One wave per (head, query block). */
+typedef struct omh_block_select_args {
+    const float* q_mean; const float* q_coh; const float* k_mean; const float* k_coh;
+    const int32_t* q_lens; const int32_t* k_lens;
+    const uint8_t* always; uint8_t* mask;
+    int32_t B, H, Lq, Lk, always_heads;
+    float score_scale, mass, min_coherence;
+} omh_block_select_args;
+int omh_block_select(const omh_block_select_args* args, omh_stream_t stream);
+
+/* omh_block_mask_tables: mask uint8 [heads][q_blocks][k_blocks] (non-zero = kept) -> the four int32 tables of
+ * omh_block_mask: row_cnt [heads][q_blocks], row_idx [heads][q_blocks][k_blocks], col_cnt [heads][k_blocks], col_idx
+ * [heads][k_blocks][q_blocks].  The kept indices stand ascending in the first cnt entries of a list; entries past cnt
+ * are not written.  One wave per list (ballot + prefix count).  OMH_E_BADARG: a null pointer or a size <= 0;
+ * OMH_E_ALIGN: a table that is not 4-byte aligned. */
+int omh_block_mask_tables(const uint8_t* mask, int32_t heads, int32_t q_blocks, int32_t k_blocks, int32_t* row_cnt,
+                          int32_t* row_idx, int32_t* col_cnt, int32_t* col_idx, omh_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * LayerNorm (no affine) fused with adaLN modulation, fp32 in -> bf16 out.
  * Replaces WanLayerNorm + "x*(1+scale)+shift" (model.py:91-104,292-293,
  * 314-315,358) and the affine norm3 (model.py:263-265,313).

@@ -133,6 +133,18 @@ class BlockMaskArgs(C.Structure):
                 ("row_cnt", vp), ("row_idx", vp), ("col_cnt", vp), ("col_idx", vp)]
 
 
+class BlockPoolOperand(C.Structure):
+    """omh_block_pool_operand (additive to ABI v12): one bf16 operand of omh_block_pool_d128 and its outputs."""
+    _fields_ = [("x", vp), ("ld", i64), ("L", i32), ("reserved", i32), ("lens", vp), ("mean", vp), ("coh", vp)]
+
+
+class BlockSelectArgs(C.Structure):
+    """omh_block_select_args (additive to ABI v12)."""
+    _fields_ = [("q_mean", vp), ("q_coh", vp), ("k_mean", vp), ("k_coh", vp), ("q_lens", vp), ("k_lens", vp),
+                ("always", vp), ("mask", vp), ("B", i32), ("H", i32), ("Lq", i32), ("Lk", i32), ("always_heads", i32),
+                ("score_scale", f32), ("mass", f32), ("min_coherence", f32)]
+
+
 class PartialReduce(C.Structure):
     _fields_ = [("part", vp), ("nj", i32), ("np", i32), ("nb", i32), ("dim", i32), ("grid_y", i32),
                 ("out", vp * 3), ("stride", i64 * 3)]
@@ -199,6 +211,9 @@ _SIGS = {
     "omh_flash_attn_bwd_varlen_d128": (i32, [C.POINTER(AttnBwdArgs), vp, i32, i32, vp]),
     "omh_flash_attn_fwd_sparse_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(BlockMaskArgs), vp]),
     "omh_flash_attn_bwd_sparse_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(BlockMaskArgs), vp]),
+    "omh_block_pool_d128": (i32, [C.POINTER(BlockPoolOperand), i32, i32, i32, vp]),
+    "omh_block_select": (i32, [C.POINTER(BlockSelectArgs), vp]),
+    "omh_block_mask_tables": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "omh_layernorm_modulate": (i32, [vp, vp, i64, i32, f32, f32, vp, vp, i64, vp, vp, i64, i64, vp]),
     "omh_rmsnorm_rope": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, vp]),
     "omh_rmsnorm_rope_bf16": (i32, [vp, i64, vp, i64, i32, vp, f32, i32, vp, vp, i32, i32, vp, i32, f32, vp]),

@@ -16,9 +16,14 @@ full attention (``q_lens`` / ``k_lens`` honoured) goes through ``ops.flash_attn_
 each input's own dtype and shape.  The band's backward exists too (``ops.flash_attn_func(window=)``); through this
 wrapper a bounded window with a grad-requiring input is still refused — see ``flash_attention``.
 """
+import importlib
+import math
+
 import torch
 
 from .._backend import ops
+
+_sparse = importlib.import_module(ops.__package__ + ".sparse")
 
 __all__ = ["flash_attention", "attention"]
 
@@ -32,6 +37,10 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     [nQb, nKb] / [N, nQb, nKb] over 128 x 128 blocks of the padded sequence — query i sees key j iff its block is kept,
     j < k_lens[b] and i < q_lens[b]; rows that see no key are zero.  Differentiable like the unmasked call.  Together
     with ``causal`` or a bounded ``window_size`` it raises ValueError (a mask is not intersected with a band).
+    A ``sparse.DynamicBlockPolicy`` in its place lets the call choose the mask itself (``sparse.block_mask_from_qk`` on
+    ``q * q_scale`` and ``k`` as bf16, ``q_lens`` / ``k_lens`` honoured): built on the device with no host synchronisation,
+    shared by the samples of the batch (the union of their selections), and no gradient flows through the selection — the
+    call stays differentiable exactly as with that mask handed in.
 
     With grad enabled and q, k or v requiring it the result carries a ``grad_fn`` (``ops.flash_attn_func``; the casts
     to bf16 and ``q * q_scale`` stay torch ops in front of it, so fp32 inputs — the reference's own call pattern — get
@@ -72,6 +81,9 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         q = q * q_scale
     kl = None if k_lens is None else k_lens.to(device=q.device, dtype=torch.int32).contiguous()
     ql = None if q_lens is None else q_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    if isinstance(block_mask, _sparse.DynamicBlockPolicy):
+        block_mask = _sparse.block_mask_from_qk(q.detach().to(torch.bfloat16), k.detach().to(torch.bfloat16), block_mask, ql, kl,
+                                                (softmax_scale if softmax_scale is not None else D ** -0.5) * math.log2(math.e))
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         o = ops.flash_attn_func(q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), kl, ql,
                                 scale=softmax_scale, window=window, block_mask=block_mask)

@@ -39,6 +39,11 @@ ptr = ops.ptr
 __all__ = ["WanModel"]
 
 
+def _sparse():
+    import importlib
+    return importlib.import_module(ops.__package__ + ".sparse")
+
+
 # ----------------------------------------------------------------------------
 # reference-compatible helpers
 # ----------------------------------------------------------------------------
@@ -227,6 +232,24 @@ class WanSelfAttention(nn.Module):
         # WanModel.set_attention_block_mask: a sparse.BlockMask or None — a plain attribute (no parameter, no buffer,
         # not in the state_dict); read by the self-attention only (_attend / the training block), never by _attend_ctx
         self._block_mask = None
+        # WanModel.set_attention_block_policy: a sparse.DynamicBlockPolicy or None, kept the same way; the mask the last
+        # self-attention call built under it is left in last_block_mask for inspection
+        self._block_policy = None
+        self.last_block_mask = None
+
+    def _dynamic_mask(self, q, k, B, S, lens32):
+        """The block mask the layer's policy chooses for this call's q and k (bf16 [B*S, dim], q already carrying
+        softmax_scale * log2(e)), built on the device: sparse.block_mask_from_rows.  None without a policy."""
+        pol = self._block_policy
+        if pol is None:
+            return None
+        if self._block_mask is not None:
+            raise ValueError("the layer has both a static block mask and a block policy")
+        if self.window_size[0] >= 0 or self.window_size[1] >= 0:
+            raise ValueError(f"a block policy excludes window_size={tuple(self.window_size)} (it is not an intersection)")
+        bm = _sparse().block_mask_from_rows(q, k, B, self.num_heads, S, S, self.dim, self.dim, pol, 1.0, None, lens32)
+        self.last_block_mask = bm
+        return bm
 
     def _mask_for(self, S):
         """The block mask of a self-attention over S (padded) positions, or None; ValueError when it was built for
@@ -305,7 +328,8 @@ class WanSelfAttention(nn.Module):
         window = tuple(self.window_size)
         nmax = None
         # (a block mask runs the short-sequence kernel over its lists: no long-sequence stream, so no bound either)
-        if bmask is None and D == 128 and d <= 5120 and ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
+        if bmask is None and self._block_policy is None and D == 128 and d <= 5120 and \
+                ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
             nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
         self.last_qk_norm2_max = nmax                                    # (read by tools/attn_bound_values.py)
         norm_args = (ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(wq) if wq is not None else None,
@@ -316,6 +340,8 @@ class WanSelfAttention(nn.Module):
         else:
             ops.rmsnorm_rope_bf16_pair_raw(*norm_args, out_scale0=q_scale, out_scale1=1.0)
         del qk
+        if self._block_policy is not None:             # the mask is chosen from the q and k this call attends with
+            bmask = self._dynamic_mask(q, k, B, S, fc.seq_lens32)
         if not fused:
             # V^T[b] = Wv h_b^T + bv  ->  [B, dim, Sp]   (pad columns stay zero)
             wv, bv = self._w("v")
@@ -747,8 +773,51 @@ class WanModel(nn.Module):
                 raise ValueError("set_attention_block_mask: self-attention needs a square mask")
             if bm.heads not in (1, self.num_heads):
                 raise ValueError(f"set_attention_block_mask: {bm.heads} heads in the mask, 1 or {self.num_heads} expected")
+        if bm is not None:
+            for i in idx:
+                if self.blocks[i].self_attn._block_policy is not None:
+                    raise ValueError(f"set_attention_block_mask: block {i} has a block policy; clear it first "
+                                     "(set_attention_block_policy(None))")
         for i in idx:
             self.blocks[i].self_attn._block_mask = bm
+
+    def set_attention_block_policy(self, policy, layers=None):
+        """Let the SELF-attention of ``layers`` (None: every block; else an iterable of block indices) choose its own
+        block mask per call, per head, from the q and k it is about to attend with: ``policy`` is a
+        ``sparse.DynamicBlockPolicy`` (top-p over block-pooled scores; the rule: include/omh.h), or None to clear.  The
+        mask is built on the device after the norm / RoPE kernel, with no host synchronisation, and handed to the
+        block-list kernels; the layer keeps it in ``self_attn.last_block_mask``.  It is shared by the samples of a batch
+        (the union of their selections; at batch 1 the sample's own) and ``seq_lens`` limits the keys it is chosen from.
+        Honoured by ``forward`` (inference and training: a block's backward and its checkpoint re-run use the mask its
+        forward built), ``forward_cfg_pair`` (block 0's shared mask is built once) and the LoRA paths; cross-attention
+        never is.  No parameter, no buffer, not in ``config`` or the ``state_dict``.  Raises ValueError for a layer that
+        has a static mask (``set_attention_block_mask``), a model with a bounded ``window_size``, and an ``always``
+        whose block count the ``seq_len`` of a later ``forward`` does not match (raised there)."""
+        sparse = _sparse()
+        idx = list(range(len(self.blocks))) if layers is None else [int(i) for i in layers]
+        for i in idx:
+            if not 0 <= i < len(self.blocks):
+                raise ValueError(f"set_attention_block_policy: no block {i} (the model has {len(self.blocks)})")
+        if policy is not None:
+            if not isinstance(policy, sparse.DynamicBlockPolicy):
+                raise ValueError("set_attention_block_policy: a sparse.DynamicBlockPolicy (or None) is expected")
+            if self.window_size[0] >= 0 or self.window_size[1] >= 0:
+                raise ValueError(f"set_attention_block_policy: the model has window_size={tuple(self.window_size)}; a "
+                                 "block policy excludes a bounded window (it is not an intersection)")
+            a = policy.always
+            if a is not None:
+                if a.shape[-1] != a.shape[-2]:
+                    raise ValueError(f"set_attention_block_policy: self-attention needs a square always, got {tuple(a.shape)}")
+                if a.dim() == 3 and a.shape[0] not in (1, self.num_heads):
+                    raise ValueError(f"set_attention_block_policy: {a.shape[0]} heads in always, 1 or {self.num_heads} expected")
+            for i in idx:
+                if self.blocks[i].self_attn._block_mask is not None:
+                    raise ValueError(f"set_attention_block_policy: block {i} has a static block mask; clear it first "
+                                     "(set_attention_block_mask(None))")
+        for i in idx:
+            self.blocks[i].self_attn._block_policy = policy
+            if policy is None:
+                self.blocks[i].self_attn.last_block_mask = None
 
     # ------------------------------------------------------------------ forward
     def _rope(self, device):

@@ -677,7 +677,7 @@ def _vt_buffer(model, key, B, d, Lp, L, dev, keep):
 
 
 # ----------------------------------------------------------------------------- block forward (training)
-def _block_forward(model, blk, idx, st, x0, P, keep, need=True):
+def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
     """The inference block (model.py:279-330 on libomh.so, WanAttentionBlock.forward of this package) with the
     residual stream out of place and the backward's extra tensors emitted by the producing epilogues.  x0 fp32
     [B, S, d] is left untouched.  Returns (x3, S) — S holds what ``_block_backward`` reads.  ``need = False`` (the
@@ -761,14 +761,17 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True):
     win = tuple(sa.window_size)                             # the band (model.py:151-156): its backward needs o32
     if need and not _ATTN_BWD2 and (win[0] >= 0 or win[1] >= 0):
         raise NotImplementedError(f"OMH_ATTN_BWD=v1 has no band backward: window_size={win} needs the default kernels")
-    bmask = sa._mask_for(Sq)                                # WanModel.set_attention_block_mask: the block-list kernels
+    if bmask is None:                                       # (else: the checkpoint re-run, handed the forward's own mask)
+        bmask = sa._mask_for(Sq)                            # WanModel.set_attention_block_mask: the block-list kernels
+        if sa._block_policy is not None:                    # set_attention_block_policy: chosen from this call's q and k
+            bmask = sa._dynamic_mask(q, k, B, Sq, fc.seq_lens32)
     if need and not _ATTN_BWD2 and bmask is not None:
         raise NotImplementedError("OMH_ATTN_BWD=v1 has no block-mask backward: the mask needs the default kernels")
     ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, Sq, Sq, Sq * d, d, Sq * d, d, d * Sp,
                        Sq * d, d, Sp, D ** -0.5, lse=ptr(lse_sa) if need else None, q_prescaled=1,
                        o32=ptr(o32_sa) if o32_sa is not None else None, flags=_ATTN_FLAGS, window=win, block_mask=bmask)
     x1, y1 = resid(x0, o, P["wo"], sa.o.bias.detach(), 2, True)
-    S.update(h1=h1, qk=qk, q=q, k=k, vt=vt, o=o, lse_sa=lse_sa, y1=y1, x1=x1, o32_sa=o32_sa)
+    S.update(h1=h1, qk=qk, q=q, k=k, vt=vt, o=o, lse_sa=lse_sa, y1=y1, x1=x1, o32_sa=o32_sa, bmask=bmask)
     # ---- cross-attention: x2 = x1 + o(attn(norm3(x1), context))                                     model.py:313
     h3 = bf(R, d)
     if blk.cross_attn_norm:
@@ -1081,7 +1084,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     v = ops.transpose_bf16_batched(S["vt"], Sq)                       # [B*S, d]
     dqkv = bf(R, 3 * d)                                               # dq | dk | dv, one buffer
     _attn_bwd(q, k, v, o, do, S["lse_sa"], fc.seq_lens32, B, N, Sq, Sq, D ** -0.5,
-              (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, tuple(sa.window_size), sa._mask_for(Sq))
+              (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, tuple(sa.window_size), S["bmask"])
     qk = S["qk"]
     rms_bwd(ptr(qk), True, 2 * d, ptr(dqkv), 3 * d, R, [sa._norm_w("norm_q"), sa._norm_w("norm_k")], sa.qk_norm, True,
             ["self_attn.norm_q.weight", "self_attn.norm_k.weight"], sa, n_seg=2, seg_x=d, seg_dy=d)   # q and k: one launch
@@ -1181,6 +1184,7 @@ class _BlockFn(torch.autograd.Function):
             out, S = _block_forward(model, blk, idx, st, x0, st.packs[idx], keep, need=keep)
         ctx.model, ctx.st, ctx.idx = model, st, idx
         ctx.kept = S if keep else None
+        ctx.bmask = S["bmask"]                               # the backward (and its re-run of the block) uses this mask
         ctx.save_for_backward(x0)
         return out
 
@@ -1198,7 +1202,7 @@ class _BlockFn(torch.autograd.Function):
             S = ctx.kept
             ctx.kept = None
             if S is None:                                    # use_checkpoint: re-run the forward's kernels on its input
-                _, S = _block_forward(model, blk, idx, st, x0, P, False)
+                _, S = _block_forward(model, blk, idx, st, x0, P, False, bmask=ctx.bmask)
             # The block backward updates the incoming gradient IN PLACE.  That is only legal when the buffer belongs to
             # this node: autograd hands a node the producer's own tensor when the block output has ONE consumer (the next
             # block / the head allocate a fresh dx), but a caller that also taps block outputs (the reference's
