@@ -357,6 +357,31 @@ int omh_flash_attn_bwd_sparse_d128(const omh_attn_bwd_args* args, const int32_t*
                                    omh_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Chunk-causal attention (a staircase over frame groups), additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout
+ * changed).  The reference has no counterpart: it denoises a clip as one bidirectional sequence.  With
+ *   qlen / klen = q_lens[b] / k_lens[b] (or Lq / Lk), clamped as elsewhere,
+ *   chunk = C >= 1 tokens, left_chunks = W (< 0: unbounded), q_offset = P >= 0 (position of query row 0 on the key axis)
+ * query i sees key j iff
+ *   i < qlen  and  j < klen  and  j div C <= (P + i) div C  and  (W < 0 or j div C >= (P + i) div C - W).
+ * Positions are absolute: no bottom-right shift.  From the query: the keys of row i are [max(0, (I - W) C), min(klen,
+ * (I + 1) C)) with I = (P + i) div C (lower end 0 for W < 0).  From the key: key j of chunk J = j div C is seen by the
+ * rows i with J C <= P + i < (J + W + 1) C (no upper end for W < 0).  C need not be a multiple of anything.
+ * A live row that sees no key gets o = 0, lse = -inf, dq = 0 (written); a key no live query sees gets dk = dv = 0
+ * (written); rows at or past qlen as in the varlen entries (zero output / gradient, their memory never used).
+ * With C >= max(Lk, P + Lq) and W < 0 the call is full attention, bit for bit the plain entry on the short-sequence
+ * kernel.  Served by the short-sequence kernels only (each workgroup runs the tiles its rows / keys can see and masks
+ * the ones a stair edge cuts per element), never split, the workspace is declined, no atomics: repeatable bit for bit.
+ * The mask is not combined with anything: a band that is set is OMH_E_BADARG ((0, 0) reads as "not set", as in the
+ * sparse entries), so are a NULL struct, chunk <= 0, q_offset < 0 and reserved != 0; q_offset + Lq + Lk >= 2^28 is
+ * OMH_E_SHAPE.  lse is optional in the forward; the backward has the o32 / lse / delta / phase / out_bf16 / q_prescaled
+ * contract of omh_flash_attn_bwd_varlen_d128 (o32 REQUIRED).
+ * ---------------------------------------------------------------------- */
+typedef struct omh_chunk_causal { int32_t chunk, left_chunks, q_offset, reserved; } omh_chunk_causal;
+int omh_flash_attn_fwd_chunk_d128(const omh_attn_args* args, const omh_chunk_causal* rule, omh_stream_t stream);
+int omh_flash_attn_bwd_chunk_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_chunk_causal* rule,
+                                  omh_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Block masks chosen from q and k on the device (top-p over block-pooled scores), additive to ABI v12 (OMH_ABI_VERSION
  * unchanged, no existing struct or entry changed).  Three launches make the tables of an omh_block_mask from the bf16
  * q and k an attention call is about to use, with no host round trip: pool, select, tables.

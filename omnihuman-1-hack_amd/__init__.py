@@ -17,6 +17,7 @@ libomh.so and fails loudly when it is missing and cannot be built.
 from . import _lib  # noqa: F401  (loads libomh.so; raises if unavailable)
 from . import ops  # noqa: F401
 from . import sparse  # noqa: F401  (block masks of the block-sparse attention)
+from . import causal  # noqa: F401  (chunk-causal attention: the rule, the K / V cache, the rollout loop)
 
 __version__ = "0.1.0"
 from . import lora  # noqa: F401

@@ -133,6 +133,11 @@ class BlockMaskArgs(C.Structure):
                 ("row_cnt", vp), ("row_idx", vp), ("col_cnt", vp), ("col_idx", vp)]
 
 
+class ChunkCausalArgs(C.Structure):
+    """omh_chunk_causal (additive to ABI v12): the chunk-causal staircase of omh_flash_attn_*_chunk_d128."""
+    _fields_ = [("chunk", i32), ("left_chunks", i32), ("q_offset", i32), ("reserved", i32)]
+
+
 class BlockPoolOperand(C.Structure):
     """omh_block_pool_operand (additive to ABI v12): one bf16 operand of omh_block_pool_d128 and its outputs."""
     _fields_ = [("x", vp), ("ld", i64), ("L", i32), ("reserved", i32), ("lens", vp), ("mean", vp), ("coh", vp)]
@@ -211,6 +216,8 @@ _SIGS = {
     "omh_flash_attn_bwd_varlen_d128": (i32, [C.POINTER(AttnBwdArgs), vp, i32, i32, vp]),
     "omh_flash_attn_fwd_sparse_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(BlockMaskArgs), vp]),
     "omh_flash_attn_bwd_sparse_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(BlockMaskArgs), vp]),
+    "omh_flash_attn_fwd_chunk_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(ChunkCausalArgs), vp]),
+    "omh_flash_attn_bwd_chunk_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(ChunkCausalArgs), vp]),
     "omh_block_pool_d128": (i32, [C.POINTER(BlockPoolOperand), i32, i32, i32, vp]),
     "omh_block_select": (i32, [C.POINTER(BlockSelectArgs), vp]),
     "omh_block_mask_tables": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),

@@ -82,10 +82,19 @@ struct AttnSplit {
 // visible.  The list is cut at the first block at or past klen and the last block loses its second tile when that holds
 // no live key, so no tile of the loop is all -inf.  The next tile's index is a scalar read one tile before its loads are
 // issued.  q_lens as in the unlimited kernel, and a workgroup with no live row runs no tile.  Never split.
-template <bool WIN, bool BLK = false>
+// CHK (with WIN): the chunk-causal staircase (include/omh.h omh_chunk_causal; omh_common.h ChunkRule) — the band's
+// machinery with another rule for the two intervals: row i at position off + i, chunk I = (off + i) / chunk, sees keys
+// [(I - left) chunk, min(klen, (I + 1) chunk)); the workgroup runs the key tiles from its first live row's lower end to its
+// last live row's upper end, and masks per element only the tiles a stair edge of one of its rows cuts (a wave-uniform
+// test against the interval every live row sees whole).  A workgroup's work grows with its position, so the query tiles
+// of a head are handed out last tile first: the long ones start first and the launch ends on short ones.  The divisions
+// happen here, once per workgroup and once per row.  Never split.
+template <bool WIN, bool BLK = false, bool CHK = false>
 __global__ __launch_bounds__(256, 2)
-void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk, const BlkList bl) {
+void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk, const BlkList bl,
+                                const ChunkRule ck) {
     static_assert(!(WIN && BLK), "a block mask excludes the band");
+    static_assert(!CHK || WIN, "the staircase runs on the band's masking");
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (KT_BYTES + VT_BYTES)];
 
     const int tid = threadIdx.x;
@@ -102,7 +111,7 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     } else {
         wid = xcd_remap(blockIdx.x, wk.n_regular);
     }
-    const int bh = wid / q_tiles, qt = wid % q_tiles;
+    const int bh = wid / q_tiles, qt = CHK ? q_tiles - 1 - wid % q_tiles : wid % q_tiles;
     const int b = bh / p.H, head = bh % p.H;
 
     int klen = p.k_lens ? p.k_lens[b] : p.Lk;
@@ -110,13 +119,23 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     const int n_tiles_all = (klen + KB - 1) / KB;
     int t_first = 0, n_tiles = n_tiles_all;
     int band_shift = 0;                                   // WIN: key index of the band's centre for query row 0
+    int whole_lo = 0, whole_hi = -1;                      // CHK: the keys EVERY live row of the workgroup sees
     if constexpr (WIN) {
         int qlen = p.q_lens ? p.q_lens[b] : p.Lq;
         qlen = min(max(qlen, 0), p.Lq);
         band_shift = klen - qlen;
         const int q0 = qt * QB, q1 = min(q0 + QB, qlen) - 1;                  // live query rows of this workgroup
-        const int lo = p.window_left < 0 ? 0 : max(0, q0 + band_shift - p.window_left);
-        const int hi = p.window_right < 0 ? klen - 1 : min(klen - 1, q1 + band_shift + p.window_right);
+        int lo, hi;
+        if constexpr (CHK) {
+            const int c0 = (ck.off + q0) / ck.chunk, c1 = (ck.off + max(q1, 0)) / ck.chunk;   // chunks of the first / last live row
+            lo = ck.left < 0 ? 0 : max(0, (c0 - ck.left) * ck.chunk);
+            hi = min(klen, (c1 + 1) * ck.chunk) - 1;
+            whole_lo = ck.left < 0 ? 0 : max(0, (c1 - ck.left) * ck.chunk);
+            whole_hi = min(klen, (c0 + 1) * ck.chunk) - 1;
+        } else {
+            lo = p.window_left < 0 ? 0 : max(0, q0 + band_shift - p.window_left);
+            hi = p.window_right < 0 ? klen - 1 : min(klen - 1, q1 + band_shift + p.window_right);
+        }
         if (q1 < q0 || hi < lo) {
             n_tiles = 0;
         } else {
@@ -157,7 +176,11 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     const int q_row = qt * QB + wave * 32 + li;
     const int q_ld = min(q_row, p.Lq - 1);
     int key_lo = 0, key_hi = klen - 1;                    // WIN: this lane's (query row's) band of keys
-    if constexpr (WIN) {
+    if constexpr (CHK) {
+        const int ci = (ck.off + q_row) / ck.chunk;                           // this row's chunk
+        if (ck.left >= 0) key_lo = max(0, (ci - ck.left) * ck.chunk);
+        key_hi = min(klen, (ci + 1) * ck.chunk) - 1;
+    } else if constexpr (WIN) {
         if (p.window_left >= 0) key_lo = max(0, q_row + band_shift - p.window_left);
         if (p.window_right >= 0) key_hi = min(klen - 1, q_row + band_shift + p.window_right);
     }
@@ -261,7 +284,9 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         }
         // register r of block kb  <->  key kv0 + 32kb + 16(r>>3) + 8h + (r&7)
         const int kv0 = t * KB;
-        if constexpr (WIN) {                          // (key_hi <= klen - 1: the band mask covers the sequence end too)
+        // CHK: a tile inside [whole_lo, whole_hi] needs no mask for a live row (rows at or past qlen are written as zeros
+        // whatever they accumulate): most tiles of a long look-back
+        if (WIN && !(CHK && kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi)) {   // (key_hi <= klen - 1: the band mask covers the sequence end too)
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -515,10 +540,10 @@ static int flash_attn_fwd_d128(const omh_attn_args* args, const float* qk_norm2_
         wk.ws_lse = pl.n_tail ? wk.ws_o + (int64_t)pl.n_tail * pl.splits * QB * D : nullptr;
         if (omh_attn_windowed(a))
             hipLaunchKernelGGL(flash_attn_fwd_d128_kernel<true>, dim3(pl.n_regular), dim3(256), 0, (hipStream_t)stream, a,
-                               q_tiles, wk, BlkList{});
+                               q_tiles, wk, BlkList{}, ChunkRule{});
         else
             hipLaunchKernelGGL(flash_attn_fwd_d128_kernel<false>, dim3(pl.n_regular + pl.n_tail * pl.splits), dim3(256), 0,
-                               (hipStream_t)stream, a, q_tiles, wk, BlkList{});
+                               (hipStream_t)stream, a, q_tiles, wk, BlkList{}, ChunkRule{});
         if (pl.n_tail)
             hipLaunchKernelGGL(attn_split_combine_kernel, dim3((pl.n_tail * QB + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                                a, q_tiles, wk);
@@ -555,6 +580,27 @@ extern "C" int omh_flash_attn_fwd_sparse_d128(const omh_attn_args* args, const o
     AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
     const BlkList bl = {mask->row_cnt, mask->row_idx, mask->heads, mask->q_blocks, mask->k_blocks};
     omh_clear_status();
-    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles, wk, bl);
+    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles, wk, bl, ChunkRule{});
+    return omh_launch_status();
+}
+
+// Additive to ABI v12: the forward under the chunk-causal staircase (include/omh.h).  The short-sequence kernel's CHK
+// instantiation, whatever the shape: no long-sequence stream, no split, no bounded stream.
+extern "C" int omh_flash_attn_fwd_chunk_d128(const omh_attn_args* args, const omh_chunk_causal* rule, omh_stream_t stream) {
+    if (!rule) return OMH_E_BADARG;
+    const int rc0 = attn_fwd_check(args);
+    if (rc0) return rc0;
+    const omh_attn_args& a = *args;
+    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
+    ChunkRule ck;
+    const int rc1 = omh_chunk_rule(rule, a.Lq, a.Lk, &ck);
+    if (rc1) return rc1;
+    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
+    const int q_tiles = (a.Lq + QB - 1) / QB;
+    const int nwg = q_tiles * a.H * a.B;
+    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
+    omh_clear_status();
+    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<true, false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles, wk,
+                       BlkList{}, ck);
     return omh_launch_status();
 }

@@ -218,11 +218,15 @@ struct BwdSplit {
 // BlkList; the forward's flash_attn_fwd_d128_kernel<false, true> documents the cut of the list) and run the body of the
 // full-attention kernel — only the last tile of the list can reach past klen.  The next tile's index is a scalar read a
 // tile before its LDS-DMA is issued.  q_lens may be NULL (= Lq); rows at or past it as under VLEN.  Never split.
-template <bool PRE, bool WIN, bool VLEN = false, bool BLK = false>
+// CHK (with WIN and VLEN; omh_flash_attn_bwd_chunk_d128): the chunk-causal staircase (omh_common.h ChunkRule) in place of
+// the band — row i, chunk I = (off + i) / chunk, sees keys [(I - left) chunk, min(klen, (I + 1) chunk)).  Only the two
+// intervals differ (one division per workgroup, one per row, none in the loop); q_lens may be NULL (= Lq).
+template <bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false>
 __global__ __launch_bounds__(256, 2)
 void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk, const int wl, const int wr,
-                         const int32_t* __restrict__ q_lens, const BlkList bl) {
+                         const int32_t* __restrict__ q_lens, const BlkList bl, const ChunkRule ck) {
     static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
+    static_assert(!CHK || (WIN && VLEN), "the staircase runs on the varlen band kernels' masking");
     static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][K tile | V tile]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
@@ -231,7 +235,9 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     // (400 KB each at S = 1560) is fetched into one 4 MiB L2 instead of eight
     const int wid = worker ? wk.n_regular + ((int)blockIdx.x - wk.n_regular) / wk.splits : xcd_remap((int)blockIdx.x, wk.n_regular);
     const int split = worker ? ((int)blockIdx.x - wk.n_regular) % wk.splits : 0;
-    const int qb = wid % q_blocks, bh = wid / q_blocks;
+    // (CHK: a query block's key loop grows with its position — a head's blocks are handed out last block first, so the
+    // long ones start first and the launch ends on short ones)
+    const int qb = CHK ? q_blocks - 1 - wid % q_blocks : wid % q_blocks, bh = wid / q_blocks;
     const int b = bh / p.H, head = bh % p.H;
     int klen = p.k_lens ? p.k_lens[b] : p.Lk;
     klen = min(max(klen, 0), p.Lk);
@@ -249,23 +255,36 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     const uint16_t* V = (const uint16_t*)p.v + (int64_t)b * p.k_bs + head * D;
     const int q_row = qb * 128 + wave * 32 + li;
     int qlen = p.Lq;
-    if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
+    if constexpr (CHK) { if (q_lens) qlen = min(max(q_lens[b], 0), p.Lq); }
+    else if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
     if constexpr (BLK) { if (q_lens) qlen = min(max(q_lens[b], 0), p.Lq); }
     const bool q_ok = q_row < qlen;
     int key_lo = 0, key_hi = klen - 1;                               // WIN: this lane's (query row's) band of keys
     if constexpr (WIN) {
         const int shift = klen - qlen;
         const int q0 = qb * 128, q1 = min(q0 + 128, qlen) - 1;      // live query rows of this workgroup
-        const int lo = wl < 0 ? 0 : max(0, q0 + shift - wl);
-        const int hi = wr < 0 ? klen - 1 : min(klen - 1, q1 + shift + wr);
+        int lo, hi;
+        if constexpr (CHK) {
+            lo = ck.left < 0 ? 0 : max(0, ((ck.off + q0) / ck.chunk - ck.left) * ck.chunk);
+            hi = min(klen, ((ck.off + max(q1, 0)) / ck.chunk + 1) * ck.chunk) - 1;
+        } else {
+            lo = wl < 0 ? 0 : max(0, q0 + shift - wl);
+            hi = wr < 0 ? klen - 1 : min(klen - 1, q1 + shift + wr);
+        }
         if (hi < lo || (VLEN && q1 < q0)) {
             n_tiles = 0;
         } else {
             t_first = lo / TB;
             n_tiles = hi / TB - t_first + 1;
         }
-        if (wl >= 0) key_lo = max(0, q_row + shift - wl);
-        if (wr >= 0) key_hi = min(klen - 1, q_row + shift + wr);
+        if constexpr (CHK) {
+            const int ci = (ck.off + q_row) / ck.chunk;              // this row's chunk
+            if (ck.left >= 0) key_lo = max(0, (ci - ck.left) * ck.chunk);
+            key_hi = min(klen, (ci + 1) * ck.chunk) - 1;
+        } else {
+            if (wl >= 0) key_lo = max(0, q_row + shift - wl);
+            if (wr >= 0) key_hi = min(klen - 1, q_row + shift + wr);
+        }
     }
     const int32_t* __restrict__ bl_idx = nullptr;                    // BLK: this workgroup's list
     if constexpr (BLK) {
@@ -510,11 +529,15 @@ __device__ __forceinline__ void dkdv_store(const omh_attn_bwd_args& p, const Bwd
 // blocks in that block's COLUMN list, cut at the first block at or past qlen (the last block's second tile dropped when
 // it holds no live row), with the unmasked body: inside a kept block every live row sees every live key.  A key block
 // at or past klen runs no tile.  Q / dO / lse / delta of rows past qlen as under VLEN.
-template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false, bool BLK = false>
+// CHK (see attn_bwd2_dq_kernel): key j of chunk J = j / chunk is seen by the rows i with J chunk <= off + i < (J + left + 1)
+// chunk (no upper end for left < 0), cut at qlen; the workgroup walks the query tiles from its first live key's lower end
+// to its last live key's upper end.  One division per workgroup and one per key, none in the loop.
+template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false>
 __global__ __launch_bounds__(64 * WAVES, 1)
 void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk, const int wl, const int wr,
-                           const int32_t* __restrict__ q_lens, const BlkList bl) {
+                           const int32_t* __restrict__ q_lens, const BlkList bl, const ChunkRule ck) {
     static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
+    static_assert(!CHK || (WIN && VLEN), "the staircase runs on the varlen band kernels' masking");
     static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
     constexpr int THREADS = 64 * WAVES;
     static_assert(WAVES * KPW == 4, "a workgroup covers 128 keys");
@@ -537,7 +560,8 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     }
     int q_lo = 0, q_hi = 0;                                          // WIN: this lane's (key's) range of queries
     int qlen = p.Lq;
-    if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
+    if constexpr (CHK) { if (q_lens) qlen = min(max(q_lens[b], 0), p.Lq); }
+    else if constexpr (VLEN) qlen = min(max(q_lens[b], 0), p.Lq);
     if constexpr (BLK) { if (q_lens) qlen = min(max(q_lens[b], 0), p.Lq); }
     const int32_t* __restrict__ bl_idx = nullptr;                    // BLK: this workgroup's list
     if constexpr (BLK) {
@@ -565,8 +589,14 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         static_assert(KPW == 1, "one key per lane");
         const int shift = klen - qlen;
         const int k0 = kb * 128, k1 = min(k0 + 128, klen) - 1;      // live keys of this workgroup
-        const int lo = wr < 0 ? 0 : max(0, k0 - shift - wr);
-        const int hi = wl < 0 ? qlen - 1 : min(qlen - 1, k1 - shift + wl);
+        int lo, hi;
+        if constexpr (CHK) {
+            lo = max(0, (k0 / ck.chunk) * ck.chunk - ck.off);
+            hi = ck.left < 0 ? qlen - 1 : min(qlen - 1, (max(k1, 0) / ck.chunk + ck.left + 1) * ck.chunk - ck.off - 1);
+        } else {
+            lo = wr < 0 ? 0 : max(0, k0 - shift - wr);
+            hi = wl < 0 ? qlen - 1 : min(qlen - 1, k1 - shift + wl);
+        }
         if (k1 < k0 || hi < lo) {
             n_tiles = 0;
         } else {
@@ -574,8 +604,14 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
             n_tiles = hi / TB - t_first + 1;
         }
         const int key = kb * 128 + wave * 32 + li;
-        q_lo = wr < 0 ? -(1 << 30) : key - shift - wr;
-        q_hi = wl < 0 ? (1 << 30) : key - shift + wl;
+        if constexpr (CHK) {
+            const int cj = key / ck.chunk;                           // this key's chunk
+            q_lo = cj * ck.chunk - ck.off;
+            q_hi = ck.left < 0 ? (1 << 30) : (cj + ck.left + 1) * ck.chunk - ck.off - 1;
+        } else {
+            q_lo = wr < 0 ? -(1 << 30) : key - shift - wr;
+            q_hi = wl < 0 ? (1 << 30) : key - shift + wl;
+        }
         if constexpr (VLEN) q_hi = min(q_hi, qlen - 1);
     }
     const int q_rows = (VLEN || BLK) ? max(qlen, 1) : p.Lq;                   // rows the Q / dO / lse / delta reads may touch
@@ -1096,8 +1132,8 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (bwd2_dq_stream()) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
             else hipLaunchKernelGGL(attn_bwd2_dq_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_DQ_W64_LDS, s, a, q_blocks, wq);
-        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr, BlkList{});
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr, BlkList{});
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr, BlkList{}, ChunkRule{});
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false>), grid, dim3(256), LDS_DQ, s, a, q_blocks, wq, -1, -1, nullptr, BlkList{}, ChunkRule{});
         if (wq.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<1>, dim3((wq.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, q_blocks, wq);
     }
@@ -1107,8 +1143,8 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
         if (!(e && e[0] == '0')) {
             if (a.q_prescaled) hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<true>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
             else hipLaunchKernelGGL(attn_bwd2_dkdv_w64_kernel<false>, grid, dim3(256), OMH_ATTN_BWD_W64_LDS, s, a, k_blocks, wkv);
-        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr, BlkList{});
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr, BlkList{});
+        } else if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr, BlkList{}, ChunkRule{});
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false>), grid, dim3(256), LDS_KV, s, a, k_blocks, wkv, -1, -1, nullptr, BlkList{}, ChunkRule{});
         if (wkv.n_tail)
             hipLaunchKernelGGL(attn_bwd2_sum_kernel<2>, dim3((wkv.n_tail * 128 + 3) / 4), dim3(256), 0, s, a, k_blocks, wkv);
     }
@@ -1147,13 +1183,13 @@ static int launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, con
     const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
     if (a.phase == 0 || a.phase == 2) {
         const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{});
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{});
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
     }
     if (a.phase == 0 || a.phase == 3) {
         const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{});
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{});
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
     }
     return 0;
 }
@@ -1191,14 +1227,53 @@ int omh_launch_attn_bwd2_sparse(const omh_attn_bwd_args& a, const int32_t* q_len
     if (a.phase == 0 || a.phase == 2) {
         const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
         const BlkList bl = {m.row_cnt, m.row_idx, m.heads, m.q_blocks, m.k_blocks};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl);
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl);
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
     }
     if (a.phase == 0 || a.phase == 3) {
         const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
         const BlkList bl = {m.col_cnt, m.col_idx, m.heads, m.k_blocks, m.q_blocks};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl);
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl);
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
+    }
+    return 0;
+}
+
+// called by omh_flash_attn_bwd_chunk_d128 (attention_bwd.hip) with validated arguments, o32 set and a normalised rule: the
+// phases of omh_launch_attn_bwd2 on the CHK instantiations of the HIP kernels; never split.
+int omh_launch_attn_bwd2_chunk(const omh_attn_bwd_args& a, const int32_t* q_lens, const ChunkRule& ck, hipStream_t s) {
+    if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
+        ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
+        return OMH_E_SHAPE;
+    if (((uintptr_t)a.o32 & 15) || (a.o_rs & 3) || (a.o_bs & 3)) return OMH_E_ALIGN;
+    if (a.phase < 0 || a.phase > 3) return OMH_E_BADARG;
+    const int64_t pairs = (int64_t)a.B * a.Lq * a.H;
+    if (pairs >= 0x7fffffffLL) return OMH_E_SHAPE;
+    constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        attr_set = true;
+    }
+    if (a.phase == 0 || a.phase == 1) {
+        const dim3 grid((unsigned)((pairs + 15) / 16));
+        if (q_lens) hipLaunchKernelGGL(attn_bwd2_delta_kernel<true>, grid, dim3(256), 0, s, a, q_lens);
+        else hipLaunchKernelGGL(attn_bwd2_delta_kernel<false>, grid, dim3(256), 0, s, a, nullptr);
+        if (a.phase == 1) return 0;
+    }
+    const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
+    if (a.phase == 0 || a.phase == 2) {
+        const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, BlkList{}, ck);
+        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, BlkList{}, ck);
+    }
+    if (a.phase == 0 || a.phase == 3) {
+        const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
+        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, BlkList{}, ck);
+        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, BlkList{}, ck);
     }
     return 0;
 }

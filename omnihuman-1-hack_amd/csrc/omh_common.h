@@ -159,6 +159,27 @@ static inline int omh_block_mask_check(const omh_block_mask* m, int H, int Lq, i
 // band set", not as the one-key band it is elsewhere; both sides < 0 is the unbounded band; anything else is refused.
 static inline bool omh_mask_window_unset(int wl, int wr) { return (wl < 0 && wr < 0) || (wl == 0 && wr == 0); }
 
+// ---- the chunk-causal staircase (include/omh.h omh_chunk_causal; attention.hip, attention_bwd2.hip) ----
+// What a CHK kernel gets: query i sits at position off + i; it sees key j iff  j / chunk <= (off + i) / chunk  and
+// (left < 0 or j / chunk >= (off + i) / chunk - left).  Normalised by omh_chunk_rule so that every product of a chunk
+// index with `chunk` the kernels form stays below 2^31.
+struct ChunkRule {
+    int chunk, left, off;
+};
+// 0 or the error code.  A chunk at least as long as both axes is clamped to that length (every position is then in chunk
+// 0 either way) and a look-back past the first chunk to one that reaches it: the same mask, small numbers.
+static inline int omh_chunk_rule(const omh_chunk_causal* c, int Lq, int Lk, ChunkRule* out) {
+    if (!c || c->chunk <= 0 || c->q_offset < 0 || c->reserved != 0) return OMH_E_BADARG;
+    const int64_t span = (int64_t)c->q_offset + Lq;                  // positions of the query axis end here
+    if (span + Lk >= (1LL << 28)) return OMH_E_SHAPE;
+    const int64_t cap = span > Lk ? span : Lk;
+    out->chunk = c->chunk > cap ? (int)cap : c->chunk;
+    const int64_t reach = span / out->chunk + 1;                     // chunks a look-back can span at most
+    out->left = c->left_chunks < 0 ? -1 : (c->left_chunks > reach ? (int)reach : c->left_chunks);
+    out->off = c->q_offset;
+    return 0;
+}
+
 // ---- split of a launch's last, partly filled round of workgroups (host side; attention.hip, attention_bwd2.hip) ----
 // A launch of `nwg` equal workgroups on `slots` resident slots takes ceil(nwg / slots) rounds; its last round holds
 // r = nwg mod slots workgroups.  Those r are split into `splits` workers each over their inner loop (`loop_tiles` tiles,

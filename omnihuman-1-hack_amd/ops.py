@@ -186,9 +186,25 @@ def _block_mask(block_mask, H, Lq, Lk, window=(-1, -1)):
     return bm.to(torch.device("cuda", torch.cuda.current_device()))
 
 
+def _chunk_causal(chunk_causal, window=(-1, -1), block_mask=None):
+    """``chunk_causal`` (None or (chunk, left_chunks, q_offset)) as an omh_chunk_causal: ValueError for a band or a block
+    mask beside it (a mask is not combined with anything), a chunk below 1 or a negative offset."""
+    if chunk_causal is None:
+        return None
+    if window[0] >= 0 or window[1] >= 0:
+        raise ValueError("chunk_causal excludes causal / a bounded window (it is not an intersection)")
+    if block_mask is not None:
+        raise ValueError("chunk_causal excludes a block mask (it is not an intersection)")
+    chunk, left, off = (int(x) for x in chunk_causal)
+    if chunk <= 0 or off < 0:
+        raise ValueError(f"chunk_causal = ({chunk}, {left}, {off}): chunk >= 1 and q_offset >= 0 expected")
+    big = 2 ** 31 - 1
+    return _lib.ChunkCausalArgs(min(chunk, big), -1 if left < 0 else min(left, big), min(off, big), 0)
+
+
 def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale,
                    lse=None, q_prescaled=0, o32=None, flags=0, q_lens=None, window=(-1, -1), qk_norm2_max=None,
-                   block_mask=None):
+                   block_mask=None, chunk_causal=None):
     """``flags``: ATTN_SHORT_KERNEL | ATTN_ALLOW_SPLIT (include/omh.h, ABI v8): the training step pins the short-sequence
     kernel (forward and re-run take the same one) and lets it split its last round of workgroups over the keys.
     ``q_lens`` (ABI v10): int32 [B] device pointer; output rows past a sample's query length are written as zero.
@@ -197,13 +213,20 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
     ``qk_norm2_max``: float [B, H, 2] device pointer from ``rmsnorm_rope_bf16_pair_bound_raw`` for these q and k: the
     long-sequence stream then runs without a running max where the bound allows (omh_flash_attn_fwd_d128_bounded).
     ``block_mask``: a ``sparse.BlockMask`` / bool block tensor (omh_flash_attn_fwd_sparse_d128: the short-sequence kernel
-    over each query block's list of key blocks, never split, never the bounded stream); ValueError beside a band."""
+    over each query block's list of key blocks, never split, never the bounded stream); ValueError beside a band.
+    ``chunk_causal``: (chunk, left_chunks, q_offset) — the staircase of omh_flash_attn_fwd_chunk_d128 (include/omh.h): query
+    i sees key j iff j // chunk <= (q_offset + i) // chunk, and >= that - left_chunks when left_chunks >= 0; the
+    short-sequence kernel, never split; ValueError beside a band or a block mask."""
+    cc = _chunk_causal(chunk_causal, window, block_mask)
     bm = _block_mask(block_mask, H, Lq, Lk, window)
     a = AttnArgs(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale, lse,
                  int(q_prescaled), None, 0, o32, int(flags), q_lens, int(window[0]), int(window[1]))
     if bm is not None:
         m = bm.c_struct()
         check(lib.omh_flash_attn_fwd_sparse_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_sparse_d128")
+        return
+    if cc is not None:
+        check(lib.omh_flash_attn_fwd_chunk_d128(C.byref(a), C.byref(cc), _stream()), "omh_flash_attn_fwd_chunk_d128")
         return
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
     ws = None
@@ -218,13 +241,15 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
                scale: Optional[float] = None, out: Optional[torch.Tensor] = None, q_lens: Optional[torch.Tensor] = None,
-               window=(-1, -1), block_mask=None, lse: Optional[torch.Tensor] = None):
+               window=(-1, -1), block_mask=None, lse: Optional[torch.Tensor] = None, chunk_causal=None):
     """q [B,Lq,H,128], k [B,Lk,H,128] bf16; vt [B,H*128,ldv] bf16 (V transposed,
     ldv >= roundup(Lk,64)); k_lens / q_lens int32 [B] or None.  Returns [B,Lq,H,128] bf16 (rows past q_lens: zero).
     ``window`` = (left, right): flash-attn's bottom-right aligned band (causal = (-1, 0)); (-1, -1): full attention.
     ``block_mask``: a ``sparse.BlockMask`` or a bool tensor [nQb, nKb] / [H, nQb, nKb] over 128 x 128 blocks — query i
     sees key j iff its block is kept (and j < k_lens[b], i < q_lens[b]); rows that see no key are zero.  ValueError
-    together with a bounded ``window``.  ``lse``: optional fp32 [B, H, Lq] the log-sum-exp is written to."""
+    together with a bounded ``window``.  ``lse``: optional fp32 [B, H, Lq] the log-sum-exp is written to.
+    ``chunk_causal`` = (chunk, left_chunks, q_offset): the chunk-causal staircase (see ``flash_attn_raw``); rows that see
+    no key are zero (lse = -inf).  ValueError together with a bounded ``window`` or a ``block_mask``."""
     _dev(q, k, vt, k_lens, out, q_lens, lse)
     if q_lens is not None:
         assert q_lens.dtype == torch.int32 and q_lens.numel() == q.shape[0]
@@ -240,12 +265,12 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
     flash_attn_raw(_p(q), _p(k), _p(vt), _p(out), _p(k_lens), B, H, Lq, Lk, q.stride(0), q.stride(1), k.stride(0),
                    k.stride(1), vt.stride(0), out.stride(0), out.stride(1), vt.stride(1),
                    float(scale if scale is not None else D ** -0.5), q_lens=_p(q_lens), window=window,
-                   block_mask=block_mask, lse=_p(lse))
+                   block_mask=block_mask, lse=_p(lse), chunk_causal=chunk_causal)
     return out
 
 
 def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_prescaled=False, out=None, o32=None,
-                   phase=0, delta=None, split=True, window=(-1, -1), q_lens=None, block_mask=None):
+                   phase=0, delta=None, split=True, window=(-1, -1), q_lens=None, block_mask=None, chunk_causal=None):
     """Fused attention backward (include/omh.h).  q, dout: bf16 [B*Lq, H*128]; k, v: bf16 [B*Lk, H*128] (row stride
     free); lse fp32 [B, H, Lq] from ``flash_attn_raw(..., lse=)``; k_lens int32 [B] or None.
     Returns fp32 dq [B*Lq, H*128], dk, dv [B*Lk, H*128] — or, with ``out=(dq, dk, dv)`` bf16 2-D tensors (row stride
@@ -262,8 +287,13 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     included; requires ``o32``): rows past a sample's query length get dq = 0, give nothing to dk / dv, and their dout /
     q / lse / o32 are not read (they may hold NaN).
     ``block_mask``: the forward's block mask (omh_flash_attn_bwd_sparse_d128; requires ``o32``, any ``q_lens``; ValueError
-    beside a bounded ``window``): keys no live query sees get dk = dv = 0, live rows that see no key dq = 0."""
+    beside a bounded ``window``): keys no live query sees get dk = dv = 0, live rows that see no key dq = 0.
+    ``chunk_causal``: the forward's (chunk, left_chunks, q_offset) (omh_flash_attn_bwd_chunk_d128; requires ``o32``, any
+    ``q_lens``; ValueError beside a bounded ``window`` or a block mask): zero gradients as under a block mask."""
     _dev(q, k, v, dout, lse, k_lens, o32, q_lens)
+    cc = _chunk_causal(chunk_causal, window, block_mask)
+    if cc is not None:
+        assert o32 is not None, "flash_attn_bwd: chunk_causal needs the forward's fp32 output (o32=)"
     bm = _block_mask(block_mask, H, Lq, Lk, window)
     if bm is not None:
         assert o32 is not None, "flash_attn_bwd: a block mask needs the forward's fp32 output (o32=)"
@@ -320,6 +350,10 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
         check(lib.omh_flash_attn_bwd_sparse_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
               "omh_flash_attn_bwd_sparse_d128")
         return dq, dk, dv
+    if cc is not None:
+        check(lib.omh_flash_attn_bwd_chunk_d128(C.byref(a), _p(q_lens), C.byref(cc), _stream()),
+              "omh_flash_attn_bwd_chunk_d128")
+        return dq, dk, dv
     if q_lens is not None:
         check(lib.omh_flash_attn_bwd_varlen_d128(C.byref(a), _p(q_lens), int(window[0]), int(window[1]), _stream()),
               "omh_flash_attn_bwd_varlen_d128")
@@ -341,7 +375,7 @@ class _FlashAttnFunc(torch.autograd.Function):
     omh_flash_attn_bwd_* call backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, k_lens, q_lens, scale, window, block_mask=None):
+    def forward(ctx, q, k, v, k_lens, q_lens, scale, window, block_mask=None, chunk_causal=None):
         _dev(q, k, v, k_lens, q_lens)
         B, Lq, H, D = q.shape
         Lk = k.shape[1]
@@ -362,9 +396,9 @@ class _FlashAttnFunc(torch.autograd.Function):
         # pinned to the short-sequence kernel, as the training step pins it (never split: this flag alone)
         flash_attn_raw(_p(q), _p(k), _p(vt), _p(o), _p(k_lens), B, H, Lq, Lk, Lq * d, d, Lk * d, d, d * Lp, Lq * d, d, Lp,
                        scale, lse=_p(lse), o32=_p(o32), flags=ATTN_SHORT_KERNEL, q_lens=_p(q_lens), window=window,
-                       block_mask=block_mask)
+                       block_mask=block_mask, chunk_causal=chunk_causal)
         ctx.save_for_backward(q, k, v, o, lse, o32, k_lens, q_lens)
-        ctx.scale, ctx.window, ctx.block_mask = scale, window, block_mask
+        ctx.scale, ctx.window, ctx.block_mask, ctx.chunk_causal = scale, window, block_mask, chunk_causal
         return o
 
     @staticmethod
@@ -378,15 +412,15 @@ class _FlashAttnFunc(torch.autograd.Function):
                torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device))
         flash_attn_bwd(q.view(B * Lq, d), k.view(B * Lk, d), v.view(B * Lk, d), o.view(B * Lq, d), do.view(B * Lq, d), lse,
                        k_lens, B, H, Lq, Lk, scale=ctx.scale, out=out, o32=o32, window=ctx.window, q_lens=q_lens,
-                       block_mask=ctx.block_mask)
+                       block_mask=ctx.block_mask, chunk_causal=ctx.chunk_causal)
         need = ctx.needs_input_grad
         return (out[0].view(B, Lq, H, D) if need[0] else None, out[1].view(B, Lk, H, D) if need[1] else None,
-                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None, None)
+                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None, None, None)
 
 
 def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
                     q_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None, window=(-1, -1),
-                    block_mask=None):
+                    block_mask=None, chunk_causal=None):
     """Differentiable attention (a ``torch.autograd.Function``): q [B,Lq,H,128], k, v [B,Lk,H,128] bf16 (V row-major: the
     padded V^T the kernel reads is built here, by the transpose kernel); k_lens / q_lens int32 [B] or None; ``window`` =
     (left, right) as in ``flash_attn``.  Returns [B,Lq,H,128] bf16 — the bits of ``flash_attn`` on the same inputs
@@ -394,12 +428,17 @@ def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: O
     lens; the backward is one ``flash_attn_bwd`` call with bf16 outputs (omh_flash_attn_bwd_varlen_d128 with q_lens, the
     band entry with a bounded window, omh_flash_attn_bwd_d128 otherwise: no atomics, repeatable bit for bit) and
     returns gradients only for the inputs that need them.  ``block_mask`` as in ``flash_attn`` (forward and backward on
-    the block-list kernels, omh_flash_attn_*_sparse_d128; ValueError beside a bounded ``window``)."""
+    the block-list kernels, omh_flash_attn_*_sparse_d128; ValueError beside a bounded ``window``).  ``chunk_causal`` =
+    (chunk, left_chunks, q_offset) as in ``flash_attn`` (omh_flash_attn_*_chunk_d128, honouring q_lens / k_lens; ValueError
+    beside a bounded ``window`` or a ``block_mask``)."""
     window = (int(window[0]) if window[0] >= 0 else -1, int(window[1]) if window[1] >= 0 else -1)
+    if chunk_causal is not None:
+        _chunk_causal(chunk_causal, window, block_mask)
+        chunk_causal = tuple(int(x) for x in chunk_causal)
     if block_mask is not None:
         block_mask = _block_mask(block_mask, q.shape[2], q.shape[1], k.shape[1], window)
     return _FlashAttnFunc.apply(q, k, v, k_lens, q_lens, float(scale if scale is not None else 128 ** -0.5), window,
-                                block_mask)
+                                block_mask, chunk_causal)
 
 
 def layernorm_modulate_raw(x, y, rows, dim, eps, mul_const, mul0, mul1, mul1_stride, add0, add1, add1_stride,

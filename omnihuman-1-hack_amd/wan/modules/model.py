@@ -173,7 +173,10 @@ def _dev_ints(values, dtype, device):
 class _FwdCtx:
     """Per-forward shared state handed to every block."""
     __slots__ = ("B", "S", "dim", "e0", "seq_lens32", "ctx_lens32", "grid32", "rope_cos", "rope_sin", "ctx",
-                 "Lc", "n_img", "seq_lens_host", "ctx_lens_host", "kv", "split_k")
+                 "Lc", "n_img", "seq_lens_host", "ctx_lens_host", "kv", "split_k",
+                 # chunk: (tokens per chunk, left_chunks, 0) under WanModel.set_causal_chunks, else None / unset;
+                 # cache, cache_layer, cache_lo: WanModel.forward_chunk (a causal.KVCache, the running block, first key)
+                 "chunk", "cache", "cache_layer", "cache_lo")
 
 
 class ContextState:
@@ -290,9 +293,15 @@ class WanSelfAttention(nn.Module):
 
     def _attend(self, h, fc: "_FwdCtx"):
         """h bf16 [B*S, dim] -> attention output bf16 [B*S, dim] (before o-proj)."""
+        if getattr(fc, "cache", None) is not None:
+            return self._attend_cached(h, fc)
         B, S, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
         R = B * S
         bmask = self._mask_for(S)
+        chunk = getattr(fc, "chunk", None)                 # WanModel.set_causal_chunks: the staircase kernels
+        if chunk is not None and (bmask is not None or self._block_policy is not None or self.window_size[0] >= 0
+                                  or self.window_size[1] >= 0):
+            raise ValueError("causal chunks exclude a block mask, a block policy and a bounded window_size")
         # q|k projection kept in bf16 (fp32 accumulate): the normalisation statistics are taken in fp32 from
         # it; measured effect on the 30-layer output < 1e-3 relative RMS, and it halves this step's traffic
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
@@ -328,7 +337,8 @@ class WanSelfAttention(nn.Module):
         window = tuple(self.window_size)
         nmax = None
         # (a block mask runs the short-sequence kernel over its lists: no long-sequence stream, so no bound either)
-        if bmask is None and self._block_policy is None and D == 128 and d <= 5120 and \
+        # (nor does the staircase: the short-sequence kernel too)
+        if chunk is None and bmask is None and self._block_policy is None and D == 128 and d <= 5120 and \
                 ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
             nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
         self.last_qk_norm2_max = nmax                                    # (read by tools/attn_bound_values.py)
@@ -351,7 +361,41 @@ class WanSelfAttention(nn.Module):
         # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
                            d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1, window=window,
-                           qk_norm2_max=ptr(nmax) if nmax is not None else None, block_mask=bmask)
+                           qk_norm2_max=ptr(nmax) if nmax is not None else None, block_mask=bmask, chunk_causal=chunk)
+        return o
+
+    def _attend_cached(self, h, fc: "_FwdCtx"):
+        """``_attend`` for WanModel.forward_chunk: h holds the rows of ONE chunk per sample.  q, k, v are projected for
+        these rows only; k (normalised, rotated) lands in rows [length, length + C) of this layer's cache and V^T in the
+        same columns, straight from the V^T product (ldc = the cache pitch); plain attention then runs with Lq = C over the
+        keys [lo, length + C) of the cache — a pointer offset, no copy.  The launches of ``_attend`` at seq_len = C
+        otherwise, so on an empty cache the result has its bits."""
+        B, C, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
+        cache, lo = fc.cache, fc.cache_lo
+        kc, vtc = cache.k[fc.cache_layer], cache.vt[fc.cache_layer]
+        L0, cap, pitch = cache.length, cache.cap, cache.pitch
+        R = B * C
+        qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
+        wqk, bqk = self._w_qk()
+        ops.gemm_raw(ptr(h), ptr(wqk), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(bqk), bias_mode=BIAS_N)
+        q = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
+        wq, wk = self._norm_w("norm_q"), self._norm_w("norm_k")
+        for b in range(B):                                 # one launch per sample: its k rows sit at their own place in the cache
+            ops.rmsnorm_rope_bf16_pair_raw(ptr(qk, b * C * 2 * d), 2 * d, d, ptr(q, b * C * d), ptr(kc, (b * cap + L0) * d), C, d,
+                                           ptr(wq) if wq is not None else None, ptr(wk) if wk is not None else None,
+                                           self.eps, int(self.qk_norm), ptr(fc.rope_cos), ptr(fc.rope_sin),
+                                           fc.rope_cos.shape[0], D, ptr(fc.grid32, 3 * b), C,
+                                           out_scale0=D ** -0.5 * 1.4426950408889634, out_scale1=1.0)
+        del qk
+        wv, bv = self._w("v")
+        ops.gemm_raw(ptr(wv), ptr(h), ptr(vtc, L0), d, C, d, d, d, pitch, EPI_BF16, bias=ptr(bv), bias_mode=BIAS_M, batch=B,
+                     strideA=0, strideB=C * d, strideC=d * pitch)
+        o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
+        Lk = L0 - lo + C
+        # pinned to the short-sequence kernel: its V^T reads end at most 63 columns past the last key (the cache keeps
+        # that much slack behind its last row); a chunk of queries does not reach the long-sequence dispatch at 12 heads
+        ops.flash_attn_raw(ptr(q), ptr(kc, lo * d), ptr(vtc, lo), ptr(o), None, B, N, C, Lk, C * d, d, cap * d, d,
+                           d * pitch, C * d, d, pitch, D ** -0.5, q_prescaled=1, flags=ops.ATTN_SHORT_KERNEL)
         return o
 
     def forward(self, x, seq_lens, grid_sizes, freqs, _fc: Optional["_FwdCtx"] = None):
@@ -713,6 +757,7 @@ class WanModel(nn.Module):
             self.img_emb = MLPProj(1280, dim)
         self._packed = _Packed()
         self._rope_dev = None
+        self._causal_chunks = None                  # set_causal_chunks: (frames per chunk, left_chunks) or None
         self.init_weights()
 
     # ------------------------------------------------------------------ loading
@@ -819,6 +864,144 @@ class WanModel(nn.Module):
             if policy is None:
                 self.blocks[i].self_attn.last_block_mask = None
 
+    # ------------------------------------------------------------------ causal chunks
+    def set_causal_chunks(self, frames_per_chunk, left_chunks=-1):
+        """Run every SELF-attention of ``forward`` under the chunk-causal staircase (the rule: include/omh.h,
+        omh_chunk_causal): with C = frames_per_chunk * (h / p_h) * (w / p_w) tokens per chunk, token i sees token j iff
+        j // C <= i // C and, for ``left_chunks`` >= 0, j // C >= i // C - left_chunks (< 0: every earlier chunk).
+        ``frames_per_chunk`` = None clears it.  Honoured by ``forward`` (inference, training, the ``use_checkpoint``
+        re-run, input gradients, LoRA) and ``forward_cfg_pair``; ``forward_chunk`` takes its chunk length and look-back
+        from it.  Cross-attention is never masked.  A run-time attribute like the block mask: in neither ``config`` nor
+        the ``state_dict``.  ValueError for a model with a bounded ``window_size`` and for a layer that has a block mask
+        or a block policy (here and again at ``forward``), and at ``forward`` for a batch whose clips do not share h, w
+        (one C serves the call; clips of different frame counts padded to ``seq_len`` are fine)."""
+        if frames_per_chunk is None:
+            self._causal_chunks = None
+            return
+        fpc, left = int(frames_per_chunk), int(left_chunks)
+        if fpc < 1:
+            raise ValueError(f"set_causal_chunks: frames_per_chunk = {frames_per_chunk}, at least 1 expected")
+        self._causal_check("set_causal_chunks")
+        self._causal_chunks = (fpc, -1 if left < 0 else left)
+
+    def _causal_check(self, who):
+        if self.window_size[0] >= 0 or self.window_size[1] >= 0:
+            raise ValueError(f"{who}: the model has window_size={tuple(self.window_size)}; causal chunks exclude a "
+                             "bounded window (it is not an intersection)")
+        for i, blk in enumerate(self.blocks):
+            if blk.self_attn._block_mask is not None or blk.self_attn._block_policy is not None:
+                raise ValueError(f"{who}: block {i} has a block mask / block policy; causal chunks exclude it "
+                                 "(clear it first)")
+
+    def _causal_rule(self, grids):
+        """(tokens per chunk, left_chunks, 0) for a forward over clips with these (f, h, w) grids, or None."""
+        cc = getattr(self, "_causal_chunks", None)
+        if cc is None:
+            return None
+        self._causal_check("forward under set_causal_chunks")
+        hw = {(g[1], g[2]) for g in grids}
+        if len(hw) != 1:
+            raise ValueError(f"forward under set_causal_chunks: the clips of a batch must share h, w (one chunk length "
+                             f"serves the call), got {sorted(hw)}")
+        h, w = next(iter(hw))
+        return (cc[0] * h * w, cc[1], 0)
+
+    def _rope_shifted(self, device, frame_offset):
+        """The cos / sin tables with the FRAME columns moved up by ``frame_offset`` rows: frame f of a chunk then rotates
+        like frame frame_offset + f of the clip; the h / w columns stay.  Cached per offset."""
+        cos, sin = self._rope(device)
+        if frame_offset == 0:
+            return cos, sin
+        key = (str(device), int(frame_offset))
+        tabs = getattr(self, "_rope_shift_cache", None)
+        if tabs is None or tabs[0] is not cos:
+            tabs = self._rope_shift_cache = (cos, {})
+        hit = tabs[1].get(key)
+        if hit is None:
+            if len(tabs[1]) > 256:
+                tabs[1].clear()
+            d = self.dim // self.num_heads
+            nf = (d - 4 * (d // 6)) // 2                                     # pair-columns of the frame axis
+            c2, s2 = cos.clone(), sin.clone()
+            n = cos.shape[0] - frame_offset
+            c2[:n, :nf] = cos[frame_offset:, :nf]
+            s2[:n, :nf] = sin[frame_offset:, :nf]
+            hit = tabs[1][key] = (c2, s2)
+        return hit
+
+    def forward_chunk(self, x, t, context, cache, frame_offset=None, commit=True, clip_fea=None, y=None):
+        """One chunk of a clip against the keys and values kept from the chunks before it (the rollout of the
+        frame-causal model).  ``x``: the latents [C_in, f, H, W] of ONE chunk per sample, all of one shape (the last chunk
+        of a clip may have fewer frames); ``cache``: a ``causal.KVCache`` of this model and batch.  Each block projects
+        q, k, v for the chunk's rows only, rotates q and k with the frame axis starting at ``frame_offset`` (default:
+        ``cache.length`` / tokens per frame), writes k and V^T at rows / columns [length, length + C) of its cache and
+        attends over the keys [lo, length + C): lo = 0, or the first token of the look-back when ``set_causal_chunks``
+        set ``left_chunks`` >= 0 (then ``cache.length`` must sit on a chunk boundary and the chunk may not exceed
+        ``frames_per_chunk``).  ``commit=True`` advances ``cache.length`` by C once, after the last block;
+        ``commit=False`` leaves the cache as it was (the rows behind ``length`` are scratch) — a denoising step of the
+        current chunk.  Cross-attention, FFN and head as in ``forward``.  Tokens per chunk must be a multiple of 8 (the
+        16-byte stores into the cache and the look-back offset): ValueError otherwise, and when the chunk does not fit.
+        Inference only: RuntimeError with grad enabled and parameters or inputs that require it.
+        Returns the list of fp32 [C_out, f, H, W]."""
+        device = self.patch_embedding.weight.device
+        if device.type != "cuda":
+            raise ops.OmhError("WanModel.forward_chunk runs on the MI355X only (no CPU fallback): move the model "
+                               "to a GPU device")
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                        or self._input_requires_grad(x, t, context, clip_fea, y, None)):
+            raise RuntimeError("forward_chunk is an inference path (no gradient flows through the cache): call it "
+                               "under torch.no_grad() with inputs that do not require grad")
+        with torch.no_grad():
+            return self._forward_chunk(list(x), t, context, cache, frame_offset, commit, clip_fea, y)
+
+    def _forward_chunk(self, x, t, context, cache, frame_offset, commit, clip_fea, y):
+        if len({tuple(u.shape) for u in x}) != 1:
+            raise ValueError("forward_chunk: the chunks of a batch must have one shape")
+        if cache.model_id != id(self) or cache.batch != len(x):
+            raise ValueError("forward_chunk: the KVCache belongs to another model or batch size")
+        pt, ph, pw = self.patch_size
+        f, h, w = x[0].shape[1] // pt, x[0].shape[2] // ph, x[0].shape[3] // pw
+        tpf, L0 = h * w, cache.length
+        C = f * tpf
+        if C == 0 or C % 8:
+            raise ValueError(f"forward_chunk: {C} tokens per chunk; a positive multiple of 8 is needed (16-byte stores "
+                             "into the cache)")
+        if L0 % 8:
+            raise ValueError(f"forward_chunk: cache.length = {L0} is no multiple of 8")
+        cache.check_room(C)                                # ValueError past max_tokens
+        lo = 0
+        cc = getattr(self, "_causal_chunks", None)
+        if cc is not None:
+            Ct = cc[0] * tpf
+            if f > cc[0] or L0 % Ct:
+                raise ValueError(f"forward_chunk: a chunk of {f} frames at {L0} cached tokens does not fit chunks of "
+                                 f"{cc[0]} frames ({Ct} tokens)")
+            if cc[1] >= 0:
+                lo = max(0, L0 // Ct - cc[1]) * Ct
+        if frame_offset is None:
+            if L0 % tpf:
+                raise ValueError(f"forward_chunk: cache.length = {L0} is no multiple of {tpf} tokens per frame; pass frame_offset")
+            frame_offset = L0 // tpf
+        frame_offset = int(frame_offset)
+        if frame_offset < 0 or frame_offset + f > self.freqs.shape[0]:
+            raise ValueError(f"forward_chunk: frames [{frame_offset}, {frame_offset + f}) leave the rotary table "
+                             f"({self.freqs.shape[0]} frames)")
+        xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, C, clip_fea, y)
+        fc.chunk = None                                    # the cache IS the causal structure: plain attention over it
+        fc.rope_cos, fc.rope_sin = self._rope_shifted(xs.device, frame_offset)
+        fc.cache, fc.cache_lo = cache, lo
+        seq_lens = _dev_ints(lens, torch.long, xs.device)
+        grid_sizes = _dev_ints(grids, torch.long, xs.device)
+        context_lens = _dev_ints(ctx_lens, torch.long, xs.device)
+        freqs = (fc.rope_cos, fc.rope_sin)
+        for i, block in enumerate(self.blocks):
+            fc.cache_layer = i
+            xs = block(xs, fc.e0, seq_lens, grid_sizes, freqs, fc.ctx, context_lens, block_idx=i, _fc=fc)
+        out = self.head(xs, e)
+        if commit:
+            cache.advance(C)
+        return self.unpatchify(out, grid_sizes, _grids=grids)
+
     # ------------------------------------------------------------------ forward
     def _rope(self, device):
         if self._rope_dev is None or self._rope_dev[0] != str(device):
@@ -903,6 +1086,7 @@ class WanModel(nn.Module):
         fc.grid32 = _dev_ints(grids, torch.int32, device)
         fc.rope_cos, fc.rope_sin = self._rope(device)
         fc.seq_lens_host = list(lens)                                       # host copies: no device sync later
+        fc.chunk = self._causal_rule(grids)
         ctx_lens = self._attach_context(fc, context, clip_fea, extra_conditions)
         return xs, e, fc, grids, lens, ctx_lens
 

@@ -304,17 +304,20 @@ _side2 = {}
 _ALWAYS_COPY_DX = os.environ.get("OMH_BLOCK_DX_COPY", "0") == "1"
 
 
-def _attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, out, o32, q_prescaled, window=(-1, -1), block_mask=None):
+def _attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, out, o32, q_prescaled, window=(-1, -1), block_mask=None,
+              chunk_causal=None):
     """ops.flash_attn_bwd on the block's pre-scaled q, bf16 gradients into ``out`` — as one call, or (OMH_ATTN_BWD_SPLIT)
     as delta -> {dQ on this stream, dK / dV on a second one} -> join.  ``window``: the self-attention's band (the
-    band kernels; o32 required).  ``block_mask``: the self-attention's block mask (the block-list kernels; o32 required)."""
+    band kernels; o32 required).  ``block_mask``: the self-attention's block mask (the block-list kernels; o32 required).
+    ``chunk_causal``: the self-attention's staircase (WanModel.set_causal_chunks; the chunk kernels; o32 required)."""
     split = _ATTN_SPLIT == "1" or (_ATTN_SPLIT == "auto" and B * N * ((Lq + 127) // 128) > 512)
     if not (split and o32 is not None):
         return ops.flash_attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, q_prescaled=q_prescaled, out=out, o32=o32,
-                                  window=window, block_mask=block_mask)
+                                  window=window, block_mask=block_mask, chunk_causal=chunk_causal)
     dev = q.device
     delta = torch.empty(B, N, Lq, dtype=torch.float32, device=dev)
-    kw = dict(q_prescaled=q_prescaled, out=out, o32=o32, delta=delta, window=window, block_mask=block_mask)
+    kw = dict(q_prescaled=q_prescaled, out=out, o32=o32, delta=delta, window=window, block_mask=block_mask,
+              chunk_causal=chunk_causal)
     ops.flash_attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, phase=1, **kw)
     main = torch.cuda.current_stream(dev)
     s2 = _side2.get(dev)
@@ -767,9 +770,15 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
             bmask = sa._dynamic_mask(q, k, B, Sq, fc.seq_lens32)
     if need and not _ATTN_BWD2 and bmask is not None:
         raise NotImplementedError("OMH_ATTN_BWD=v1 has no block-mask backward: the mask needs the default kernels")
+    chunk = getattr(fc, "chunk", None)                      # WanModel.set_causal_chunks: the staircase kernels
+    if chunk is not None and (bmask is not None or win[0] >= 0 or win[1] >= 0):
+        raise ValueError("causal chunks exclude a block mask, a block policy and a bounded window_size")
+    if need and not _ATTN_BWD2 and chunk is not None:
+        raise NotImplementedError("OMH_ATTN_BWD=v1 has no chunk-causal backward: the mask needs the default kernels")
     ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, Sq, Sq, Sq * d, d, Sq * d, d, d * Sp,
                        Sq * d, d, Sp, D ** -0.5, lse=ptr(lse_sa) if need else None, q_prescaled=1,
-                       o32=ptr(o32_sa) if o32_sa is not None else None, flags=_ATTN_FLAGS, window=win, block_mask=bmask)
+                       o32=ptr(o32_sa) if o32_sa is not None else None, flags=_ATTN_FLAGS, window=win, block_mask=bmask,
+                       chunk_causal=chunk)
     x1, y1 = resid(x0, o, P["wo"], sa.o.bias.detach(), 2, True)
     S.update(h1=h1, qk=qk, q=q, k=k, vt=vt, o=o, lse_sa=lse_sa, y1=y1, x1=x1, o32_sa=o32_sa, bmask=bmask)
     # ---- cross-attention: x2 = x1 + o(attn(norm3(x1), context))                                     model.py:313
@@ -1084,7 +1093,8 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     v = ops.transpose_bf16_batched(S["vt"], Sq)                       # [B*S, d]
     dqkv = bf(R, 3 * d)                                               # dq | dk | dv, one buffer
     _attn_bwd(q, k, v, o, do, S["lse_sa"], fc.seq_lens32, B, N, Sq, Sq, D ** -0.5,
-              (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, tuple(sa.window_size), S["bmask"])
+              (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, tuple(sa.window_size), S["bmask"],
+              getattr(fc, "chunk", None))
     qk = S["qk"]
     rms_bwd(ptr(qk), True, 2 * d, ptr(dqkv), 3 * d, R, [sa._norm_w("norm_q"), sa._norm_w("norm_k")], sa.qk_norm, True,
             ["self_attn.norm_q.weight", "self_attn.norm_k.weight"], sa, n_seg=2, seg_x=d, seg_dy=d)   # q and k: one launch
