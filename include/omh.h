@@ -357,6 +357,44 @@ int omh_flash_attn_bwd_sparse_d128(const omh_attn_bwd_args* args, const int32_t*
                                    omh_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Interval masks: up to two key intervals per group of query rows, additive to ABI v12 (OMH_ABI_VERSION unchanged, no
+ * struct layout changed).  Both axes are cut into groups of `group` >= 8 positions (any such number: 1560 = 24 * 65
+ * works); a bool matrix vis[q_groups][k_groups], q_groups = ceil(Lq / group), k_groups = ceil(Lk / group), says which
+ * key groups a query group sees, and query i of sample b sees key j iff
+ *   i < qlen  and  j < klen  and  vis[i div group][j div group]     (qlen / klen = q_lens[b] / k_lens[b] or Lq / Lk).
+ * Positions are absolute.  vis has at most TWO runs of true in every row and in every column, so it is handed over as
+ * two device int32 tables of half-open group intervals:
+ *   q_iv [q_groups][4] = lo0, hi0, lo1, hi1: query group g sees the key groups [lo0, hi0) U [lo1, hi1), hi0 <= lo1,
+ *                                            lo == hi: empty (forward and dQ read it)
+ *   k_iv [k_groups][4]: the same relation seen from the key — the query groups that see key group g (dK / dV read it)
+ * omh_interval_mask_tables (a HOST function: plain memory in, plain memory out) builds both from vis (row-major bytes,
+ * non-zero = true) and returns OMH_E_BADARG for a third run in a row or a column, null pointers or a count < 1.
+ * Teacher forcing over [clean chunks | noisy chunks], the chunk-causal staircase and an attention sink + window are such
+ * tables.  Each workgroup runs the tiles inside the hull of its groups' first intervals and inside the hull of their
+ * second ones, in ascending order (one range when the two touch), skips the tiles between, and masks per element only
+ * the tiles that some live row of it does not see whole.
+ * A live row that sees no key gets o = 0, lse = -inf, dq = 0 (written); a key no live query sees gets dk = dv = 0
+ * (written); rows at or past qlen as in the varlen entries (zero output / gradient, their memory never used, NaN
+ * included).  Served by the short-sequence kernels only, never split, the workspace is declined, no atomics: repeatable
+ * bit for bit; with vis = [[1]] the bits of the plain entry on the short-sequence kernel.
+ * Not combined with anything: a band that is set is OMH_E_BADARG ((0, 0) reads as "not set", as in the sparse entries),
+ * so are a NULL struct, null tables, group < 8, reserved != 0 and group counts other than the ceilings above; tables not
+ * 4-byte aligned are OMH_E_ALIGN; Lq + Lk >= 2^28 is OMH_E_SHAPE.  The tables are read on the device and not validated:
+ * a bound outside [0, groups of the other axis] is clamped, an interval with hi <= lo is empty.  lse is optional in the
+ * forward; the backward has the o32 / lse / delta / phase / out_bf16 / q_prescaled contract of
+ * omh_flash_attn_bwd_varlen_d128 (o32 REQUIRED).
+ * ---------------------------------------------------------------------- */
+typedef struct omh_interval_mask {
+    int32_t group, q_groups, k_groups, reserved;
+    const int32_t* q_iv;   /* device [q_groups][4]: lo0, hi0, lo1, hi1 — key groups [lo0,hi0) U [lo1,hi1), hi0 <= lo1, lo == hi: empty */
+    const int32_t* k_iv;   /* device [k_groups][4]: the same relation seen from the key: query groups                                   */
+} omh_interval_mask;
+int omh_flash_attn_fwd_interval_d128(const omh_attn_args* args, const omh_interval_mask* mask, omh_stream_t stream);
+int omh_flash_attn_bwd_interval_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_interval_mask* mask,
+                                     omh_stream_t stream);
+int omh_interval_mask_tables(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv);
+
+/* ------------------------------------------------------------------------
  * Chunk-causal attention (a staircase over frame groups), additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout
  * changed).  The reference has no counterpart: it denoises a clip as one bidirectional sequence.  With
  *   qlen / klen = q_lens[b] / k_lens[b] (or Lq / Lk), clamped as elsewhere,

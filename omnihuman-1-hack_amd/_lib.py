@@ -138,6 +138,11 @@ class ChunkCausalArgs(C.Structure):
     _fields_ = [("chunk", i32), ("left_chunks", i32), ("q_offset", i32), ("reserved", i32)]
 
 
+class IntervalMaskArgs(C.Structure):
+    """omh_interval_mask (additive to ABI v12): the two int32 tables of causal.IntervalMask."""
+    _fields_ = [("group", i32), ("q_groups", i32), ("k_groups", i32), ("reserved", i32), ("q_iv", vp), ("k_iv", vp)]
+
+
 class BlockPoolOperand(C.Structure):
     """omh_block_pool_operand (additive to ABI v12): one bf16 operand of omh_block_pool_d128 and its outputs."""
     _fields_ = [("x", vp), ("ld", i64), ("L", i32), ("reserved", i32), ("lens", vp), ("mean", vp), ("coh", vp)]
@@ -218,6 +223,9 @@ _SIGS = {
     "omh_flash_attn_bwd_sparse_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(BlockMaskArgs), vp]),
     "omh_flash_attn_fwd_chunk_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(ChunkCausalArgs), vp]),
     "omh_flash_attn_bwd_chunk_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(ChunkCausalArgs), vp]),
+    "omh_flash_attn_fwd_interval_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(IntervalMaskArgs), vp]),
+    "omh_flash_attn_bwd_interval_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(IntervalMaskArgs), vp]),
+    "omh_interval_mask_tables": (i32, [vp, i32, i32, vp, vp]),
     "omh_block_pool_d128": (i32, [C.POINTER(BlockPoolOperand), i32, i32, i32, vp]),
     "omh_block_select": (i32, [C.POINTER(BlockSelectArgs), vp]),
     "omh_block_mask_tables": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),

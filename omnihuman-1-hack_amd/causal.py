@@ -9,10 +9,18 @@ The rule (include/omh.h, ``omh_chunk_causal``): with ``chunk`` = C >= 1 tokens, 
 Positions are absolute (no bottom-right shift).  ``WanModel.set_causal_chunks`` runs every self-attention of a forward
 under it with C = a group of latent frames; ``WanModel.forward_chunk`` produces the same clip frame group by frame group
 against a ``KVCache``, and ``sample`` denoises a clip that way.
+
+Interval masks (include/omh.h, ``omh_interval_mask``) are the table-driven generalisation: both axes are cut into groups
+of ``group`` tokens and a bool matrix ``vis[q_groups, k_groups]`` with at most two runs of True per row and per column
+says which key groups a query group sees.  ``IntervalMask`` holds such a matrix with its device tables;
+``teacher_forcing_groups`` and ``sink_window_groups`` build two useful ones, ``interval_visible`` is the dense mask.
 """
+import ctypes
+
 import torch
 
-__all__ = ["chunk_causal_visible", "KVCache", "sample"]
+__all__ = ["chunk_causal_visible", "KVCache", "sample", "IntervalMask", "interval_visible", "teacher_forcing_groups",
+           "sink_window_groups", "forcing_loss"]
 
 
 def chunk_causal_visible(Lq, Lk, chunk, left_chunks=-1, q_offset=0, qlen=None, klen=None):
@@ -30,6 +38,118 @@ def chunk_causal_visible(Lq, Lk, chunk, left_chunks=-1, q_offset=0, qlen=None, k
     if left_chunks >= 0:
         vis = vis & (cj >= ci - left_chunks)
     return vis
+
+
+class IntervalMask:
+    """An interval mask for ``ops.flash_attn(interval_mask=)`` and its family: ``vis`` is a bool matrix
+    [q_groups, k_groups] (anything ``torch.as_tensor`` takes) over groups of ``group`` >= 8 tokens; query i sees key j iff
+    ``vis[i // group, j // group]`` (and both are below their sample's lengths).  Every row and every column may hold at
+    most two runs of True (ValueError otherwise): the kernels carry two key intervals per query group and two query
+    intervals per key group.  Both int32 tables [groups, 4] = lo0, hi0, lo1, hi1 are built once, on the host
+    (omh_interval_mask_tables), and held on ``device``."""
+
+    def __init__(self, vis, group, device="cpu"):
+        from . import _lib
+        vis = torch.as_tensor(vis).detach().to("cpu")
+        group = int(group)
+        if vis.dim() != 2 or vis.shape[0] < 1 or vis.shape[1] < 1:
+            raise ValueError(f"IntervalMask: a matrix [q_groups, k_groups] expected, got {tuple(vis.shape)}")
+        if group < 8:
+            raise ValueError(f"IntervalMask: group = {group}, at least 8 tokens expected")
+        self.vis = (vis != 0).contiguous()
+        self.group, self.q_groups, self.k_groups = group, int(vis.shape[0]), int(vis.shape[1])
+        bytes_ = self.vis.to(torch.uint8).contiguous()
+        q_iv = torch.zeros(self.q_groups, 4, dtype=torch.int32)
+        k_iv = torch.zeros(self.k_groups, 4, dtype=torch.int32)
+        rc = _lib.lib.omh_interval_mask_tables(ctypes.c_void_p(bytes_.data_ptr()), self.q_groups, self.k_groups,
+                                               ctypes.c_void_p(q_iv.data_ptr()), ctypes.c_void_p(k_iv.data_ptr()))
+        if rc != 0:
+            raise ValueError("IntervalMask: a row or a column of vis holds more than two runs of True")
+        self._host = (q_iv, k_iv)
+        self.q_iv = self.k_iv = None
+        self._move(torch.device(device))
+
+    def _move(self, device):
+        self.device = device
+        self.q_iv, self.k_iv = (t.to(device) for t in self._host)
+
+    def to(self, device):
+        """This mask with its tables on ``device`` (itself when they are there already)."""
+        device = torch.device(device)
+        if device == self.device:
+            return self
+        other = object.__new__(IntervalMask)
+        other.__dict__.update(self.__dict__)
+        other._move(device)
+        return other
+
+    def intervals(self):
+        """The two tables as nested lists (host copies): ([q_groups][4], [k_groups][4]) of lo0, hi0, lo1, hi1."""
+        return self._host[0].tolist(), self._host[1].tolist()
+
+    def c_struct(self):
+        from . import _lib
+        return _lib.IntervalMaskArgs(self.group, self.q_groups, self.k_groups, 0, self.q_iv.data_ptr(), self.k_iv.data_ptr())
+
+    def tiles(self, Lq, Lk, block=128, tile=64):
+        """Key tiles of ``tile`` tokens the forward's workgroups (``block`` query rows each) run on full-length samples,
+        per head: what the kernel derives from the q_iv table, computed here from the same numbers."""
+        q_iv, total = self.intervals()[0], 0
+        for q0 in range(0, Lq, block):
+            rows = q_iv[q0 // self.group:(min(q0 + block, Lq) - 1) // self.group + 1]
+            hull = []
+            for lo, hi in ((0, 1), (2, 3)):
+                iv = [(r[lo] * self.group, min(r[hi] * self.group, Lk)) for r in rows if r[hi] > r[lo]]
+                iv = [(a, b) for a, b in iv if b > a]
+                if iv:
+                    hull.append((min(a for a, _ in iv) // tile, (max(b for _, b in iv) - 1) // tile + 1))
+            if len(hull) == 2 and hull[1][0] <= hull[0][1]:
+                hull = [(hull[0][0], max(hull[0][1], hull[1][1]))]
+            total += sum(b - a for a, b in hull)
+        return total
+
+
+def interval_visible(mask, Lq, Lk, qlen=None, klen=None):
+    """The rule of an ``IntervalMask`` as a dense bool mask [Lq, Lk] (plain torch, on the CPU): True where query i sees
+    key j.  ValueError when the mask's group counts are not ceil(Lq / group) x ceil(Lk / group)."""
+    g = mask.group
+    if (mask.q_groups, mask.k_groups) != ((Lq + g - 1) // g, (Lk + g - 1) // g):
+        raise ValueError(f"interval_visible: a mask of {mask.q_groups} x {mask.k_groups} groups of {g} does not cover "
+                         f"Lq = {Lq}, Lk = {Lk}")
+    qlen = Lq if qlen is None else min(max(int(qlen), 0), Lq)
+    klen = Lk if klen is None else min(max(int(klen), 0), Lk)
+    i = torch.arange(Lq, dtype=torch.int64).view(Lq, 1)
+    j = torch.arange(Lk, dtype=torch.int64).view(1, Lk)
+    dense = mask.vis.repeat_interleave(g, 0)[:Lq].repeat_interleave(g, 1)[:, :Lk]
+    return dense & (i < qlen) & (j < klen)
+
+
+def teacher_forcing_groups(n_chunks, left_chunks=-1):
+    """The teacher-forcing matrix over the sequence [n clean chunks | n noisy chunks], bool [2n, 2n]: clean row g sees
+    clean j <= g (and j >= g - W when W = ``left_chunks`` >= 0); noisy row n + I sees clean j < I (and j >= I - W) and noisy
+    n + I only — what ``WanModel.forward_chunk`` attends to at chunk I with ``left_chunks`` = W."""
+    n, W = int(n_chunks), int(left_chunks)
+    if n < 1:
+        raise ValueError(f"teacher_forcing_groups: n_chunks = {n} >= 1 expected")
+    g = torch.arange(n).view(n, 1)
+    j = torch.arange(n).view(1, n)
+    back = (j >= g - W) if W >= 0 else torch.ones(n, n, dtype=torch.bool)
+    vis = torch.zeros(2 * n, 2 * n, dtype=torch.bool)
+    vis[:n, :n] = (j <= g) & back
+    vis[n:, :n] = (j < g) & back
+    vis[n:, n:] = torch.eye(n, dtype=torch.bool)
+    return vis
+
+
+def sink_window_groups(n_chunks, sink_chunks, left_chunks):
+    """An attention sink plus a causal window, bool [n, n]: row g sees j <= g with j < ``sink_chunks`` or
+    j >= g - ``left_chunks``.  Only the mask: nothing here evicts a cache."""
+    n, S, W = int(n_chunks), int(sink_chunks), int(left_chunks)
+    if n < 1 or S < 0 or W < 0:
+        raise ValueError(f"sink_window_groups: n_chunks = {n} >= 1, sink_chunks = {S} >= 0 and left_chunks = {W} >= 0 expected")
+    g = torch.arange(n).view(n, 1)
+    j = torch.arange(n).view(1, n)
+    return (j <= g) & ((j < S) | (j >= g - W))
 
 
 class KVCache:
@@ -120,3 +240,36 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
         return torch.cat(done, dim=1)
     finally:
         model._causal_chunks = prev
+
+
+def forcing_loss(model, latents, noise, sigmas, timesteps, context, mode="teacher"):
+    """The flow-matching loss of a frame-causal student with one noise level per chunk.  ``latents`` / ``noise``: lists of
+    [C, F, H, W] (x_0 and epsilon, every clip of one shape); ``sigmas`` / ``timesteps``: [B, F / fpc], per chunk
+    (fpc = the model's ``set_causal_chunks`` frames per chunk).  x_t = (1 - sigma) x_0 + sigma epsilon per chunk, the
+    target is epsilon - x_0.  ``mode="teacher"``: ``model.forward_teacher_forcing(latents, x_t, timesteps, context)`` —
+    the noisy chunks attend to the CLEAN chunks before them; ``mode="diffusion"``: ``model.forward`` on x_t alone with
+    the per-frame timesteps under the staircase (diffusion forcing: they attend to the noisy ones).  Returns the mean
+    squared error over all clips (plain torch on the model's outputs)."""
+    cc = getattr(model, "_causal_chunks", None)
+    if cc is None:
+        raise ValueError("forcing_loss: model.set_causal_chunks(frames_per_chunk, left_chunks) first")
+    if mode not in ("teacher", "diffusion"):
+        raise ValueError(f"forcing_loss: mode = {mode!r}, 'teacher' or 'diffusion' expected")
+    fpc = cc[0]
+    latents, noise = list(latents), list(noise)
+    F = latents[0].shape[1] // model.patch_size[0]
+    if F % fpc or tuple(sigmas.shape) != (len(latents), F // fpc) or tuple(timesteps.shape) != tuple(sigmas.shape):
+        raise ValueError(f"forcing_loss: sigmas and timesteps of shape [{len(latents)}, F / {fpc}] expected for F = {F}")
+    per_frame = lambda v: v.repeat_interleave(fpc * model.patch_size[0], dim=1)
+    x_t, target = [], []
+    for b, (x0, eps) in enumerate(zip(latents, noise)):
+        s = per_frame(sigmas[b:b + 1]).to(device=x0.device, dtype=x0.dtype).view(1, -1, 1, 1)
+        x_t.append((1 - s) * x0 + s * eps)
+        target.append(eps - x0)
+    if mode == "teacher":
+        out = model.forward_teacher_forcing(latents, x_t, timesteps, context)
+    else:
+        pt, ph, pw = model.patch_size
+        tokens = F * (latents[0].shape[2] // ph) * (latents[0].shape[3] // pw)
+        out = model(x_t, timesteps.repeat_interleave(fpc, dim=1), context, tokens)
+    return torch.stack([(o.float() - v.to(o.device).float()).square().mean() for o, v in zip(out, target)]).mean()

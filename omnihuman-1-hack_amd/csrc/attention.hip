@@ -89,12 +89,20 @@ struct AttnSplit {
 // test against the interval every live row sees whole).  A workgroup's work grows with its position, so the query tiles
 // of a head are handed out last tile first: the long ones start first and the launch ends on short ones.  The divisions
 // happen here, once per workgroup and once per row.  Never split.
-template <bool WIN, bool BLK = false, bool CHK = false>
+// IVL (with WIN): an interval mask (include/omh.h omh_interval_mask; omh_common.h IvlTab, the q_iv table) — again the
+// band's machinery, with TWO key intervals per row, read from the row of its group.  The workgroup reads the table rows
+// of the groups its live rows span (scalar loads, before the loop), runs the tiles inside the hull of their first
+// intervals, then — `gap` tiles further — those inside the hull of their second ones (one range when the two touch), and
+// masks per element only the tiles that are not inside an interval every one of those groups shares.  Never split.
+// The query tiles keep their natural order: last tile first, CHK's order, lost time under teacher forcing.
+template <bool WIN, bool BLK = false, bool CHK = false, bool IVL = false>
 __global__ __launch_bounds__(256, 2)
 void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk, const BlkList bl,
                                 const ChunkRule ck) {
     static_assert(!(WIN && BLK), "a block mask excludes the band");
     static_assert(!CHK || WIN, "the staircase runs on the band's masking");
+    static_assert(!IVL || (WIN && !CHK), "an interval mask runs on the band's masking, in place of the other rules");
+    const IvlTab iv = omh_ivl_tab(bl);                    // IVL: the table arrives in the BlkList argument
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (KT_BYTES + VT_BYTES)];
 
     const int tid = threadIdx.x;
@@ -120,13 +128,25 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     int t_first = 0, n_tiles = n_tiles_all;
     int band_shift = 0;                                   // WIN: key index of the band's centre for query row 0
     int whole_lo = 0, whole_hi = -1;                      // CHK: the keys EVERY live row of the workgroup sees
+    int whole1_lo = 0, whole1_hi = -1;                    // IVL: ... through its second interval (whole_lo / hi: the first)
+    int n_first = 0, t_gap = 0;                           // IVL: tiles of the first range, tiles skipped behind it
     if constexpr (WIN) {
         int qlen = p.q_lens ? p.q_lens[b] : p.Lq;
         qlen = min(max(qlen, 0), p.Lq);
         band_shift = klen - qlen;
         const int q0 = qt * QB, q1 = min(q0 + QB, qlen) - 1;                  // live query rows of this workgroup
         int lo, hi;
-        if constexpr (CHK) {
+        if constexpr (IVL) {
+            lo = 0; hi = -1;
+            if (q1 >= q0) {
+                int w0[2], w1[2];
+                const IvlTiles it = omh_ivl_tiles(iv, q0, q1, klen, KB, w0, w1);
+                whole_lo = w0[0]; whole_hi = w0[1]; whole1_lo = w1[0]; whole1_hi = w1[1];
+                t_first = it.t_first; n_first = it.n0; t_gap = it.gap; n_tiles = it.n_tiles;
+            } else {
+                n_tiles = 0;
+            }
+        } else if constexpr (CHK) {
             const int c0 = (ck.off + q0) / ck.chunk, c1 = (ck.off + max(q1, 0)) / ck.chunk;   // chunks of the first / last live row
             lo = ck.left < 0 ? 0 : max(0, (c0 - ck.left) * ck.chunk);
             hi = min(klen, (c1 + 1) * ck.chunk) - 1;
@@ -136,11 +156,13 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
             lo = p.window_left < 0 ? 0 : max(0, q0 + band_shift - p.window_left);
             hi = p.window_right < 0 ? klen - 1 : min(klen - 1, q1 + band_shift + p.window_right);
         }
+        if constexpr (!IVL) {
         if (q1 < q0 || hi < lo) {
             n_tiles = 0;
         } else {
             t_first = lo / KB;
             n_tiles = hi / KB - t_first + 1;
+        }
         }
     }
     if (worker) {
@@ -176,7 +198,10 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     const int q_row = qt * QB + wave * 32 + li;
     const int q_ld = min(q_row, p.Lq - 1);
     int key_lo = 0, key_hi = klen - 1;                    // WIN: this lane's (query row's) band of keys
-    if constexpr (CHK) {
+    IvlSpan span = {0, 0, 0, 0};                          // IVL: this lane's two intervals of keys
+    if constexpr (IVL) {
+        span = omh_ivl_row(iv, q_row / iv.group, klen);
+    } else if constexpr (CHK) {
         const int ci = (ck.off + q_row) / ck.chunk;                           // this row's chunk
         if (ck.left >= 0) key_lo = max(0, (ci - ck.left) * ck.chunk);
         key_hi = min(klen, (ci + 1) * ck.chunk) - 1;
@@ -257,11 +282,15 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     for (int tt = 0; tt < n_tiles; ++tt) {
         const int buf = tt & 1;
         int t = t_first + tt;
+        if constexpr (IVL) t += tt >= n_first ? t_gap : 0;
         if constexpr (BLK) {
             t = t_cur;
             OMH_GLOAD(t_nxt)
             t_cur = t_nxt;
             t_nxt = blk_tile(min(tt + 2, n_tiles - 1));   // a tile ahead of its loads
+        } else if constexpr (IVL) {
+            const int nx = min(tt + 1, n_tiles - 1);
+            OMH_GLOAD(t_first + nx + (nx >= n_first ? t_gap : 0))
         } else {
         OMH_GLOAD(t_first + min(tt + 1, n_tiles - 1))   // unconditional: keeps the staging registers out of scratch
         }
@@ -286,6 +315,17 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         const int kv0 = t * KB;
         // CHK: a tile inside [whole_lo, whole_hi] needs no mask for a live row (rows at or past qlen are written as zeros
         // whatever they accumulate): most tiles of a long look-back
+        if (IVL && ((kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi) || (kv0 >= whole1_lo && kv0 + KB - 1 <= whole1_hi))) {
+            // inside an interval every live row of the workgroup sees (cut at klen): nothing to mask
+        } else if constexpr (IVL) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = kv0 + kb * 32 + ((r >> 3) << 4) + lh * 8 + (r & 7);
+                    if (!span.sees(key)) s[kb][r] = -INFINITY;
+                }
+        } else
         if (WIN && !(CHK && kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi)) {   // (key_hi <= klen - 1: the band mask covers the sequence end too)
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -603,4 +643,50 @@ extern "C" int omh_flash_attn_fwd_chunk_d128(const omh_attn_args* args, const om
     hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<true, false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles, wk,
                        BlkList{}, ck);
     return omh_launch_status();
+}
+
+// Additive to ABI v12: the forward under an interval mask (include/omh.h).  The short-sequence kernel's IVL
+// instantiation, whatever the shape: no long-sequence stream, no split, no bounded stream.
+extern "C" int omh_flash_attn_fwd_interval_d128(const omh_attn_args* args, const omh_interval_mask* mask, omh_stream_t stream) {
+    if (!mask) return OMH_E_BADARG;
+    const int rc0 = attn_fwd_check(args);
+    if (rc0) return rc0;
+    const omh_attn_args& a = *args;
+    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
+    const int rc1 = omh_interval_mask_check(mask, a.Lq, a.Lk);
+    if (rc1) return rc1;
+    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
+    const int q_tiles = (a.Lq + QB - 1) / QB;
+    const int nwg = q_tiles * a.H * a.B;
+    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
+    omh_clear_status();
+    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<true, false, false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles,
+                       wk, omh_ivl_arg(mask->q_iv, mask->group, mask->q_groups, mask->k_groups), ChunkRule{});
+    return omh_launch_status();
+}
+
+// The two tables of an omh_interval_mask from its bool matrix (a host function: no device is touched).  Row g of q_iv:
+// the at most two runs of true in row g of vis, as half-open intervals; k_iv: the same for the columns.
+static int ivl_runs(const uint8_t* v, int n, int64_t stride, int32_t* out) {
+    int runs = 0;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    for (int j = 0; j < n; ++j) {
+        const bool on = v[j * stride] != 0, prev = j > 0 && v[(j - 1) * stride] != 0;
+        if (on && !prev) {
+            if (runs == 2) return OMH_E_BADARG;
+            out[2 * runs] = j;
+            ++runs;
+        }
+        if (on) out[2 * runs - 1] = j + 1;
+    }
+    if (runs < 2) out[2] = out[3] = out[1];               // hi0 <= lo1 = hi1: empty
+    return 0;
+}
+extern "C" int omh_interval_mask_tables(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv) {
+    if (!vis || !q_iv || !k_iv || q_groups < 1 || k_groups < 1) return OMH_E_BADARG;
+    for (int g = 0; g < q_groups; ++g)
+        if (ivl_runs(vis + (int64_t)g * k_groups, k_groups, 1, q_iv + 4 * (int64_t)g)) return OMH_E_BADARG;
+    for (int g = 0; g < k_groups; ++g)
+        if (ivl_runs(vis + g, q_groups, k_groups, k_iv + 4 * (int64_t)g)) return OMH_E_BADARG;
+    return 0;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/omh.h"
 
@@ -143,6 +144,10 @@ static inline int omh_launch_status() {
 // ---- block masks (include/omh.h omh_block_mask; attention.hip, attention_bwd2.hip) ----
 // What a BLK kernel gets: one list per (mask head, 128-row block of the workgroup's side) — `cnt` entries of `idx`,
 // ascending indices of the 128-position blocks of the other side (row lists: forward and dQ; column lists: dK / dV).
+// The IVL kernels (interval masks, below) receive their table in this same argument, since no kernel has both a block
+// mask and an interval mask: idx = the table, heads = group, lists = its rows, stride = groups of the other axis, cnt
+// unused.  omh_ivl_arg / omh_ivl_tab are the only two places that know the mapping; a change of this struct's fields
+// must keep them (and the asserts behind IvlTab) in step.
 struct BlkList {
     const int32_t* cnt;   // [heads][lists]
     const int32_t* idx;   // [heads][lists][stride]
@@ -179,6 +184,80 @@ static inline int omh_chunk_rule(const omh_chunk_causal* c, int Lq, int Lk, Chun
     out->off = c->q_offset;
     return 0;
 }
+
+// ---- interval masks (include/omh.h omh_interval_mask; attention.hip, attention_bwd2.hip) ----
+// What an IVL kernel gets: ONE of the two tables — row g of `iv` holds the (at most two) intervals [lo0, hi0) U [lo1, hi1)
+// of groups of the OTHER axis that group g of the workgroup's axis sees (q_iv: forward and dQ; k_iv: dK / dV), in groups
+// of `group` positions; `n` rows, `other` groups on the other axis.
+struct IvlTab {
+    const int32_t* iv;    // [n][4]
+    int group, n, other;
+};
+// The IVL kernels take their table in the BlkList argument (no kernel has both): a further kernel argument would change
+// the kernarg segment, and with it the scalar loads of the instantiations that must keep their instruction streams.
+static inline BlkList omh_ivl_arg(const int32_t* iv, int group, int n, int other) { return BlkList{nullptr, iv, group, n, other}; }
+static_assert(sizeof(BlkList) == 2 * sizeof(void*) + 4 * sizeof(int) && sizeof(IvlTab) + sizeof(void*) == sizeof(BlkList),
+              "IvlTab travels in a BlkList: one pointer and three ints beside the unused cnt");
+static_assert(std::is_same<decltype(BlkList::idx), decltype(IvlTab::iv)>::value && std::is_same<decltype(BlkList::heads), int>::value &&
+              std::is_same<decltype(BlkList::lists), int>::value && std::is_same<decltype(BlkList::stride), int>::value,
+              "omh_ivl_arg / omh_ivl_tab map idx, heads, lists, stride to iv, group, n, other");
+// 0 or the error code (the tables themselves live on the device: the kernels clamp what they read to [0, other])
+static inline int omh_interval_mask_check(const omh_interval_mask* m, int Lq, int Lk) {
+    if (!m || !m->q_iv || !m->k_iv || m->group < 8 || m->reserved != 0) return OMH_E_BADARG;
+    if ((int64_t)Lq + Lk >= (1LL << 28)) return OMH_E_SHAPE;
+    if (m->q_groups != (Lq + m->group - 1) / m->group || m->k_groups != (Lk + m->group - 1) / m->group) return OMH_E_BADARG;
+    if (((uintptr_t)m->q_iv | (uintptr_t)m->k_iv) & 3) return OMH_E_ALIGN;
+    return 0;
+}
+#if defined(__HIPCC__)
+__device__ __forceinline__ IvlTab omh_ivl_tab(const BlkList& bl) { return IvlTab{bl.idx, bl.heads, bl.lists, bl.stride}; }
+// One position's (or one workgroup's) view of the other axis: two intervals of positions [lo, lo + len), len <= 0: empty.
+struct IvlSpan {
+    int lo0, len0, lo1, len1;
+    __device__ __forceinline__ bool sees(int x) const {
+        return (unsigned)(x - lo0) < (unsigned)len0 || (unsigned)(x - lo1) < (unsigned)len1;
+    }
+};
+// row g of the table in positions, cut at `end` (the live length of the other axis)
+__device__ __forceinline__ IvlSpan omh_ivl_row(const IvlTab& tb, int g, int end) {
+    const int32_t* __restrict__ r = tb.iv + 4 * (int64_t)min(max(g, 0), tb.n - 1);
+    const int a0 = min(max(r[0], 0), tb.other), a1 = min(max(r[1], 0), tb.other);
+    const int b0 = min(max(r[2], 0), tb.other), b1 = min(max(r[3], 0), tb.other);
+    IvlSpan s;
+    s.lo0 = a0 * tb.group; s.len0 = max(min(a1 * tb.group, end) - s.lo0, 0);
+    s.lo1 = b0 * tb.group; s.len1 = max(min(b1 * tb.group, end) - s.lo1, 0);
+    return s;
+}
+// The tiles of `tile` positions a workgroup whose live positions are x0 .. x1 (x1 >= x0) runs: the hull of its groups'
+// first intervals and the hull of their second ones, as tile ranges [t_first, t_first + n0) and, `gap` tiles further,
+// n_tiles - n0 more; one range when they touch.  whole0 / whole1 (may be NULL): the positions EVERY one of those groups
+// sees through its first / second interval ([lo, hi], hi < lo: none).  Scalar reads, once per workgroup.
+struct IvlTiles { int t_first, n0, gap, n_tiles; };
+__device__ __forceinline__ IvlTiles omh_ivl_tiles(const IvlTab& tb, int x0, int x1, int end, int tile, int* whole0, int* whole1) {
+    const int g0 = x0 / tb.group, g1 = x1 / tb.group;
+    int alo = 1 << 30, ahi = 0, blo = 1 << 30, bhi = 0;              // hulls, [lo, hi)
+    int w0lo = 0, w0hi = 1 << 30, w1lo = 0, w1hi = 1 << 30;          // intersections, [lo, hi)
+    for (int g = g0; g <= g1; ++g) {
+        const IvlSpan s = omh_ivl_row(tb, __builtin_amdgcn_readfirstlane(g), end);
+        if (s.len0 > 0) { alo = min(alo, s.lo0); ahi = max(ahi, s.lo0 + s.len0); }
+        if (s.len1 > 0) { blo = min(blo, s.lo1); bhi = max(bhi, s.lo1 + s.len1); }
+        w0lo = max(w0lo, s.lo0); w0hi = min(w0hi, s.lo0 + s.len0);
+        w1lo = max(w1lo, s.lo1); w1hi = min(w1hi, s.lo1 + s.len1);
+    }
+    if (whole0) { whole0[0] = w0lo; whole0[1] = w0hi - 1; }
+    if (whole1) { whole1[0] = w1lo; whole1[1] = w1hi - 1; }
+    if (ahi <= alo) { alo = blo; ahi = bhi; blo = 1 << 30; bhi = 0; }   // only second intervals: they are the one range
+    IvlTiles t = {0, 0, 0, 0};
+    if (ahi <= alo) return t;
+    const int a0 = alo / tile, a1 = (ahi - 1) / tile + 1;
+    t.t_first = a0;
+    if (bhi <= blo) { t.n0 = t.n_tiles = a1 - a0; return t; }
+    const int b0 = blo / tile, b1 = (bhi - 1) / tile + 1;
+    if (b0 <= a1) { t.n0 = t.n_tiles = max(a1, b1) - a0; return t; }
+    t.n0 = a1 - a0; t.gap = b0 - a1; t.n_tiles = t.n0 + (b1 - b0);
+    return t;
+}
+#endif
 
 // ---- split of a launch's last, partly filled round of workgroups (host side; attention.hip, attention_bwd2.hip) ----
 // A launch of `nwg` equal workgroups on `slots` resident slots takes ceil(nwg / slots) rounds; its last round holds

@@ -202,9 +202,36 @@ def _chunk_causal(chunk_causal, window=(-1, -1), block_mask=None):
     return _lib.ChunkCausalArgs(min(chunk, big), -1 if left < 0 else min(left, big), min(off, big), 0)
 
 
+def _interval_mask(interval_mask, Lq, Lk, window=(-1, -1), block_mask=None, chunk_causal=None, device=None):
+    """``interval_mask`` (None or a ``causal.IntervalMask``) checked against this call, with its tables on ``device`` (the
+    operands' device; the callers that only have pointers pass None: a mask that is on a GPU already stays there, one on
+    the CPU goes to the current device): ValueError for a band, a block mask or ``chunk_causal`` beside it (a mask is not
+    combined with anything), or group counts other than ceil(Lq / group) x ceil(Lk / group)."""
+    if interval_mask is None:
+        return None
+    from .causal import IntervalMask
+    if window[0] >= 0 or window[1] >= 0:
+        raise ValueError("interval_mask excludes causal / a bounded window (it is not an intersection)")
+    if block_mask is not None:
+        raise ValueError("interval_mask excludes a block mask (it is not an intersection)")
+    if chunk_causal is not None:
+        raise ValueError("interval_mask excludes chunk_causal (it is not an intersection)")
+    if not isinstance(interval_mask, IntervalMask):
+        raise ValueError("interval_mask: a causal.IntervalMask expected (it holds the group size and the device tables)")
+    g = interval_mask.group
+    if (interval_mask.q_groups, interval_mask.k_groups) != ((Lq + g - 1) // g, (Lk + g - 1) // g):
+        raise ValueError(f"interval mask of {interval_mask.q_groups} x {interval_mask.k_groups} groups of {g} on a call with "
+                         f"Lq = {Lq}, Lk = {Lk} ({(Lq + g - 1) // g} x {(Lk + g - 1) // g} expected)")
+    if device is None:
+        if interval_mask.device.type == "cuda":
+            return interval_mask
+        device = torch.device("cuda", torch.cuda.current_device())
+    return interval_mask.to(device)
+
+
 def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale,
                    lse=None, q_prescaled=0, o32=None, flags=0, q_lens=None, window=(-1, -1), qk_norm2_max=None,
-                   block_mask=None, chunk_causal=None):
+                   block_mask=None, chunk_causal=None, interval_mask=None):
     """``flags``: ATTN_SHORT_KERNEL | ATTN_ALLOW_SPLIT (include/omh.h, ABI v8): the training step pins the short-sequence
     kernel (forward and re-run take the same one) and lets it split its last round of workgroups over the keys.
     ``q_lens`` (ABI v10): int32 [B] device pointer; output rows past a sample's query length are written as zero.
@@ -216,7 +243,11 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
     over each query block's list of key blocks, never split, never the bounded stream); ValueError beside a band.
     ``chunk_causal``: (chunk, left_chunks, q_offset) — the staircase of omh_flash_attn_fwd_chunk_d128 (include/omh.h): query
     i sees key j iff j // chunk <= (q_offset + i) // chunk, and >= that - left_chunks when left_chunks >= 0; the
-    short-sequence kernel, never split; ValueError beside a band or a block mask."""
+    short-sequence kernel, never split; ValueError beside a band or a block mask.
+    ``interval_mask``: a ``causal.IntervalMask`` — up to two key intervals per group of query rows
+    (omh_flash_attn_fwd_interval_d128, include/omh.h): the short-sequence kernel over the tiles inside each workgroup's
+    two ranges, never split; ValueError beside a band, a block mask or ``chunk_causal``."""
+    im = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal)
     cc = _chunk_causal(chunk_causal, window, block_mask)
     bm = _block_mask(block_mask, H, Lq, Lk, window)
     a = AttnArgs(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale, lse,
@@ -227,6 +258,10 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
         return
     if cc is not None:
         check(lib.omh_flash_attn_fwd_chunk_d128(C.byref(a), C.byref(cc), _stream()), "omh_flash_attn_fwd_chunk_d128")
+        return
+    if im is not None:
+        m = im.c_struct()
+        check(lib.omh_flash_attn_fwd_interval_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_interval_d128")
         return
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
     ws = None
@@ -241,7 +276,8 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
                scale: Optional[float] = None, out: Optional[torch.Tensor] = None, q_lens: Optional[torch.Tensor] = None,
-               window=(-1, -1), block_mask=None, lse: Optional[torch.Tensor] = None, chunk_causal=None):
+               window=(-1, -1), block_mask=None, lse: Optional[torch.Tensor] = None, chunk_causal=None,
+               interval_mask=None):
     """q [B,Lq,H,128], k [B,Lk,H,128] bf16; vt [B,H*128,ldv] bf16 (V transposed,
     ldv >= roundup(Lk,64)); k_lens / q_lens int32 [B] or None.  Returns [B,Lq,H,128] bf16 (rows past q_lens: zero).
     ``window`` = (left, right): flash-attn's bottom-right aligned band (causal = (-1, 0)); (-1, -1): full attention.
@@ -249,12 +285,16 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
     sees key j iff its block is kept (and j < k_lens[b], i < q_lens[b]); rows that see no key are zero.  ValueError
     together with a bounded ``window``.  ``lse``: optional fp32 [B, H, Lq] the log-sum-exp is written to.
     ``chunk_causal`` = (chunk, left_chunks, q_offset): the chunk-causal staircase (see ``flash_attn_raw``); rows that see
-    no key are zero (lse = -inf).  ValueError together with a bounded ``window`` or a ``block_mask``."""
+    no key are zero (lse = -inf).  ValueError together with a bounded ``window`` or a ``block_mask``.
+    ``interval_mask``: a ``causal.IntervalMask`` (see ``flash_attn_raw``): query i sees key j iff the mask's matrix holds
+    True at [i // group, j // group] (and j < k_lens[b], i < q_lens[b]); rows that see no key are zero (lse = -inf).
+    ValueError together with any of the other three."""
     _dev(q, k, vt, k_lens, out, q_lens, lse)
     if q_lens is not None:
         assert q_lens.dtype == torch.int32 and q_lens.numel() == q.shape[0]
     B, Lq, H, D = q.shape
     Lk = k.shape[1]
+    interval_mask = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal, device=q.device)   # the tables beside q
     assert D == 128 and k.shape == (B, Lk, H, D) and vt.shape[0] == B and vt.shape[1] == H * D
     assert q.dtype == k.dtype == vt.dtype == torch.bfloat16
     assert q.stride(3) == 1 and q.stride(2) == D and k.stride(3) == 1 and k.stride(2) == D and vt.stride(2) == 1
@@ -265,12 +305,13 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
     flash_attn_raw(_p(q), _p(k), _p(vt), _p(out), _p(k_lens), B, H, Lq, Lk, q.stride(0), q.stride(1), k.stride(0),
                    k.stride(1), vt.stride(0), out.stride(0), out.stride(1), vt.stride(1),
                    float(scale if scale is not None else D ** -0.5), q_lens=_p(q_lens), window=window,
-                   block_mask=block_mask, lse=_p(lse), chunk_causal=chunk_causal)
+                   block_mask=block_mask, lse=_p(lse), chunk_causal=chunk_causal, interval_mask=interval_mask)
     return out
 
 
 def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_prescaled=False, out=None, o32=None,
-                   phase=0, delta=None, split=True, window=(-1, -1), q_lens=None, block_mask=None, chunk_causal=None):
+                   phase=0, delta=None, split=True, window=(-1, -1), q_lens=None, block_mask=None, chunk_causal=None,
+                   interval_mask=None):
     """Fused attention backward (include/omh.h).  q, dout: bf16 [B*Lq, H*128]; k, v: bf16 [B*Lk, H*128] (row stride
     free); lse fp32 [B, H, Lq] from ``flash_attn_raw(..., lse=)``; k_lens int32 [B] or None.
     Returns fp32 dq [B*Lq, H*128], dk, dv [B*Lk, H*128] — or, with ``out=(dq, dk, dv)`` bf16 2-D tensors (row stride
@@ -289,8 +330,13 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     ``block_mask``: the forward's block mask (omh_flash_attn_bwd_sparse_d128; requires ``o32``, any ``q_lens``; ValueError
     beside a bounded ``window``): keys no live query sees get dk = dv = 0, live rows that see no key dq = 0.
     ``chunk_causal``: the forward's (chunk, left_chunks, q_offset) (omh_flash_attn_bwd_chunk_d128; requires ``o32``, any
-    ``q_lens``; ValueError beside a bounded ``window`` or a block mask): zero gradients as under a block mask."""
+    ``q_lens``; ValueError beside a bounded ``window`` or a block mask): zero gradients as under a block mask.
+    ``interval_mask``: the forward's ``causal.IntervalMask`` (omh_flash_attn_bwd_interval_d128; requires ``o32``, any
+    ``q_lens``; ValueError beside any of the other three): zero gradients as under a block mask."""
     _dev(q, k, v, dout, lse, k_lens, o32, q_lens)
+    im = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal, device=q.device)
+    if im is not None:
+        assert o32 is not None, "flash_attn_bwd: interval_mask needs the forward's fp32 output (o32=)"
     cc = _chunk_causal(chunk_causal, window, block_mask)
     if cc is not None:
         assert o32 is not None, "flash_attn_bwd: chunk_causal needs the forward's fp32 output (o32=)"
@@ -354,6 +400,11 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
         check(lib.omh_flash_attn_bwd_chunk_d128(C.byref(a), _p(q_lens), C.byref(cc), _stream()),
               "omh_flash_attn_bwd_chunk_d128")
         return dq, dk, dv
+    if im is not None:
+        m = im.c_struct()
+        check(lib.omh_flash_attn_bwd_interval_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
+              "omh_flash_attn_bwd_interval_d128")
+        return dq, dk, dv
     if q_lens is not None:
         check(lib.omh_flash_attn_bwd_varlen_d128(C.byref(a), _p(q_lens), int(window[0]), int(window[1]), _stream()),
               "omh_flash_attn_bwd_varlen_d128")
@@ -375,7 +426,7 @@ class _FlashAttnFunc(torch.autograd.Function):
     omh_flash_attn_bwd_* call backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, k_lens, q_lens, scale, window, block_mask=None, chunk_causal=None):
+    def forward(ctx, q, k, v, k_lens, q_lens, scale, window, block_mask=None, chunk_causal=None, interval_mask=None):
         _dev(q, k, v, k_lens, q_lens)
         B, Lq, H, D = q.shape
         Lk = k.shape[1]
@@ -396,9 +447,10 @@ class _FlashAttnFunc(torch.autograd.Function):
         # pinned to the short-sequence kernel, as the training step pins it (never split: this flag alone)
         flash_attn_raw(_p(q), _p(k), _p(vt), _p(o), _p(k_lens), B, H, Lq, Lk, Lq * d, d, Lk * d, d, d * Lp, Lq * d, d, Lp,
                        scale, lse=_p(lse), o32=_p(o32), flags=ATTN_SHORT_KERNEL, q_lens=_p(q_lens), window=window,
-                       block_mask=block_mask, chunk_causal=chunk_causal)
+                       block_mask=block_mask, chunk_causal=chunk_causal, interval_mask=interval_mask)
         ctx.save_for_backward(q, k, v, o, lse, o32, k_lens, q_lens)
         ctx.scale, ctx.window, ctx.block_mask, ctx.chunk_causal = scale, window, block_mask, chunk_causal
+        ctx.interval_mask = interval_mask
         return o
 
     @staticmethod
@@ -412,15 +464,15 @@ class _FlashAttnFunc(torch.autograd.Function):
                torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device))
         flash_attn_bwd(q.view(B * Lq, d), k.view(B * Lk, d), v.view(B * Lk, d), o.view(B * Lq, d), do.view(B * Lq, d), lse,
                        k_lens, B, H, Lq, Lk, scale=ctx.scale, out=out, o32=o32, window=ctx.window, q_lens=q_lens,
-                       block_mask=ctx.block_mask, chunk_causal=ctx.chunk_causal)
+                       block_mask=ctx.block_mask, chunk_causal=ctx.chunk_causal, interval_mask=ctx.interval_mask)
         need = ctx.needs_input_grad
         return (out[0].view(B, Lq, H, D) if need[0] else None, out[1].view(B, Lk, H, D) if need[1] else None,
-                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None, None, None)
+                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None, None, None, None)
 
 
 def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
                     q_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None, window=(-1, -1),
-                    block_mask=None, chunk_causal=None):
+                    block_mask=None, chunk_causal=None, interval_mask=None):
     """Differentiable attention (a ``torch.autograd.Function``): q [B,Lq,H,128], k, v [B,Lk,H,128] bf16 (V row-major: the
     padded V^T the kernel reads is built here, by the transpose kernel); k_lens / q_lens int32 [B] or None; ``window`` =
     (left, right) as in ``flash_attn``.  Returns [B,Lq,H,128] bf16 — the bits of ``flash_attn`` on the same inputs
@@ -430,15 +482,18 @@ def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: O
     returns gradients only for the inputs that need them.  ``block_mask`` as in ``flash_attn`` (forward and backward on
     the block-list kernels, omh_flash_attn_*_sparse_d128; ValueError beside a bounded ``window``).  ``chunk_causal`` =
     (chunk, left_chunks, q_offset) as in ``flash_attn`` (omh_flash_attn_*_chunk_d128, honouring q_lens / k_lens; ValueError
-    beside a bounded ``window`` or a ``block_mask``)."""
+    beside a bounded ``window`` or a ``block_mask``).  ``interval_mask``: a ``causal.IntervalMask`` as in ``flash_attn``
+    (omh_flash_attn_*_interval_d128, honouring q_lens / k_lens; ValueError beside any of the other three)."""
     window = (int(window[0]) if window[0] >= 0 else -1, int(window[1]) if window[1] >= 0 else -1)
+    if interval_mask is not None:
+        interval_mask = _interval_mask(interval_mask, q.shape[1], k.shape[1], window, block_mask, chunk_causal, device=q.device)
     if chunk_causal is not None:
         _chunk_causal(chunk_causal, window, block_mask)
         chunk_causal = tuple(int(x) for x in chunk_causal)
     if block_mask is not None:
         block_mask = _block_mask(block_mask, q.shape[2], q.shape[1], k.shape[1], window)
     return _FlashAttnFunc.apply(q, k, v, k_lens, q_lens, float(scale if scale is not None else 128 ** -0.5), window,
-                                block_mask, chunk_causal)
+                                block_mask, chunk_causal, interval_mask)
 
 
 def layernorm_modulate_raw(x, y, rows, dim, eps, mul_const, mul0, mul1, mul1_stride, add0, add1, add1_stride,

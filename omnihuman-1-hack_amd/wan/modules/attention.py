@@ -30,8 +30,14 @@ __all__ = ["flash_attention", "attention"]
 
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None,
                     causal=False, window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None,
-                    chunk_causal=None, block_mask=None):
+                    chunk_causal=None, interval_mask=None, block_mask=None):
     """q [B, Lq, N, 128], k/v [B, Lk, N, 128]; returns [B, Lq, N, 128] in q's dtype.
+
+    ``interval_mask`` (not in the reference): a ``causal.IntervalMask`` — query i sees key j < k_lens[b] iff the mask's
+    bool matrix holds True at [i // group, j // group] (at most two runs of True per row and per column: teacher forcing,
+    the staircase, sink + window); absolute positions; rows that see no key are zero.  Differentiable through this wrapper
+    like the unmasked call.  Together with ``causal``, a bounded ``window_size``, ``block_mask`` or ``chunk_causal`` it
+    raises ValueError.
 
     ``chunk_causal`` = (chunk, left_chunks, q_offset) (not in the reference): the chunk-causal staircase of
     ``ops.flash_attn(chunk_causal=)`` — query i, at position q_offset + i, sees key j < k_lens[b] iff j // chunk <=
@@ -81,6 +87,11 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         chunk_causal = tuple(int(x) for x in chunk_causal)
         if len(chunk_causal) != 3 or chunk_causal[0] <= 0 or chunk_causal[2] < 0:
             raise ValueError("flash_attention: chunk_causal = (chunk >= 1, left_chunks, q_offset >= 0) expected")
+    if interval_mask is not None:
+        if window != (-1, -1) or block_mask is not None or chunk_causal is not None:
+            raise ValueError("flash_attention: interval_mask excludes causal / a bounded window_size / block_mask / chunk_causal")
+        if not hasattr(interval_mask, "q_iv"):
+            raise ValueError("flash_attention: interval_mask must be a causal.IntervalMask")
     if window != (-1, -1) and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         raise NotImplementedError("flash_attention on gfx950: causal / window_size are forward-only through this wrapper; "
                                   "the differentiable band is ops.flash_attn_func(window=)")
@@ -98,7 +109,8 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
                                                 (softmax_scale if softmax_scale is not None else D ** -0.5) * math.log2(math.e))
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         o = ops.flash_attn_func(q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), kl, ql,
-                                scale=softmax_scale, window=window, block_mask=block_mask, chunk_causal=chunk_causal)
+                                scale=softmax_scale, window=window, block_mask=block_mask, chunk_causal=chunk_causal,
+                                interval_mask=interval_mask)
         return o.type(out_dtype)
     qb = q.to(torch.bfloat16).contiguous()
     kb = k.to(torch.bfloat16).contiguous()
@@ -108,13 +120,14 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     # q_lens (attention.py:55-60,79): the reference cuts the queries past q_lens[b] out of the packed batch — and can only
     # un-flatten the result when every q_lens[b] == Lq (attention.py:110); here those rows come back as zeros
     o = ops.flash_attn(qb, kb, vt, kl, scale=softmax_scale, q_lens=ql, window=window, block_mask=block_mask,
-                       chunk_causal=chunk_causal)
+                       chunk_causal=chunk_causal, interval_mask=interval_mask)
     return o.type(out_dtype)
 
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,
               window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, fa_version=None,
-              chunk_causal=None, block_mask=None):
+              chunk_causal=None, interval_mask=None, block_mask=None):
     """attention.py:133-179 — same kernel; the reference's SDPA fallback is not needed here."""
     return flash_attention(q, k, v, q_lens, k_lens, dropout_p, softmax_scale, q_scale, causal, window_size,
-                           deterministic, dtype, fa_version, block_mask=block_mask, chunk_causal=chunk_causal)
+                           deterministic, dtype, fa_version, block_mask=block_mask, chunk_causal=chunk_causal,
+                           interval_mask=interval_mask)

@@ -176,7 +176,10 @@ class _FwdCtx:
                  "Lc", "n_img", "seq_lens_host", "ctx_lens_host", "kv", "split_k",
                  # chunk: (tokens per chunk, left_chunks, 0) under WanModel.set_causal_chunks, else None / unset;
                  # cache, cache_layer, cache_lo: WanModel.forward_chunk (a causal.KVCache, the running block, first key)
-                 "chunk", "cache", "cache_layer", "cache_lo")
+                 "chunk", "cache", "cache_layer", "cache_lo",
+                 # rpb: rows of the sequence that share one row of e0 (seq_len, or h * w with a per-frame t);
+                 # interval: a causal.IntervalMask every self-attention runs under (forward_teacher_forcing), else unset
+                 "rpb", "interval")
 
 
 class ContextState:
@@ -302,6 +305,10 @@ class WanSelfAttention(nn.Module):
         if chunk is not None and (bmask is not None or self._block_policy is not None or self.window_size[0] >= 0
                                   or self.window_size[1] >= 0):
             raise ValueError("causal chunks exclude a block mask, a block policy and a bounded window_size")
+        ivl = getattr(fc, "interval", None)                # WanModel.forward_teacher_forcing: the interval-mask kernels
+        if ivl is not None and (bmask is not None or self._block_policy is not None or self.window_size[0] >= 0
+                                or self.window_size[1] >= 0):
+            raise ValueError("teacher forcing excludes a block mask, a block policy and a bounded window_size")
         # q|k projection kept in bf16 (fp32 accumulate): the normalisation statistics are taken in fp32 from
         # it; measured effect on the 30-layer output < 1e-3 relative RMS, and it halves this step's traffic
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
@@ -338,7 +345,7 @@ class WanSelfAttention(nn.Module):
         nmax = None
         # (a block mask runs the short-sequence kernel over its lists: no long-sequence stream, so no bound either)
         # (nor does the staircase: the short-sequence kernel too)
-        if chunk is None and bmask is None and self._block_policy is None and D == 128 and d <= 5120 and \
+        if chunk is None and ivl is None and bmask is None and self._block_policy is None and D == 128 and d <= 5120 and \
                 ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
             nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
         self.last_qk_norm2_max = nmax                                    # (read by tools/attn_bound_values.py)
@@ -361,7 +368,8 @@ class WanSelfAttention(nn.Module):
         # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
                            d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1, window=window,
-                           qk_norm2_max=ptr(nmax) if nmax is not None else None, block_mask=bmask, chunk_causal=chunk)
+                           qk_norm2_max=ptr(nmax) if nmax is not None else None, block_mask=bmask, chunk_causal=chunk,
+                           interval_mask=ivl)
         return o
 
     def _attend_cached(self, h, fc: "_FwdCtx"):
@@ -537,11 +545,12 @@ class WanAttentionBlock(nn.Module):
             mod = mod.float()
         e0 = fc.e0
         xp, six_d = ptr(x), 6 * d
+        rpb = getattr(fc, "rpb", None) or S                # rows per row of e0: the sequence, or a frame (per-frame t)
 
         def ln_mod(shift_i, scale_i):
             h = torch.empty(R, d, dtype=torch.bfloat16, device=x.device)
             ops.layernorm_modulate_raw(xp, ptr(h), R, d, self.eps, 1.0, ptr(mod, scale_i * d), ptr(e0, scale_i * d),
-                                       six_d, ptr(mod, shift_i * d), ptr(e0, shift_i * d), six_d, S)
+                                       six_d, ptr(mod, shift_i * d), ptr(e0, shift_i * d), six_d, rpb)
             return h
 
         def resid(a, w, b, gate_i=None):
@@ -554,7 +563,7 @@ class WanAttentionBlock(nn.Module):
                 # (split_k: at one or two [16,1,60,104] clips the FFN-down contraction, K = ffn_dim over 56 / 104 tiles,
                 # runs in slices — ABI v9; nothing is split at the sampling sizes)
                 ops.gemm_raw(ptr(a), ptr(w), xp, M, d, K, K, K, d, EPI_RESID, bias=ptr(b), bias_mode=BIAS_N,
-                             gate0=ptr(mod, gate_i * d), gate1=ptr(e0, gate_i * d), gate1_stride=six_d, gate_rows=S,
+                             gate0=ptr(mod, gate_i * d), gate1=ptr(e0, gate_i * d), gate1_stride=six_d, gate_rows=rpb,
                              gate_const=0.0, split_k=fc.split_k)
 
         # ---- self-attention: x += o(attn(LN(x)(1+e1)+e0)) * e2        model.py:292-296
@@ -606,8 +615,9 @@ class Head(nn.Module):
         self.modulation = nn.Parameter(torch.randn(1, 2, dim) / dim ** 0.5)
         self._packed = _Packed()
 
-    def forward(self, x, e):
-        """x fp32 [B, L, C], e fp32 [B, C] -> fp32 [B, L, prod(patch)*out_dim]."""
+    def forward(self, x, e, rows_per_batch=None):
+        """x fp32 [B, L, C], e fp32 [B, C] -> fp32 [B, L, prod(patch)*out_dim].  ``rows_per_batch``: rows of x that share
+        one row of e (default L; h * w with a per-frame t, e then [B * L / (h w), C])."""
         assert e.dtype == torch.float32
         B, S, d = x.shape
         R = B * S
@@ -616,7 +626,7 @@ class Head(nn.Module):
         mod = self.modulation.detach().float()
         h = torch.empty(R, d, dtype=torch.bfloat16, device=x.device)
         ops.layernorm_modulate_raw(ptr(x), ptr(h), R, d, self.eps, 1.0, ptr(mod, d), ptr(e), d, ptr(mod, 0), ptr(e), d,
-                                   S)
+                                   rows_per_batch or S)
         w, b = self._packed.get("head", (self.head.weight, self.head.bias), lambda: (
             _bf16(self.head.weight), self.head.bias.detach().float().contiguous()))
         return ops.gemm(h, w, bias=b, epilogue=EPI_F32).view(B, S, -1)
@@ -929,6 +939,86 @@ class WanModel(nn.Module):
             hit = tabs[1][key] = (c2, s2)
         return hit
 
+    def _rope_repeated(self, device, frames):
+        """The cos / sin tables with rows [frames, 2 frames) of the FRAME columns repeating rows [0, frames): frame
+        frames + f of a doubled clip rotates like frame f; the h / w columns stay.  Cached per frame count."""
+        cos, sin = self._rope(device)
+        key = (str(device), int(frames))
+        tabs = getattr(self, "_rope_repeat_cache", None)
+        if tabs is None or tabs[0] is not cos:
+            tabs = self._rope_repeat_cache = (cos, {})
+        hit = tabs[1].get(key)
+        if hit is None:
+            if len(tabs[1]) > 64:
+                tabs[1].clear()
+            d = self.dim // self.num_heads
+            nf = (d - 4 * (d // 6)) // 2                                     # pair-columns of the frame axis
+            c2, s2 = cos.clone(), sin.clone()
+            c2[frames:2 * frames, :nf] = cos[:frames, :nf]
+            s2[frames:2 * frames, :nf] = sin[:frames, :nf]
+            hit = tabs[1][key] = (c2, s2)
+        return hit
+
+    def forward_teacher_forcing(self, x_clean, x_noisy, t, context, context_t=0.0, clip_fea=None, y=None,
+                                extra_conditions=None):
+        """All chunks of a clip in one pass, as the rollout sees them (teacher forcing).  Needs ``set_causal_chunks(fpc,
+        W)``.  ``x_clean`` / ``x_noisy``: lists of [C_in, F, H, W], every clip of one shape, F a multiple of fpc;
+        ``t``: [B, F / fpc], one timestep per noisy chunk.  The sequence of a sample is [clean tokens | noisy tokens]
+        (2 S tokens): the clean frames are modulated at ``context_t`` and the frames of noisy chunk I at ``t[:, I]``
+        (per-frame timesteps), q and k of both halves rotate with the SAME frame positions, and every self-attention
+        runs under ``causal.IntervalMask(causal.teacher_forcing_groups(F / fpc, W), fpc h w)``: a clean chunk sees the
+        clean chunks up to itself, noisy chunk I the clean chunks before it and itself — what ``forward_chunk`` attends
+        to at chunk I (both cut to W chunks back).  Cross-attention and the FFN are unchanged, ``y`` goes to both
+        halves, the head runs on the noisy rows only.  Returns the list of fp32 [C_out, F, H, W] for the noisy half.
+        ValueError without causal chunks, for a bounded ``window_size``, a block mask or policy, clips of different
+        shapes, F no multiple of fpc, h w no multiple of 8 and a ``t`` of another shape."""
+        cc = getattr(self, "_causal_chunks", None)
+        if cc is None:
+            raise ValueError("forward_teacher_forcing: set_causal_chunks(frames_per_chunk, left_chunks) first")
+        self._causal_check("forward_teacher_forcing")
+        x_clean, x_noisy = list(x_clean), list(x_noisy)
+        shapes = {tuple(u.shape) for u in x_clean} | {tuple(u.shape) for u in x_noisy}
+        if len(x_clean) != len(x_noisy) or len(shapes) != 1:
+            raise ValueError("forward_teacher_forcing: clean and noisy latents of ONE shape per clip are expected")
+        pt, ph, pw = self.patch_size
+        F, h, w = x_noisy[0].shape[1] // pt, x_noisy[0].shape[2] // ph, x_noisy[0].shape[3] // pw
+        fpc, B = cc[0], len(x_noisy)
+        if F % fpc:
+            raise ValueError(f"forward_teacher_forcing: {F} latent frames are no multiple of frames_per_chunk = {fpc}")
+        if not isinstance(t, torch.Tensor) or t.shape != (B, F // fpc):
+            raise ValueError(f"forward_teacher_forcing: t of shape [{B}, {F // fpc}] expected (one timestep per noisy chunk)")
+        if (h * w) % 8:
+            raise ValueError(f"forward_teacher_forcing: {h * w} tokens per frame; a multiple of 8 is needed")
+        if 2 * F > self.freqs.shape[0]:
+            raise ValueError(f"forward_teacher_forcing: 2 x {F} frames leave the rotary table ({self.freqs.shape[0]} rows)")
+        device = self.patch_embedding.weight.device
+        if device.type != "cuda":
+            raise ops.OmhError("WanModel.forward_teacher_forcing runs on the MI355X only (no CPU fallback): move the "
+                               "model to a GPU device")
+        from ... import causal as _causal
+        key = (F // fpc, cc[1], fpc * h * w, str(device))
+        masks = self.__dict__.setdefault("_tf_masks", {})
+        if key not in masks:
+            if len(masks) > 64:
+                masks.clear()
+            masks[key] = _causal.IntervalMask(_causal.teacher_forcing_groups(F // fpc, cc[1]), fpc * h * w, device)
+        x = [torch.cat([c.to(n.device), n], dim=1) for c, n in zip(x_clean, x_noisy)]
+        if y is not None:
+            y = [torch.cat([v, v], dim=1) for v in y]
+        t = t.to(device)
+        if not t.is_floating_point():
+            t = t.float()
+        t_frames = torch.cat([torch.full((B, F), float(context_t), dtype=t.dtype, device=device),
+                              t.repeat_interleave(fpc, dim=1)], dim=1)
+        self._tf_state = (masks[key], self._rope_repeated(device, F))
+        try:
+            out = self.forward(x, t_frames, context, 2 * F * h * w, clip_fea, y, extra_conditions)
+        finally:
+            self._tf_state = None
+        # (the inference blocks ran the head on the noisy rows only; the training forward runs it on every row, and the
+        # clean half's output is cut off here: no gradient enters through it)
+        return [o if o.shape[1] == F * pt else o[:, F * pt:] for o in out]
+
     def forward_chunk(self, x, t, context, cache, frame_offset=None, commit=True, clip_fea=None, y=None):
         """One chunk of a clip against the keys and values kept from the chunks before it (the rollout of the
         frame-causal model).  ``x``: the latents [C_in, f, H, W] of ONE chunk per sample, all of one shape (the last chunk
@@ -955,6 +1045,8 @@ class WanModel(nn.Module):
             return self._forward_chunk(list(x), t, context, cache, frame_offset, commit, clip_fea, y)
 
     def _forward_chunk(self, x, t, context, cache, frame_offset, commit, clip_fea, y):
+        if t.dim() != 1:
+            raise ValueError(f"forward_chunk: t of shape {tuple(t.shape)}; one timestep per sample, [B], is expected")
         if len({tuple(u.shape) for u in x}) != 1:
             raise ValueError("forward_chunk: the chunks of a batch must have one shape")
         if cache.model_id != id(self) or cache.batch != len(x):
@@ -1073,13 +1165,17 @@ class WanModel(nn.Module):
                 xs[b, lens[b]:].zero_()                 # only the padding rows need the fill; the GEMM wrote the rest
         # ---- time embedding (fp32)                                              model.py:526-528
         t = t.to(device=device)
+        rpb = seq_len
+        if t.dim() == 2:                                                    # per-frame timesteps: one row of e0 per frame
+            t, rpb = self._per_frame_t(t, grids, seq_len)
         te0, te2, tp1 = self.time_embedding[0], self.time_embedding[2], self.time_projection[1]
         sin = ops.sinusoidal_embedding(t, self.freq_dim)
         e = ops.dense_f32(ops.dense_f32(sin, te0.weight.detach().float(), te0.bias.detach().float(), 0, 1),
                           te2.weight.detach().float(), te2.bias.detach().float(), 0, 0)
-        e0 = ops.dense_f32(e, tp1.weight.detach().float(), tp1.bias.detach().float(), 1, 0).view(B, 6, d)
+        e0 = ops.dense_f32(e, tp1.weight.detach().float(), tp1.bias.detach().float(), 1, 0).view(-1, 6, d)
         fc = _FwdCtx()
         fc.B, fc.S, fc.dim = B, seq_len, d
+        fc.rpb = rpb
         fc.split_k = not getattr(self, "batch_invariant", False)
         fc.e0 = e0.contiguous()
         fc.seq_lens32 = _dev_ints(lens, torch.int32, device)
@@ -1087,8 +1183,34 @@ class WanModel(nn.Module):
         fc.rope_cos, fc.rope_sin = self._rope(device)
         fc.seq_lens_host = list(lens)                                       # host copies: no device sync later
         fc.chunk = self._causal_rule(grids)
+        tf = getattr(self, "_tf_state", None)                               # forward_teacher_forcing: its mask and rotary table
+        if tf is not None:
+            fc.chunk, fc.interval = None, tf[0]
+            fc.rope_cos, fc.rope_sin = tf[1]
         ctx_lens = self._attach_context(fc, context, clip_fea, extra_conditions)
         return xs, e, fc, grids, lens, ctx_lens
+
+    def _per_frame_t(self, t, grids, seq_len):
+        """``t`` [B, F] (F: the latent frames of the longest clip) -> (the timesteps of the B * G frames of the padded
+        sequences, flat; h * w), G = seq_len / (h w); frames past F take the last frame's t.  Plain torch: a gradient
+        w.r.t. ``t`` flows back to [B, F].  ValueError when the clips do not share h, w, when seq_len is no multiple of
+        h w, when h w is no multiple of 8, and when F is not the frame count of the longest clip."""
+        hw = {(g[1], g[2]) for g in grids}
+        if len(hw) != 1:
+            raise ValueError(f"per-frame t: the clips of a batch must share h, w, got {sorted(hw)}")
+        h, w = next(iter(hw))
+        tpf = h * w
+        if tpf % 8:
+            raise ValueError(f"per-frame t: {tpf} tokens per frame; a multiple of 8 is needed")
+        if seq_len % tpf:
+            raise ValueError(f"per-frame t: seq_len = {seq_len} is no multiple of the {tpf} tokens of a frame")
+        G, F = seq_len // tpf, max(g[0] for g in grids)
+        if t.shape != (len(grids), F):
+            raise ValueError(f"per-frame t: shape {tuple(t.shape)}, [{len(grids)}, {F}] expected (one timestep per latent "
+                             "frame of the longest clip)")
+        if G > F:
+            t = torch.cat([t, t[:, -1:].expand(-1, G - F)], dim=1)
+        return t.reshape(-1), tpf
 
     def _attach_context(self, fc, context, clip_fea=None, extra_conditions=None):
         """The context-dependent fields of a forward's shared state: text (+ image) embedding, model.py:531-537."""
@@ -1176,7 +1298,12 @@ class WanModel(nn.Module):
         for i, block in enumerate(self.blocks):
             # module __call__ so forward hooks on blocks fire (seaweed_apt/model.py:150-155)
             xs = block(xs, fc.e0, seq_lens, grid_sizes, freqs, fc.ctx, context_lens, block_idx=i, _fc=fc)
-        out = self.head(xs, e)                                   # fp32 [B, seq_len, prod(patch)*out_dim]
+        if getattr(self, "_tf_state", None) is not None:         # teacher forcing: the head runs on the noisy half only
+            half = seq_len // 2
+            xs = xs[:, half:].contiguous()
+            e = e.view(len(grids), -1, e.shape[-1])[:, half // fc.rpb:].reshape(-1, e.shape[-1])
+            grids = [(g[0] // 2, g[1], g[2]) for g in grids]
+        out = self.head(xs, e, fc.rpb)                           # fp32 [B, seq_len, prod(patch)*out_dim]
         return self.unpatchify(out, grid_sizes, _grids=grids)
 
     def forward_cfg_pair(self, x, t, context, context_null, seq_len, clip_fea=None, y=None):
@@ -1200,6 +1327,8 @@ class WanModel(nn.Module):
             return self._forward_cfg_pair(x, t, context, context_null, seq_len, clip_fea, y)
 
     def _forward_cfg_pair(self, x, t, context, context_null, seq_len, clip_fea, y):
+        if t.dim() != 1:
+            raise ValueError(f"forward_cfg_pair: t of shape {tuple(t.shape)}; one timestep per sample, [B], is expected")
         xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, seq_len, clip_fea, y)
         seq_lens = _dev_ints(lens, torch.long, xs.device)
         grid_sizes = _dev_ints(grids, torch.long, xs.device)

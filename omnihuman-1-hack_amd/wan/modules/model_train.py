@@ -305,19 +305,21 @@ _ALWAYS_COPY_DX = os.environ.get("OMH_BLOCK_DX_COPY", "0") == "1"
 
 
 def _attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, out, o32, q_prescaled, window=(-1, -1), block_mask=None,
-              chunk_causal=None):
+              chunk_causal=None, interval_mask=None):
     """ops.flash_attn_bwd on the block's pre-scaled q, bf16 gradients into ``out`` — as one call, or (OMH_ATTN_BWD_SPLIT)
     as delta -> {dQ on this stream, dK / dV on a second one} -> join.  ``window``: the self-attention's band (the
     band kernels; o32 required).  ``block_mask``: the self-attention's block mask (the block-list kernels; o32 required).
-    ``chunk_causal``: the self-attention's staircase (WanModel.set_causal_chunks; the chunk kernels; o32 required)."""
+    ``chunk_causal``: the self-attention's staircase (WanModel.set_causal_chunks; the chunk kernels; o32 required).
+    ``interval_mask``: the self-attention's interval mask (WanModel.forward_teacher_forcing; o32 required)."""
     split = _ATTN_SPLIT == "1" or (_ATTN_SPLIT == "auto" and B * N * ((Lq + 127) // 128) > 512)
     if not (split and o32 is not None):
         return ops.flash_attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, q_prescaled=q_prescaled, out=out, o32=o32,
-                                  window=window, block_mask=block_mask, chunk_causal=chunk_causal)
+                                  window=window, block_mask=block_mask, chunk_causal=chunk_causal,
+                                  interval_mask=interval_mask)
     dev = q.device
     delta = torch.empty(B, N, Lq, dtype=torch.float32, device=dev)
     kw = dict(q_prescaled=q_prescaled, out=out, o32=o32, delta=delta, window=window, block_mask=block_mask,
-              chunk_causal=chunk_causal)
+              chunk_causal=chunk_causal, interval_mask=interval_mask)
     ops.flash_attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, phase=1, **kw)
     main = torch.cuda.current_stream(dev)
     s2 = _side2.get(dev)
@@ -698,6 +700,7 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
         mod = mod.float()
     mod = mod.contiguous()
     e0 = fc.e0
+    rpb = getattr(fc, "rpb", None) or Sq                 # rows per row of e0: the sequence, or a frame (per-frame t)
     six = 6 * d
     i2v = hasattr(ca, "k_img")
     n_img = 257 if i2v else 0
@@ -723,7 +726,7 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
     def ln_mod(xin, shift_i, scale_i):
         h = bf(R, d)
         ops.layernorm_modulate_raw(ptr(xin), ptr(h), R, d, blk.eps, 1.0, ptr(mod, scale_i * d), ptr(e0, scale_i * d), six,
-                                   ptr(mod, shift_i * d), ptr(e0, shift_i * d), six, Sq)
+                                   ptr(mod, shift_i * d), ptr(e0, shift_i * d), six, rpb)
         return h
 
     def resid(xin, a, w, b, gate_i, want_y, xout=None):
@@ -739,7 +742,7 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
         else:
             ops.gemm_raw(ptr(a), ptr(w), ptr(xo), M, d, K, a.stride(0), w.stride(0), d, EPI_RESID, bias=ptr(b),
                          bias_mode=BIAS_N, gate0=ptr(mod, gate_i * d), gate1=ptr(e0, gate_i * d), gate1_stride=six,
-                         gate_rows=Sq, gate_const=0.0, split_k=fc.split_k, **kw)      # (same slices as the inference block: model.py)
+                         gate_rows=rpb, gate_const=0.0, split_k=fc.split_k, **kw)      # (same slices as the inference block: model.py)
         return xo, y
 
     # ---- self-attention: x1 = x0 + o(attn(LN(x0)(1+e1)+e0)) * e2                                    model.py:292-296
@@ -775,10 +778,15 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
         raise ValueError("causal chunks exclude a block mask, a block policy and a bounded window_size")
     if need and not _ATTN_BWD2 and chunk is not None:
         raise NotImplementedError("OMH_ATTN_BWD=v1 has no chunk-causal backward: the mask needs the default kernels")
+    ivl = getattr(fc, "interval", None)                     # WanModel.forward_teacher_forcing: the interval-mask kernels
+    if ivl is not None and (bmask is not None or win[0] >= 0 or win[1] >= 0):
+        raise ValueError("teacher forcing excludes a block mask, a block policy and a bounded window_size")
+    if need and not _ATTN_BWD2 and ivl is not None:
+        raise NotImplementedError("OMH_ATTN_BWD=v1 has no interval-mask backward: the mask needs the default kernels")
     ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, Sq, Sq, Sq * d, d, Sq * d, d, d * Sp,
                        Sq * d, d, Sp, D ** -0.5, lse=ptr(lse_sa) if need else None, q_prescaled=1,
                        o32=ptr(o32_sa) if o32_sa is not None else None, flags=_ATTN_FLAGS, window=win, block_mask=bmask,
-                       chunk_causal=chunk)
+                       chunk_causal=chunk, interval_mask=ivl)
     x1, y1 = resid(x0, o, P["wo"], sa.o.bias.detach(), 2, True)
     S.update(h1=h1, qk=qk, q=q, k=k, vt=vt, o=o, lse_sa=lse_sa, y1=y1, x1=x1, o32_sa=o32_sa, bmask=bmask)
     # ---- cross-attention: x2 = x1 + o(attn(norm3(x1), context))                                     model.py:313
@@ -843,6 +851,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     eps = blk.eps
     mod = blk.modulation.detach().float().contiguous()
     e0 = fc.e0
+    rpb = getattr(fc, "rpb", None) or Sq                 # rows per row of e0: the sequence, or a frame (per-frame t)
     six = 6 * d
     i2v = hasattr(ca, "k_img")
     n_img = 257 if i2v else 0
@@ -850,9 +859,10 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     Lc = fc.Lc
     Lt = Lc - n_img
     bf = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
-    arena = _ZeroArena(B * six + 2 * six + 20 * d + 2 * f + 4096, dev)
+    nE = e0.shape[0]                                                  # rows of e0: B, or B * frames with a per-frame t
+    arena = _ZeroArena(nE * six + 2 * six + 20 * d + 2 * f + 4096, dev)
     wg = _WgradGroup(dev)
-    d_eb = arena.take(B, 6, d)                                        # grads of e = modulation + e0
+    d_eb = arena.take(nE, 6, d)                                       # grads of e = modulation + e0
     g = {}
     tgt = tgt or {}
     slots = slots or {}                                               # fresh weight gradients written into reducer buckets
@@ -966,7 +976,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
                 kw = dict(dy_next=dy_next, y_next=y, gate_const=0.0, gate0=ptr(mod, gi * d), gate1=ptr(e0, gi * d),
                           gate1_stride=six, dgate=ptr(d_eb, gi * d), dgate_stride=six)
         ops.layernorm_modulate_bwd2(xin, dh, dx, R, d, eps, 1.0, ptr(mod, scale_i * d), ptr(e0, scale_i * d), six,
-                                    ptr(d_eb, scale_i * d), ptr(d_eb, shift_i * d), six, Sq, defer=deferred, **kw)
+                                    ptr(d_eb, scale_i * d), ptr(d_eb, shift_i * d), six, rpb, defer=deferred, **kw)
         return dy_next
 
     def resid_bwd(y, gate_i):
@@ -975,7 +985,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
             ops.gated_residual_bwd_raw(ptr(dx), None, ptr(dy), None, 0, R, d, 1.0, None, None, 0, Sq)
         else:
             ops.gated_residual_bwd_raw(ptr(dx), ptr(y), ptr(dy), ptr(d_eb, gate_i * d), six, R, d, 0.0,
-                                       ptr(mod, gate_i * d), ptr(e0, gate_i * d), six, Sq)
+                                       ptr(mod, gate_i * d), ptr(e0, gate_i * d), six, rpb)
         return dy
 
     def rms_bwd(x, x_bf16, ldx, dy, lddy, rows, weights, norm_on, rope, names, mod_, n_seg=1, seg_x=0, seg_dy=0, defer=True):
@@ -1008,7 +1018,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
         # the reference's quirk ran this block's FFN without a graph (model.py:317-324): nothing flows back through y3, only
         # its gate gets a gradient (dx . y3) — in the same pass over dx that makes the cross-attention branch's dy2 = bf16(dx)
         dy2 = bf(R, d)
-        ops.gated_residual_bwd_raw(ptr(dx), ptr(S["y3"]), ptr(dy2), ptr(d_eb, 5 * d), six, R, d, 1.0, None, None, 0, Sq)
+        ops.gated_residual_bwd_raw(ptr(dx), ptr(S["y3"]), ptr(dy2), ptr(d_eb, 5 * d), six, R, d, 1.0, None, None, 0, rpb)
     oc, qc, kc = S["oc"], S["qc"], S["kc"]
     wgrad(dy2, oc, ["cross_attn.o.weight"]), bgrad(dy2, ["cross_attn.o.bias"])
     doc = _dgrad(dy2, P["wo_cT"], epilogue=EPI_BF16)
@@ -1073,7 +1083,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
         # ---- self-attention branch: x1 = x0 + y1 * g2  (dy1 = bf16(dx * g2) and the gate's gradient: same pass)
         dw3, db3 = acc1("norm3.weight", d), acc1("norm3.bias", d)
         dy1 = bf(R, d)
-        ops.layernorm_modulate_bwd2(x1, dh3, dx, R, d, blk.norm3.eps, 0.0, ptr(S["w3"]), None, 0, ptr(dw3), ptr(db3), 0, Sq,
+        ops.layernorm_modulate_bwd2(x1, dh3, dx, R, d, blk.norm3.eps, 0.0, ptr(S["w3"]), None, 0, ptr(dw3), ptr(db3), 0, rpb,
                                     dy_next=dy1, y_next=S["y1"], gate_const=0.0, gate0=ptr(mod, 2 * d), gate1=ptr(e0, 2 * d),
                                     gate1_stride=six, dgate=ptr(d_eb, 2 * d), dgate_stride=six, defer=deferred)
         g["norm3.weight"], g["norm3.bias"] = dw3, db3
@@ -1094,7 +1104,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     dqkv = bf(R, 3 * d)                                               # dq | dk | dv, one buffer
     _attn_bwd(q, k, v, o, do, S["lse_sa"], fc.seq_lens32, B, N, Sq, Sq, D ** -0.5,
               (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, tuple(sa.window_size), S["bmask"],
-              getattr(fc, "chunk", None))
+              getattr(fc, "chunk", None), getattr(fc, "interval", None))
     qk = S["qk"]
     rms_bwd(ptr(qk), True, 2 * d, ptr(dqkv), 3 * d, R, [sa._norm_w("norm_q"), sa._norm_w("norm_k")], sa.qk_norm, True,
             ["self_attn.norm_q.weight", "self_attn.norm_k.weight"], sa, n_seg=2, seg_x=d, seg_dy=d)   # q and k: one launch
@@ -1107,9 +1117,9 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     if deferred:                                                     # d_eb and the gains are complete behind this launch
         ops.partial_colsum_multi(deferred)
     dmod = acc1("modulation", six)
-    ops.colsum_accum(d_eb.view(B, six), dmod)
+    ops.colsum_accum(d_eb.view(nE, six), dmod)
     g["modulation"] = dmod
-    ops.colsum_accum(d_eb.view(1, B * six), st.d_e0.view(B * six))      # d_e0 += d_eb
+    ops.colsum_accum(d_eb.view(1, nE * six), st.d_e0.view(nE * six))    # d_e0 += d_eb
     wg.launch()
     if _SIDE_BIAS:                                                   # the bias gradients' column sums: second stream too
         _on_side(dev, arena.flush, [dy_ for dy_, _ in arena.pending] + [arena.buf])
@@ -1287,7 +1297,7 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model, st, grids, *params):
         with torch.no_grad():
-            out = model.head(x.detach(), st.e)
+            out = model.head(x.detach(), st.e, getattr(st.fc, "rpb", None))
             outs = model.unpatchify(out, None, _grids=grids)
         ctx.save_for_backward(x.detach())
         ctx.model, ctx.st, ctx.grids = model, st, grids
@@ -1313,8 +1323,9 @@ class _HeadFn(torch.autograd.Function):
                 n = grd[0] * grd[1] * grd[2]
                 dtok[b * S:b * S + n].copy_(ops.unpatchify_bwd(gb.contiguous().float(), grd, model.patch_size))
             hh = torch.empty(R, d, dtype=torch.bfloat16, device=dev)
+            rpb, nE = getattr(st.fc, "rpb", None) or S, e.shape[0]  # rows per row of e (a frame with a per-frame t)
             ops.layernorm_modulate_raw(ptr(x), ptr(hh), R, d, head.eps, 1.0, ptr(mod, d), ptr(e), d, ptr(mod, 0),
-                                       ptr(e), d, S)
+                                       ptr(e), d, rpb)
             w, _ = head._packed.get("head", (head.head.weight, head.head.bias), lambda: (
                 ops.cast_bf16(head.head.weight.detach().float().contiguous()),
                 head.head.bias.detach().float().contiguous()))
@@ -1323,13 +1334,16 @@ class _HeadFn(torch.autograd.Function):
             gb_ = _bgrad(dtok) if head.head.bias.requires_grad else None
             dhh = _dgrad(dtok, _wT(head, "head", w))
             dx = torch.zeros(R, d, dtype=torch.float32, device=dev)
-            d_hb = torch.zeros(B, 2, d, dtype=torch.float32, device=dev)
+            d_hb = torch.zeros(nE, 2, d, dtype=torch.float32, device=dev)
             ops.layernorm_modulate_bwd2(x, dhh, dx, R, d, head.eps, 1.0, ptr(mod, d), ptr(e), d,
-                                        ptr(d_hb, d), ptr(d_hb, 0), 2 * d, S)
+                                        ptr(d_hb, d), ptr(d_hb, 0), 2 * d, rpb)
             dmod = torch.zeros(2 * d, dtype=torch.float32, device=dev)
-            ops.colsum_accum(d_hb.view(B, 2 * d), dmod)
-            for b in range(B):                       # e enters both the scale and the shift (model.py:357-358)
-                ops.colsum_accum(d_hb[b], st.d_e[b])
+            ops.colsum_accum(d_hb.view(nE, 2 * d), dmod)
+            if nE == B:
+                for b in range(B):                   # e enters both the scale and the shift (model.py:357-358)
+                    ops.colsum_accum(d_hb[b], st.d_e[b])
+            else:                                    # per-frame t: many rows, one torch add instead of a launch per row
+                st.d_e += d_hb.sum(1)
         grads = {"modulation": dmod.view(1, 2, d), "head.weight": gw, "head.bias": gb_}
         out = []
         for n, p in head.named_parameters():
@@ -1434,8 +1448,9 @@ class _EmbedFn(torch.autograd.Function):
         st.fc, st.e, st.grids, st.lens = fc, e, grids, lens
         B, d = fc.B, fc.dim
         dev = xs.device
-        st.d_e0 = torch.zeros(B, 6, d, dtype=torch.float32, device=dev)
-        st.d_e = torch.zeros(B, d, dtype=torch.float32, device=dev)
+        nE = e.shape[0]                                               # B, or B * frames with a per-frame t
+        st.d_e0 = torch.zeros(nE, 6, d, dtype=torch.float32, device=dev)
+        st.d_e = torch.zeros(nE, d, dtype=torch.float32, device=dev)
         st.d_ctx = torch.zeros(B, fc.Lc, d, dtype=torch.float32, device=dev)
         ctx.model, ctx.st = model, st
         ctx.inputs = (x_list, t, context, seq_len, y, clip_fea)
@@ -1517,19 +1532,26 @@ class _EmbedFn(torch.autograd.Function):
                 te0, te2, tp1 = model.time_embedding[0], model.time_embedding[2], model.time_projection[1]
                 W0, W2, Wp = (m.weight.detach().float().contiguous() for m in (te0, te2, tp1))
                 t_dev = t.to(dev)
+                if t.dim() == 2:                                     # per-frame t: the rows _embed made of it
+                    t_dev = model._per_frame_t(t_dev, st.grids, seq_len)[0].contiguous()
+                nE = t_dev.numel()
                 sin = ops.sinusoidal_embedding(t_dev, model.freq_dim)
                 z0 = ops.dense_f32(sin, W0, te0.bias.detach().float(), 0, 0)
                 e = st.e
                 dWp, dbp = torch.zeros_like(Wp), torch.zeros(Wp.shape[0], dtype=torch.float32, device=dev)
-                ops.dense_f32_bwd(e, Wp, st.d_e0.view(B, 6 * d), dW=dWp, db=dbp, dx=st.d_e, dx_accumulate=True, act_in=1)
+                ops.dense_f32_bwd(e, Wp, st.d_e0.view(nE, 6 * d), dW=dWp, db=dbp, dx=st.d_e, dx_accumulate=True, act_in=1)
                 dW2, db2 = torch.zeros_like(W2), torch.zeros(d, dtype=torch.float32, device=dev)
-                dz0 = torch.empty(B, d, dtype=torch.float32, device=dev)
+                dz0 = torch.empty(nE, d, dtype=torch.float32, device=dev)
                 ops.dense_f32_bwd(z0, W2, st.d_e, dW=dW2, db=db2, dx=dz0, act_in=1)
                 dW0, db0 = torch.zeros_like(W0), torch.zeros(d, dtype=torch.float32, device=dev)
-                dsin = torch.empty(B, model.freq_dim, dtype=torch.float32, device=dev) if need_t else None
+                dsin = torch.empty(nE, model.freq_dim, dtype=torch.float32, device=dev) if need_t else None
                 ops.dense_f32_bwd(sin, W0, dz0, dW=dW0, db=db0, dx=dsin, act_in=0)
                 if need_t:
-                    gin[pos + 1] = ops.sinusoidal_embedding_bwd(dsin, t_dev).view(t.shape).to(device=t.device, dtype=t.dtype)
+                    dt = ops.sinusoidal_embedding_bwd(dsin, t_dev)
+                    if t.dim() == 2 and nE != t.numel():             # the pad frames took the last frame's t
+                        dt = dt.view(t.shape[0], -1)
+                        dt = torch.cat([dt[:, :t.shape[1] - 1], dt[:, t.shape[1] - 1:].sum(1, keepdim=True)], dim=1)
+                    gin[pos + 1] = dt.reshape(t.shape).to(device=t.device, dtype=t.dtype)
                 g.update({"time_projection.1.weight": dWp, "time_projection.1.bias": dbp, "time_embedding.2.weight": dW2,
                           "time_embedding.2.bias": db2, "time_embedding.0.weight": dW0, "time_embedding.0.bias": db0})
             # ---- text embedding: ctx = W2t gelu(W0t cin + b0t) + b2t
