@@ -395,6 +395,33 @@ int omh_flash_attn_bwd_interval_d128(const omh_attn_bwd_args* args, const int32_
 int omh_interval_mask_tables(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv);
 
 /* ------------------------------------------------------------------------
+ * Interval masks with up to THREE runs per row and per column, additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct
+ * layout changed; the two-run entries above stay as they are and still refuse a third run).  The same rule and the same
+ * contract in every respect — clamped table values, blind rows (o = 0, lse = -inf, dq = 0), unseen keys (dk = dv = 0),
+ * rows past qlen, lse optional / o32 REQUIRED, phases, out_bf16, q_prescaled, no workspace, no split, no atomics, the
+ * refusals and their codes — with table rows of 6 ints:
+ *   q_iv [q_groups][6] = lo0, hi0, lo1, hi1, lo2, hi2, half-open, in group units, lo0 <= hi0 <= lo1 <= hi1 <= lo2 <= hi2,
+ *                        lo == hi: empty; runs fill the slots in ascending order from slot 0
+ *   k_iv [k_groups][6]: the same relation seen from the key.
+ * A workgroup forms the hulls of the first, second and third intervals of the groups its live 128 rows (keys) span, drops
+ * the empty ones and merges neighbours that touch or overlap in tile units: up to three tile ranges with up to two jumps,
+ * in ascending order; tiles between ranges are never fetched.  The forward runs its unmasked body on a tile inside the
+ * intersection of the i-th intervals of all those groups, for any i; dQ and dK / dV mask every tile.
+ * Teacher forcing with an attention sink (clean sink | clean window | own noisy chunk) is such a table; a table with at
+ * most two runs gives the bits of the two-run entries.  omh_interval_mask_tables3 (a HOST function) builds both tables
+ * from vis and returns OMH_E_BADARG for a FOURTH run in a row or a column, null pointers or a count < 1.
+ * ---------------------------------------------------------------------- */
+typedef struct omh_interval3_mask {
+    int32_t group, q_groups, k_groups, reserved;
+    const int32_t* q_iv;   /* device [q_groups][6]: lo0, hi0, lo1, hi1, lo2, hi2 — key groups, ascending, lo == hi: empty */
+    const int32_t* k_iv;   /* device [k_groups][6]: the same relation seen from the key: query groups                    */
+} omh_interval3_mask;
+int omh_flash_attn_fwd_interval3_d128(const omh_attn_args* args, const omh_interval3_mask* mask, omh_stream_t stream);
+int omh_flash_attn_bwd_interval3_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_interval3_mask* mask,
+                                      omh_stream_t stream);
+int omh_interval_mask_tables3(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv);
+
+/* ------------------------------------------------------------------------
  * Chunk-causal attention (a staircase over frame groups), additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout
  * changed).  The reference has no counterpart: it denoises a clip as one bidirectional sequence.  With
  *   qlen / klen = q_lens[b] / k_lens[b] (or Lq / Lk), clamped as elsewhere,

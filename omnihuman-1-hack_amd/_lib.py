@@ -143,6 +143,11 @@ class IntervalMaskArgs(C.Structure):
     _fields_ = [("group", i32), ("q_groups", i32), ("k_groups", i32), ("reserved", i32), ("q_iv", vp), ("k_iv", vp)]
 
 
+class Interval3MaskArgs(C.Structure):
+    """omh_interval3_mask (additive to ABI v12): the two [groups, 6] tables of causal.IntervalMask(runs=3)."""
+    _fields_ = [("group", i32), ("q_groups", i32), ("k_groups", i32), ("reserved", i32), ("q_iv", vp), ("k_iv", vp)]
+
+
 class BlockPoolOperand(C.Structure):
     """omh_block_pool_operand (additive to ABI v12): one bf16 operand of omh_block_pool_d128 and its outputs."""
     _fields_ = [("x", vp), ("ld", i64), ("L", i32), ("reserved", i32), ("lens", vp), ("mean", vp), ("coh", vp)]
@@ -226,6 +231,9 @@ _SIGS = {
     "omh_flash_attn_fwd_interval_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(IntervalMaskArgs), vp]),
     "omh_flash_attn_bwd_interval_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(IntervalMaskArgs), vp]),
     "omh_interval_mask_tables": (i32, [vp, i32, i32, vp, vp]),
+    "omh_flash_attn_fwd_interval3_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(Interval3MaskArgs), vp]),
+    "omh_flash_attn_bwd_interval3_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(Interval3MaskArgs), vp]),
+    "omh_interval_mask_tables3": (i32, [vp, i32, i32, vp, vp]),
     "omh_block_pool_d128": (i32, [C.POINTER(BlockPoolOperand), i32, i32, i32, vp]),
     "omh_block_select": (i32, [C.POINTER(BlockSelectArgs), vp]),
     "omh_block_mask_tables": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),

@@ -14,12 +14,17 @@ Interval masks (include/omh.h, ``omh_interval_mask``) are the table-driven gener
 of ``group`` tokens and a bool matrix ``vis[q_groups, k_groups]`` with at most two runs of True per row and per column
 says which key groups a query group sees.  ``IntervalMask`` holds such a matrix with its device tables;
 ``teacher_forcing_groups`` and ``sink_window_groups`` build two useful ones, ``interval_visible`` is the dense mask.
+``IntervalMask(..., runs=3)`` is the three-run form (``omh_interval3_mask``): teacher forcing with an attention sink.
+
+An attention sink plus a window (``WanModel.set_causal_chunks(fpc, W, S)``) rolls out on a ``RollingKVCache``: S sink slots
+and a ring of W + 1, so the cache's size does not depend on the clip's length.
 """
 import ctypes
 
 import torch
 
-__all__ = ["chunk_causal_visible", "KVCache", "sample", "IntervalMask", "interval_visible", "teacher_forcing_groups",
+__all__ = ["chunk_causal_visible", "KVCache", "RollingKVCache", "sample", "IntervalMask", "interval_visible",
+           "teacher_forcing_groups",
            "sink_window_groups", "forcing_loss"]
 
 
@@ -46,10 +51,18 @@ class IntervalMask:
     ``vis[i // group, j // group]`` (and both are below their sample's lengths).  Every row and every column may hold at
     most two runs of True (ValueError otherwise): the kernels carry two key intervals per query group and two query
     intervals per key group.  Both int32 tables [groups, 4] = lo0, hi0, lo1, hi1 are built once, on the host
-    (omh_interval_mask_tables), and held on ``device``."""
+    (omh_interval_mask_tables), and held on ``device``.
 
-    def __init__(self, vis, group, device="cpu"):
+    ``runs=3``: the three-run form (omh_interval3_mask) — at most THREE runs per row and per column (ValueError for a
+    fourth), tables [groups, 6] = lo0, hi0, lo1, hi1, lo2, hi2 from omh_interval_mask_tables3, and the three-run kernels
+    wherever the mask is passed.  Teacher forcing with an attention sink needs it."""
+
+    def __init__(self, vis, group, device="cpu", runs=2):
         from . import _lib
+        runs = int(runs)
+        if runs not in (2, 3):
+            raise ValueError(f"IntervalMask: runs = {runs}, 2 or 3 expected")
+        self.runs = runs
         vis = torch.as_tensor(vis).detach().to("cpu")
         group = int(group)
         if vis.dim() != 2 or vis.shape[0] < 1 or vis.shape[1] < 1:
@@ -59,12 +72,14 @@ class IntervalMask:
         self.vis = (vis != 0).contiguous()
         self.group, self.q_groups, self.k_groups = group, int(vis.shape[0]), int(vis.shape[1])
         bytes_ = self.vis.to(torch.uint8).contiguous()
-        q_iv = torch.zeros(self.q_groups, 4, dtype=torch.int32)
-        k_iv = torch.zeros(self.k_groups, 4, dtype=torch.int32)
-        rc = _lib.lib.omh_interval_mask_tables(ctypes.c_void_p(bytes_.data_ptr()), self.q_groups, self.k_groups,
-                                               ctypes.c_void_p(q_iv.data_ptr()), ctypes.c_void_p(k_iv.data_ptr()))
+        q_iv = torch.zeros(self.q_groups, 2 * runs, dtype=torch.int32)
+        k_iv = torch.zeros(self.k_groups, 2 * runs, dtype=torch.int32)
+        tables = _lib.lib.omh_interval_mask_tables3 if runs == 3 else _lib.lib.omh_interval_mask_tables
+        rc = tables(ctypes.c_void_p(bytes_.data_ptr()), self.q_groups, self.k_groups,
+                    ctypes.c_void_p(q_iv.data_ptr()), ctypes.c_void_p(k_iv.data_ptr()))
         if rc != 0:
-            raise ValueError("IntervalMask: a row or a column of vis holds more than two runs of True")
+            raise ValueError(f"IntervalMask: a row or a column of vis holds more than {'three' if runs == 3 else 'two'} "
+                             f"runs of True")
         self._host = (q_iv, k_iv)
         self.q_iv = self.k_iv = None
         self._move(torch.device(device))
@@ -84,11 +99,14 @@ class IntervalMask:
         return other
 
     def intervals(self):
-        """The two tables as nested lists (host copies): ([q_groups][4], [k_groups][4]) of lo0, hi0, lo1, hi1."""
+        """The two tables as nested lists (host copies): ([q_groups][4], [k_groups][4]) of lo0, hi0, lo1, hi1
+        (``runs=3``: rows of 6, with lo2, hi2)."""
         return self._host[0].tolist(), self._host[1].tolist()
 
     def c_struct(self):
         from . import _lib
+        if self.runs == 3:
+            return _lib.Interval3MaskArgs(self.group, self.q_groups, self.k_groups, 0, self.q_iv.data_ptr(), self.k_iv.data_ptr())
         return _lib.IntervalMaskArgs(self.group, self.q_groups, self.k_groups, 0, self.q_iv.data_ptr(), self.k_iv.data_ptr())
 
     def tiles(self, Lq, Lk, block=128, tile=64):
@@ -98,13 +116,16 @@ class IntervalMask:
         for q0 in range(0, Lq, block):
             rows = q_iv[q0 // self.group:(min(q0 + block, Lq) - 1) // self.group + 1]
             hull = []
-            for lo, hi in ((0, 1), (2, 3)):
+            for lo, hi in ((0, 1), (2, 3), (4, 5))[:self.runs]:
                 iv = [(r[lo] * self.group, min(r[hi] * self.group, Lk)) for r in rows if r[hi] > r[lo]]
                 iv = [(a, b) for a, b in iv if b > a]
-                if iv:
-                    hull.append((min(a for a, _ in iv) // tile, (max(b for _, b in iv) - 1) // tile + 1))
-            if len(hull) == 2 and hull[1][0] <= hull[0][1]:
-                hull = [(hull[0][0], max(hull[0][1], hull[1][1]))]
+                if not iv:
+                    continue
+                a, b = min(a for a, _ in iv) // tile, (max(b for _, b in iv) - 1) // tile + 1
+                if hull and a <= hull[-1][1]:                     # touches or overlaps the range before it: one range
+                    hull[-1] = (hull[-1][0], max(hull[-1][1], b))
+                else:
+                    hull.append((a, b))
             total += sum(b - a for a, b in hull)
         return total
 
@@ -124,16 +145,20 @@ def interval_visible(mask, Lq, Lk, qlen=None, klen=None):
     return dense & (i < qlen) & (j < klen)
 
 
-def teacher_forcing_groups(n_chunks, left_chunks=-1):
+def teacher_forcing_groups(n_chunks, left_chunks=-1, sink_chunks=0):
     """The teacher-forcing matrix over the sequence [n clean chunks | n noisy chunks], bool [2n, 2n]: clean row g sees
     clean j <= g (and j >= g - W when W = ``left_chunks`` >= 0); noisy row n + I sees clean j < I (and j >= I - W) and noisy
-    n + I only — what ``WanModel.forward_chunk`` attends to at chunk I with ``left_chunks`` = W."""
-    n, W = int(n_chunks), int(left_chunks)
-    if n < 1:
-        raise ValueError(f"teacher_forcing_groups: n_chunks = {n} >= 1 expected")
+    n + I only — what ``WanModel.forward_chunk`` attends to at chunk I with ``left_chunks`` = W.  With W >= 0 and
+    S = ``sink_chunks`` > 0 the first S clean chunks stay visible behind the window (j >= . - W or j < S): up to three
+    runs per row, an ``IntervalMask(runs=3)``."""
+    n, W, S = int(n_chunks), int(left_chunks), int(sink_chunks)
+    if n < 1 or S < 0:
+        raise ValueError(f"teacher_forcing_groups: n_chunks = {n} >= 1 and sink_chunks = {S} >= 0 expected")
     g = torch.arange(n).view(n, 1)
     j = torch.arange(n).view(1, n)
     back = (j >= g - W) if W >= 0 else torch.ones(n, n, dtype=torch.bool)
+    if W >= 0 and S > 0:
+        back = back | (j < S)
     vis = torch.zeros(2 * n, 2 * n, dtype=torch.bool)
     vis[:n, :n] = (j <= g) & back
     vis[n:, :n] = (j < g) & back
@@ -198,9 +223,78 @@ class KVCache:
         self.length = 0
 
 
+class RollingKVCache:
+    """A ``KVCache`` of constant size for a model under ``set_causal_chunks(fpc, W, S)``, W = ``left_chunks`` >= 0,
+    S = ``sink_chunks`` >= 0: ``slots`` = S + W + 1 slots of ``chunk_tokens`` = fpc h w tokens per layer, laid out as in
+    ``KVCache`` (``k[l]`` bf16 [batch, cap, dim] token-major, ``vt[l]`` bf16 [batch, dim, pitch] with 64 elements of slack
+    behind it), cap = slots * chunk_tokens.  The sink slots come first, the rest is a ring: chunk I < S lives in slot I,
+    chunk I >= S in slot S + (I - S) mod (W + 1) — the slot of chunk I - W - 1, which chunk I does not see.  After any
+    number of commits the resident chunks are the sink and the last W + 1.
+
+    ``length`` counts the tokens committed since ``reset()`` and does not stop at the capacity.  ``truncate`` reaches
+    back to the start of the last committed chunk only: what lay before it may be evicted already."""
+    rolling = True
+
+    def __init__(self, model, batch, chunk_tokens, sink_chunks, left_chunks, device):
+        batch, Ct, S, W = int(batch), int(chunk_tokens), int(sink_chunks), int(left_chunks)
+        if batch < 1 or Ct < 1:
+            raise ValueError(f"RollingKVCache: batch = {batch} and chunk_tokens = {Ct} must be positive")
+        if S < 0 or W < 0:
+            raise ValueError(f"RollingKVCache: sink_chunks = {S} >= 0 and left_chunks = {W} >= 0 expected (an unbounded "
+                             f"look-back never evicts: use KVCache)")
+        self.model_id = id(model)
+        self.batch, self.dim = batch, int(model.dim)
+        self.chunk_tokens, self.sink_chunks, self.left_chunks = Ct, S, W
+        self.slots = S + W + 1
+        self.cap = self.slots * Ct
+        self.pitch = (self.cap + 63) // 64 * 64
+        self.length = 0
+        self._floor = 0                                    # truncate() may not go below it
+        n = len(model.blocks)
+        self.k = [torch.zeros(batch, self.cap, self.dim, dtype=torch.bfloat16, device=device) for _ in range(n)]
+        self._vt_store = [torch.zeros(batch * self.dim * self.pitch + 64, dtype=torch.bfloat16, device=device)
+                          for _ in range(n)]
+        self.vt = [s[:batch * self.dim * self.pitch].view(batch, self.dim, self.pitch) for s in self._vt_store]
+
+    def slot(self, chunk):
+        """The slot chunk ``chunk`` of the clip lives in."""
+        S = self.sink_chunks
+        return chunk if chunk < S else S + (chunk - S) % (self.left_chunks + 1)
+
+    def resident(self):
+        """{slot: chunk} of the committed chunks that are still in the cache (a partly committed chunk counts)."""
+        n = (self.length + self.chunk_tokens - 1) // self.chunk_tokens
+        return {self.slot(c): c for c in range(n) if c < self.sink_chunks or c >= n - 1 - self.left_chunks}
+
+    def check_room(self, n_tokens):
+        """ValueError when ``n_tokens`` more do not fit into the chunk ``length`` stands in."""
+        if n_tokens < 0 or self.length % self.chunk_tokens + n_tokens > self.chunk_tokens:
+            raise ValueError(f"RollingKVCache: {n_tokens} tokens at {self.length} committed ones cross the end of a chunk of "
+                             f"{self.chunk_tokens} tokens")
+
+    def advance(self, n_tokens):
+        """Commit ``n_tokens`` more (their k / V^T are in their slot)."""
+        self.check_room(n_tokens)
+        if n_tokens > 0:
+            self._floor = self.length - self.length % self.chunk_tokens
+        self.length += int(n_tokens)
+
+    def truncate(self, n_tokens):
+        """Forget every token from ``n_tokens`` on — within the last committed chunk (ValueError otherwise: the chunk
+        before the window of an earlier one has been overwritten)."""
+        n_tokens = int(n_tokens)
+        if not self._floor <= n_tokens <= self.length:
+            raise ValueError(f"RollingKVCache.truncate({n_tokens}): only [{self._floor}, {self.length}], the last committed "
+                             f"chunk, can be cut")
+        self.length = n_tokens
+
+    def reset(self):
+        self.length = self._floor = 0
+
+
 @torch.no_grad()
 def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks=-1, make_scheduler, guide_scale,
-           context_t=0.0):
+           context_t=0.0, sink_chunks=0, rolling=False, caches=None):
     """Denoise one clip chunk by chunk.  ``noise``: the initial latents [C, F, H, W] of the clip; ``context`` /
     ``context_null``: what ``WanModel.forward`` takes for a batch of one (a list with one [L, text_dim] tensor, or a
     ``ContextState``).  For every group of ``frames_per_chunk`` latent frames (the last one may be shorter):
@@ -211,7 +305,11 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
     3. one ``commit=True`` pass of the finished chunk at t = ``context_t`` on both caches, so that the later chunks
        attend to its keys and values (skipped behind the last chunk: nothing reads them).
 
-    A chunk sees itself and the ``left_chunks`` chunks before it (< 0: all of them).  The model's own
+    A chunk sees itself and the ``left_chunks`` chunks before it (< 0: all of them), and with ``sink_chunks`` > 0 the
+    first ``sink_chunks`` chunks of the clip as well.  ``rolling=True`` (needs ``left_chunks`` >= 0; implied by a sink):
+    two ``RollingKVCache``s in place of the two ``KVCache``s — cache memory then does not depend on the clip's length.
+    ``caches``: a pair (conditional, unconditional) of caches of batch 1 to use in place of fresh ones (they are reset).
+    The model's own
     ``set_causal_chunks`` setting is restored on the way out.  Returns the latents of the whole clip, fp32 [C, F, H, W]."""
     fpc = int(frames_per_chunk)
     if noise.dim() != 4:
@@ -219,10 +317,27 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
     F = noise.shape[1]
     pt, ph, pw = model.patch_size
     tokens = (F // pt) * (noise.shape[2] // ph) * (noise.shape[3] // pw)
+    left_chunks, sink_chunks = int(left_chunks), int(sink_chunks)
+    if rolling and left_chunks < 0:
+        raise ValueError("sample: rolling=True needs left_chunks >= 0 (an unbounded look-back never evicts)")
+    if sink_chunks < 0:
+        raise ValueError(f"sample: sink_chunks = {sink_chunks} >= 0 expected")
+    if left_chunks < 0:
+        sink_chunks = 0
     prev = getattr(model, "_causal_chunks", None)
-    model.set_causal_chunks(fpc, left_chunks)
+    model.set_causal_chunks(fpc, left_chunks, sink_chunks)
     try:
-        caches = (KVCache(model, 1, tokens, noise.device), KVCache(model, 1, tokens, noise.device))
+        if caches is not None:
+            caches = tuple(caches)
+            if len(caches) != 2:
+                raise ValueError("sample: caches = (conditional, unconditional) expected")
+            for c in caches:
+                c.reset()
+        elif rolling or sink_chunks > 0:
+            Ct = fpc * (noise.shape[2] // ph) * (noise.shape[3] // pw)
+            caches = tuple(RollingKVCache(model, 1, Ct, sink_chunks, left_chunks, noise.device) for _ in range(2))
+        else:
+            caches = (KVCache(model, 1, tokens, noise.device), KVCache(model, 1, tokens, noise.device))
         t_ctx = torch.full((1,), float(context_t), device=noise.device)
         done = []
         for f0 in range(0, F, fpc):

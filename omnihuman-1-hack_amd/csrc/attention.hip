@@ -95,13 +95,17 @@ struct AttnSplit {
 // intervals, then — `gap` tiles further — those inside the hull of their second ones (one range when the two touch), and
 // masks per element only the tiles that are not inside an interval every one of those groups shares.  Never split.
 // The query tiles keep their natural order: last tile first, CHK's order, lost time under teacher forcing.
-template <bool WIN, bool BLK = false, bool CHK = false, bool IVL = false>
+// IV3 (with IVL): the three-run form (omh_interval3_mask; omh_common.h Ivl3Span / omh_ivl3_tiles) — table rows of 6 ints,
+// THREE key intervals per row, up to three tile ranges with two jumps (`t_gap` behind tile n_first, `t_gap1` behind tile
+// n_second of the loop), and the unmasked body for a tile inside the intersection of the i-th intervals, any i.
+template <bool WIN, bool BLK = false, bool CHK = false, bool IVL = false, bool IV3 = false>
 __global__ __launch_bounds__(256, 2)
 void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk, const BlkList bl,
                                 const ChunkRule ck) {
     static_assert(!(WIN && BLK), "a block mask excludes the band");
     static_assert(!CHK || WIN, "the staircase runs on the band's masking");
     static_assert(!IVL || (WIN && !CHK), "an interval mask runs on the band's masking, in place of the other rules");
+    static_assert(!IV3 || IVL, "the three-run form is an interval mask");
     const IvlTab iv = omh_ivl_tab(bl);                    // IVL: the table arrives in the BlkList argument
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (KT_BYTES + VT_BYTES)];
 
@@ -130,6 +134,7 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     int whole_lo = 0, whole_hi = -1;                      // CHK: the keys EVERY live row of the workgroup sees
     int whole1_lo = 0, whole1_hi = -1;                    // IVL: ... through its second interval (whole_lo / hi: the first)
     int n_first = 0, t_gap = 0;                           // IVL: tiles of the first range, tiles skipped behind it
+    int whole2_lo = 0, whole2_hi = -1, n_second = 0, t_gap1 = 0;   // IV3: the third interval, tiles of the first two ranges, the second jump
     if constexpr (WIN) {
         int qlen = p.q_lens ? p.q_lens[b] : p.Lq;
         qlen = min(max(qlen, 0), p.Lq);
@@ -138,6 +143,16 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         int lo, hi;
         if constexpr (IVL) {
             lo = 0; hi = -1;
+            if constexpr (IV3) {
+                if (q1 >= q0) {
+                    int w[6];
+                    const Ivl3Tiles it = omh_ivl3_tiles(iv, q0, q1, klen, KB, w);
+                    whole_lo = w[0]; whole_hi = w[1]; whole1_lo = w[2]; whole1_hi = w[3]; whole2_lo = w[4]; whole2_hi = w[5];
+                    t_first = it.t_first; n_first = it.n0; t_gap = it.gap0; n_second = it.n1; t_gap1 = it.gap1; n_tiles = it.n_tiles;
+                } else {
+                    n_tiles = 0;
+                }
+            } else
             if (q1 >= q0) {
                 int w0[2], w1[2];
                 const IvlTiles it = omh_ivl_tiles(iv, q0, q1, klen, KB, w0, w1);
@@ -199,7 +214,10 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     const int q_ld = min(q_row, p.Lq - 1);
     int key_lo = 0, key_hi = klen - 1;                    // WIN: this lane's (query row's) band of keys
     IvlSpan span = {0, 0, 0, 0};                          // IVL: this lane's two intervals of keys
-    if constexpr (IVL) {
+    Ivl3Span span3 = {0, 0, 0, 0, 0, 0};                  // IV3: this lane's three intervals of keys
+    if constexpr (IV3) {
+        span3 = omh_ivl3_row(iv, q_row / iv.group, klen);
+    } else if constexpr (IVL) {
         span = omh_ivl_row(iv, q_row / iv.group, klen);
     } else if constexpr (CHK) {
         const int ci = (ck.off + q_row) / ck.chunk;                           // this row's chunk
@@ -283,11 +301,15 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         const int buf = tt & 1;
         int t = t_first + tt;
         if constexpr (IVL) t += tt >= n_first ? t_gap : 0;
+        if constexpr (IV3) t += tt >= n_second ? t_gap1 : 0;
         if constexpr (BLK) {
             t = t_cur;
             OMH_GLOAD(t_nxt)
             t_cur = t_nxt;
             t_nxt = blk_tile(min(tt + 2, n_tiles - 1));   // a tile ahead of its loads
+        } else if constexpr (IV3) {
+            const int nx = min(tt + 1, n_tiles - 1);
+            OMH_GLOAD(t_first + nx + (nx >= n_first ? t_gap : 0) + (nx >= n_second ? t_gap1 : 0))
         } else if constexpr (IVL) {
             const int nx = min(tt + 1, n_tiles - 1);
             OMH_GLOAD(t_first + nx + (nx >= n_first ? t_gap : 0))
@@ -315,7 +337,8 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         const int kv0 = t * KB;
         // CHK: a tile inside [whole_lo, whole_hi] needs no mask for a live row (rows at or past qlen are written as zeros
         // whatever they accumulate): most tiles of a long look-back
-        if (IVL && ((kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi) || (kv0 >= whole1_lo && kv0 + KB - 1 <= whole1_hi))) {
+        if (IVL && ((kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi) || (kv0 >= whole1_lo && kv0 + KB - 1 <= whole1_hi) ||
+                    (IV3 && kv0 >= whole2_lo && kv0 + KB - 1 <= whole2_hi))) {
             // inside an interval every live row of the workgroup sees (cut at klen): nothing to mask
         } else if constexpr (IVL) {
 #pragma unroll
@@ -323,7 +346,8 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kv0 + kb * 32 + ((r >> 3) << 4) + lh * 8 + (r & 7);
-                    if (!span.sees(key)) s[kb][r] = -INFINITY;
+                    if constexpr (IV3) s[kb][r] = span3.sees(key) ? s[kb][r] : -INFINITY;
+                    else if (!span.sees(key)) s[kb][r] = -INFINITY;
                 }
         } else
         if (WIN && !(CHK && kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi)) {   // (key_hi <= klen - 1: the band mask covers the sequence end too)
@@ -665,21 +689,42 @@ extern "C" int omh_flash_attn_fwd_interval_d128(const omh_attn_args* args, const
     return omh_launch_status();
 }
 
+// Additive to ABI v12: the forward under a three-run interval mask (include/omh.h): the IV3 instantiation, otherwise
+// omh_flash_attn_fwd_interval_d128.
+extern "C" int omh_flash_attn_fwd_interval3_d128(const omh_attn_args* args, const omh_interval3_mask* mask, omh_stream_t stream) {
+    if (!mask) return OMH_E_BADARG;
+    const int rc0 = attn_fwd_check(args);
+    if (rc0) return rc0;
+    const omh_attn_args& a = *args;
+    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
+    const int rc1 = omh_interval3_mask_check(mask, a.Lq, a.Lk);
+    if (rc1) return rc1;
+    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
+    const int q_tiles = (a.Lq + QB - 1) / QB;
+    const int nwg = q_tiles * a.H * a.B;
+    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
+    omh_clear_status();
+    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<true, false, false, true, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a,
+                       q_tiles, wk, omh_ivl_arg(mask->q_iv, mask->group, mask->q_groups, mask->k_groups), ChunkRule{});
+    return omh_launch_status();
+}
+
 // The two tables of an omh_interval_mask from its bool matrix (a host function: no device is touched).  Row g of q_iv:
 // the at most two runs of true in row g of vis, as half-open intervals; k_iv: the same for the columns.
-static int ivl_runs(const uint8_t* v, int n, int64_t stride, int32_t* out) {
+// (`max_runs` = 2 or 3: the row holds 2 max_runs ints; unused slots are empty intervals at the end of the last run)
+static int ivl_runs(const uint8_t* v, int n, int64_t stride, int32_t* out, int max_runs = 2) {
     int runs = 0;
-    out[0] = out[1] = out[2] = out[3] = 0;
+    for (int i = 0; i < 2 * max_runs; ++i) out[i] = 0;
     for (int j = 0; j < n; ++j) {
         const bool on = v[j * stride] != 0, prev = j > 0 && v[(j - 1) * stride] != 0;
         if (on && !prev) {
-            if (runs == 2) return OMH_E_BADARG;
+            if (runs == max_runs) return OMH_E_BADARG;
             out[2 * runs] = j;
             ++runs;
         }
         if (on) out[2 * runs - 1] = j + 1;
     }
-    if (runs < 2) out[2] = out[3] = out[1];               // hi0 <= lo1 = hi1: empty
+    for (int r = runs > 0 ? runs : 1; r < max_runs; ++r) out[2 * r] = out[2 * r + 1] = out[2 * r - 1];   // hi <= lo = hi: empty
     return 0;
 }
 extern "C" int omh_interval_mask_tables(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv) {
@@ -688,5 +733,14 @@ extern "C" int omh_interval_mask_tables(const uint8_t* vis, int32_t q_groups, in
         if (ivl_runs(vis + (int64_t)g * k_groups, k_groups, 1, q_iv + 4 * (int64_t)g)) return OMH_E_BADARG;
     for (int g = 0; g < k_groups; ++g)
         if (ivl_runs(vis + g, q_groups, k_groups, k_iv + 4 * (int64_t)g)) return OMH_E_BADARG;
+    return 0;
+}
+// The three-run tables (rows of 6 ints) of an omh_interval3_mask: a fourth run in a row or a column is OMH_E_BADARG.
+extern "C" int omh_interval_mask_tables3(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv) {
+    if (!vis || !q_iv || !k_iv || q_groups < 1 || k_groups < 1) return OMH_E_BADARG;
+    for (int g = 0; g < q_groups; ++g)
+        if (ivl_runs(vis + (int64_t)g * k_groups, k_groups, 1, q_iv + 6 * (int64_t)g, 3)) return OMH_E_BADARG;
+    for (int g = 0; g < k_groups; ++g)
+        if (ivl_runs(vis + g, q_groups, k_groups, k_iv + 6 * (int64_t)g, 3)) return OMH_E_BADARG;
     return 0;
 }

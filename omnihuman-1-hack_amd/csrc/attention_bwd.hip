@@ -394,6 +394,7 @@ int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const 
 int omh_launch_attn_bwd2_sparse(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_block_mask& m, hipStream_t s);
 int omh_launch_attn_bwd2_chunk(const omh_attn_bwd_args& a, const int32_t* q_lens, const ChunkRule& ck, hipStream_t s);
 int omh_launch_attn_bwd2_interval(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval_mask& m, hipStream_t s);
+int omh_launch_attn_bwd2_interval3(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval3_mask& m, hipStream_t s);
 
 static bool bwd_ptrs_set(const omh_attn_bwd_args& a) {
     return a.q && a.k && a.v && a.dout && a.lse && a.delta && a.dq && a.dk && a.dv;
@@ -477,6 +478,21 @@ extern "C" int omh_flash_attn_bwd_interval_d128(const omh_attn_bwd_args* args, c
     if (rc1) return rc1;
     omh_clear_status();
     const int rc = omh_launch_attn_bwd2_interval(*args, q_lens, *mask, (hipStream_t)stream);
+    return rc ? rc : omh_launch_status();
+}
+
+// the backward under a three-run interval mask (include/omh.h): the same rules on the IV3 instantiations
+extern "C" int omh_flash_attn_bwd_interval3_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_interval3_mask* mask,
+                                                 omh_stream_t stream) {
+    if (!mask) return OMH_E_BADARG;
+    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
+    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
+    const int rc0 = bwd2_check(*args);
+    if (rc0) return rc0;
+    const int rc1 = omh_interval3_mask_check(mask, args->Lq, args->Lk);
+    if (rc1) return rc1;
+    omh_clear_status();
+    const int rc = omh_launch_attn_bwd2_interval3(*args, q_lens, *mask, (hipStream_t)stream);
     return rc ? rc : omh_launch_status();
 }
 

@@ -190,7 +190,7 @@ static inline int omh_chunk_rule(const omh_chunk_causal* c, int Lq, int Lk, Chun
 // of groups of the OTHER axis that group g of the workgroup's axis sees (q_iv: forward and dQ; k_iv: dK / dV), in groups
 // of `group` positions; `n` rows, `other` groups on the other axis.
 struct IvlTab {
-    const int32_t* iv;    // [n][4]
+    const int32_t* iv;    // [n][4] (the three-run form below: [n][6])
     int group, n, other;
 };
 // The IVL kernels take their table in the BlkList argument (no kernel has both): a further kernel argument would change
@@ -203,6 +203,14 @@ static_assert(std::is_same<decltype(BlkList::idx), decltype(IvlTab::iv)>::value 
               "omh_ivl_arg / omh_ivl_tab map idx, heads, lists, stride to iv, group, n, other");
 // 0 or the error code (the tables themselves live on the device: the kernels clamp what they read to [0, other])
 static inline int omh_interval_mask_check(const omh_interval_mask* m, int Lq, int Lk) {
+    if (!m || !m->q_iv || !m->k_iv || m->group < 8 || m->reserved != 0) return OMH_E_BADARG;
+    if ((int64_t)Lq + Lk >= (1LL << 28)) return OMH_E_SHAPE;
+    if (m->q_groups != (Lq + m->group - 1) / m->group || m->k_groups != (Lk + m->group - 1) / m->group) return OMH_E_BADARG;
+    if (((uintptr_t)m->q_iv | (uintptr_t)m->k_iv) & 3) return OMH_E_ALIGN;
+    return 0;
+}
+// the same rules for the three-run mask (its tables have rows of 6 ints; the kernels know the stride from their instantiation)
+static inline int omh_interval3_mask_check(const omh_interval3_mask* m, int Lq, int Lk) {
     if (!m || !m->q_iv || !m->k_iv || m->group < 8 || m->reserved != 0) return OMH_E_BADARG;
     if ((int64_t)Lq + Lk >= (1LL << 28)) return OMH_E_SHAPE;
     if (m->q_groups != (Lq + m->group - 1) / m->group || m->k_groups != (Lk + m->group - 1) / m->group) return OMH_E_BADARG;
@@ -255,6 +263,68 @@ __device__ __forceinline__ IvlTiles omh_ivl_tiles(const IvlTab& tb, int x0, int 
     const int b0 = blo / tile, b1 = (bhi - 1) / tile + 1;
     if (b0 <= a1) { t.n0 = t.n_tiles = max(a1, b1) - a0; return t; }
     t.n0 = a1 - a0; t.gap = b0 - a1; t.n_tiles = t.n0 + (b1 - b0);
+    return t;
+}
+// ---- the three-run form (include/omh.h omh_interval3_mask): rows of 6 ints, lo0, hi0, lo1, hi1, lo2, hi2.  The same
+// rules with one more (lo, len) pair and one more jump; kept beside the two-run form, which stays as it is so that its
+// kernels keep their instruction streams.  The table travels in the BlkList argument in the same way.
+struct Ivl3Span {
+    int lo0, len0, lo1, len1, lo2, len2;
+    __device__ __forceinline__ bool sees(int x) const {
+        // (bitwise: three compares and two ORs per element, no short-circuit branches)
+        return ((unsigned)(x - lo0) < (unsigned)len0) | ((unsigned)(x - lo1) < (unsigned)len1) | ((unsigned)(x - lo2) < (unsigned)len2);
+    }
+};
+// row g of the [n][6] table in positions, cut at `end`
+__device__ __forceinline__ Ivl3Span omh_ivl3_row(const IvlTab& tb, int g, int end) {
+    const int32_t* __restrict__ r = tb.iv + 6 * (int64_t)min(max(g, 0), tb.n - 1);
+    const int a0 = min(max(r[0], 0), tb.other), a1 = min(max(r[1], 0), tb.other);
+    const int b0 = min(max(r[2], 0), tb.other), b1 = min(max(r[3], 0), tb.other);
+    const int c0 = min(max(r[4], 0), tb.other), c1 = min(max(r[5], 0), tb.other);
+    Ivl3Span s;
+    s.lo0 = a0 * tb.group; s.len0 = max(min(a1 * tb.group, end) - s.lo0, 0);
+    s.lo1 = b0 * tb.group; s.len1 = max(min(b1 * tb.group, end) - s.lo1, 0);
+    s.lo2 = c0 * tb.group; s.len2 = max(min(c1 * tb.group, end) - s.lo2, 0);
+    return s;
+}
+// The tiles a workgroup whose live positions are x0 .. x1 runs: the hulls of its groups' first, second and third
+// intervals (their lower ends ascend: every row's do), empty ones dropped, neighbours that touch or overlap in tile units
+// merged — up to three ranges.  Tile x of the loop, x in [0, n_tiles), is  t_first + x + (x >= n0 ? gap0 : 0) +
+// (x >= n1 ? gap1 : 0);  n0 <= n1 <= n_tiles count the tiles of the first range and of the first two.  whole (may be NULL):
+// [lo, hi] of the positions EVERY one of those groups sees through its i-th interval, i = 0, 1, 2 (hi < lo: none).
+struct Ivl3Tiles { int t_first, n0, gap0, n1, gap1, n_tiles; };
+__device__ __forceinline__ Ivl3Tiles omh_ivl3_tiles(const IvlTab& tb, int x0, int x1, int end, int tile, int* whole) {
+    const int g0 = x0 / tb.group, g1 = x1 / tb.group;
+    int hlo[3] = {1 << 30, 1 << 30, 1 << 30}, hhi[3] = {0, 0, 0};    // hulls, [lo, hi)
+    int wlo[3] = {0, 0, 0}, whi[3] = {1 << 30, 1 << 30, 1 << 30};    // intersections, [lo, hi)
+    for (int g = g0; g <= g1; ++g) {
+        const Ivl3Span s = omh_ivl3_row(tb, __builtin_amdgcn_readfirstlane(g), end);
+        const int lo[3] = {s.lo0, s.lo1, s.lo2}, len[3] = {s.len0, s.len1, s.len2};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (len[i] > 0) { hlo[i] = min(hlo[i], lo[i]); hhi[i] = max(hhi[i], lo[i] + len[i]); }
+            wlo[i] = max(wlo[i], lo[i]); whi[i] = min(whi[i], lo[i] + len[i]);
+        }
+    }
+    if (whole) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { whole[2 * i] = wlo[i]; whole[2 * i + 1] = whi[i] - 1; }
+    }
+    int s0 = 0, e0 = 0, s1 = 0, e1 = 0, s2 = 0, e2 = 0, nr = 0;      // merged tile ranges [s, e), ascending (scalars: no indexing)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (hhi[i] <= hlo[i]) continue;
+        const int a = hlo[i] / tile, b = (hhi[i] - 1) / tile + 1;
+        if (nr == 0) { s0 = a; e0 = b; nr = 1; }
+        else if (nr == 1) { if (a <= e0) e0 = max(e0, b); else { s1 = a; e1 = b; nr = 2; } }
+        else { if (a <= e1) e1 = max(e1, b); else { s2 = a; e2 = b; nr = 3; } }
+    }
+    Ivl3Tiles t = {0, 0, 0, 0, 0, 0};
+    if (nr == 0) return t;
+    t.t_first = s0;
+    t.n0 = t.n1 = t.n_tiles = e0 - s0;
+    if (nr >= 2) { t.gap0 = s1 - e0; t.n1 = t.n_tiles = t.n0 + (e1 - s1); }
+    if (nr == 3) { t.gap1 = s2 - e1; t.n_tiles = t.n1 + (e2 - s2); }
     return t;
 }
 #endif

@@ -246,7 +246,8 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
     short-sequence kernel, never split; ValueError beside a band or a block mask.
     ``interval_mask``: a ``causal.IntervalMask`` — up to two key intervals per group of query rows
     (omh_flash_attn_fwd_interval_d128, include/omh.h): the short-sequence kernel over the tiles inside each workgroup's
-    two ranges, never split; ValueError beside a band, a block mask or ``chunk_causal``."""
+    two ranges, never split; ValueError beside a band, a block mask or ``chunk_causal``.  A mask built with ``runs=3``
+    goes to the three-run entries (omh_flash_attn_fwd_interval3_d128; ``flash_attn_bwd``: ..._bwd_interval3_d128)."""
     im = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal)
     cc = _chunk_causal(chunk_causal, window, block_mask)
     bm = _block_mask(block_mask, H, Lq, Lk, window)
@@ -261,6 +262,9 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
         return
     if im is not None:
         m = im.c_struct()
+        if im.runs == 3:
+            check(lib.omh_flash_attn_fwd_interval3_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_interval3_d128")
+            return
         check(lib.omh_flash_attn_fwd_interval_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_interval_d128")
         return
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
@@ -402,6 +406,10 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
         return dq, dk, dv
     if im is not None:
         m = im.c_struct()
+        if im.runs == 3:
+            check(lib.omh_flash_attn_bwd_interval3_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
+                  "omh_flash_attn_bwd_interval3_d128")
+            return dq, dk, dv
         check(lib.omh_flash_attn_bwd_interval_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
               "omh_flash_attn_bwd_interval_d128")
         return dq, dk, dv

@@ -179,7 +179,10 @@ class _FwdCtx:
                  "chunk", "cache", "cache_layer", "cache_lo",
                  # rpb: rows of the sequence that share one row of e0 (seq_len, or h * w with a per-frame t);
                  # interval: a causal.IntervalMask every self-attention runs under (forward_teacher_forcing), else unset
-                 "rpb", "interval")
+                 "rpb", "interval",
+                 # cache_pos, cache_hi, cache_mask: forward_chunk on a causal.RollingKVCache (the chunk's slot, the end of
+                 # the filled slots, the mask over stale keys of a short last chunk), else None / unset
+                 "cache_pos", "cache_hi", "cache_mask")
 
 
 class ContextState:
@@ -377,11 +380,18 @@ class WanSelfAttention(nn.Module):
         these rows only; k (normalised, rotated) lands in rows [length, length + C) of this layer's cache and V^T in the
         same columns, straight from the V^T product (ldc = the cache pitch); plain attention then runs with Lq = C over the
         keys [lo, length + C) of the cache — a pointer offset, no copy.  The launches of ``_attend`` at seq_len = C
-        otherwise, so on an empty cache the result has its bits."""
+        otherwise, so on an empty cache the result has its bits.
+        A ``causal.RollingKVCache``: the chunk's rows go to ``fc.cache_pos`` (its slot) and the keys are [0, fc.cache_hi) —
+        every filled slot; softmax attention does not depend on the order of its keys, and they carry absolute rotary
+        positions.  ``fc.cache_mask`` (a short last chunk in a wrapped ring): the interval kernel skips the stale keys
+        behind the chunk in its slot."""
         B, C, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
         cache, lo = fc.cache, fc.cache_lo
         kc, vtc = cache.k[fc.cache_layer], cache.vt[fc.cache_layer]
         L0, cap, pitch = cache.length, cache.cap, cache.pitch
+        hi = L0 + C
+        if getattr(fc, "cache_pos", None) is not None:
+            L0, hi = fc.cache_pos, fc.cache_hi             # (L0: where this chunk's rows go)
         R = B * C
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
         wqk, bqk = self._w_qk()
@@ -399,7 +409,11 @@ class WanSelfAttention(nn.Module):
         ops.gemm_raw(ptr(wv), ptr(h), ptr(vtc, L0), d, C, d, d, d, pitch, EPI_BF16, bias=ptr(bv), bias_mode=BIAS_M, batch=B,
                      strideA=0, strideB=C * d, strideC=d * pitch)
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
-        Lk = L0 - lo + C
+        Lk = hi - lo
+        if getattr(fc, "cache_mask", None) is not None:
+            ops.flash_attn_raw(ptr(q), ptr(kc, lo * d), ptr(vtc, lo), ptr(o), None, B, N, C, Lk, C * d, d, cap * d, d,
+                               d * pitch, C * d, d, pitch, D ** -0.5, q_prescaled=1, interval_mask=fc.cache_mask)
+            return o
         # pinned to the short-sequence kernel: its V^T reads end at most 63 columns past the last key (the cache keeps
         # that much slack behind its last row); a chunk of queries does not reach the long-sequence dispatch at 12 heads
         ops.flash_attn_raw(ptr(q), ptr(kc, lo * d), ptr(vtc, lo), ptr(o), None, B, N, C, Lk, C * d, d, cap * d, d,
@@ -767,7 +781,7 @@ class WanModel(nn.Module):
             self.img_emb = MLPProj(1280, dim)
         self._packed = _Packed()
         self._rope_dev = None
-        self._causal_chunks = None                  # set_causal_chunks: (frames per chunk, left_chunks) or None
+        self._causal_chunks = None                  # set_causal_chunks: (frames per chunk, left_chunks[, sink_chunks > 0]) or None
         self.init_weights()
 
     # ------------------------------------------------------------------ loading
@@ -875,7 +889,7 @@ class WanModel(nn.Module):
                 self.blocks[i].self_attn.last_block_mask = None
 
     # ------------------------------------------------------------------ causal chunks
-    def set_causal_chunks(self, frames_per_chunk, left_chunks=-1):
+    def set_causal_chunks(self, frames_per_chunk, left_chunks=-1, sink_chunks=0):
         """Run every SELF-attention of ``forward`` under the chunk-causal staircase (the rule: include/omh.h,
         omh_chunk_causal): with C = frames_per_chunk * (h / p_h) * (w / p_w) tokens per chunk, token i sees token j iff
         j // C <= i // C and, for ``left_chunks`` >= 0, j // C >= i // C - left_chunks (< 0: every earlier chunk).
@@ -884,15 +898,29 @@ class WanModel(nn.Module):
         from it.  Cross-attention is never masked.  A run-time attribute like the block mask: in neither ``config`` nor
         the ``state_dict``.  ValueError for a model with a bounded ``window_size`` and for a layer that has a block mask
         or a block policy (here and again at ``forward``), and at ``forward`` for a batch whose clips do not share h, w
-        (one C serves the call; clips of different frame counts padded to ``seq_len`` are fine)."""
+        (one C serves the call; clips of different frame counts padded to ``seq_len`` are fine).
+
+        ``sink_chunks`` = S > 0 (with ``left_chunks`` = W >= 0; it is 0 otherwise): an attention sink — the first S chunks
+        stay visible behind the window, j // C < S or j // C >= i // C - W.  ``forward`` and ``forward_cfg_pair`` then run
+        self-attention under ``causal.IntervalMask(causal.sink_window_groups(ceil(seq_len / C), S, W), C)`` (two runs, the
+        interval kernels) in place of the staircase kernels, ``forward_teacher_forcing`` under the three-run teacher-forcing
+        mask, and ``forward_chunk`` needs a ``causal.RollingKVCache`` of the same (C, W, S)."""
         if frames_per_chunk is None:
             self._causal_chunks = None
             return
-        fpc, left = int(frames_per_chunk), int(left_chunks)
+        fpc, left, sink = int(frames_per_chunk), int(left_chunks), int(sink_chunks)
         if fpc < 1:
             raise ValueError(f"set_causal_chunks: frames_per_chunk = {frames_per_chunk}, at least 1 expected")
+        if sink < 0:
+            raise ValueError(f"set_causal_chunks: sink_chunks = {sink_chunks}, at least 0 expected")
         self._causal_check("set_causal_chunks")
-        self._causal_chunks = (fpc, -1 if left < 0 else left)
+        # (fpc, W) as ever without a sink; (fpc, W, S) with one — causal.sample saves and restores the tuple whole
+        self._causal_chunks = (fpc, -1 if left < 0 else left) + ((sink,) if left >= 0 and sink > 0 else ())
+
+    def _causal_sink(self):
+        """``sink_chunks`` of ``set_causal_chunks`` (0: none, or no causal chunks)."""
+        cc = getattr(self, "_causal_chunks", None)
+        return cc[2] if cc is not None and len(cc) > 2 else 0
 
     def _causal_check(self, who):
         if self.window_size[0] >= 0 or self.window_size[1] >= 0:
@@ -915,6 +943,37 @@ class WanModel(nn.Module):
                              f"serves the call), got {sorted(hw)}")
         h, w = next(iter(hw))
         return (cc[0] * h * w, cc[1], 0)
+
+    def _sink_mask(self, seq_len, chunk_tokens, device):
+        """The sink + window mask of a ``forward`` over ``seq_len`` tokens (cached per shape, as ``_tf_masks`` is)."""
+        from ... import causal as _causal
+        cc = self._causal_chunks
+        n = (seq_len + chunk_tokens - 1) // chunk_tokens
+        key = ("sink", n, cc[1], cc[2], chunk_tokens, str(device))
+        masks = self.__dict__.setdefault("_tf_masks", {})
+        if key not in masks:
+            if len(masks) > 64:
+                masks.clear()
+            masks[key] = _causal.IntervalMask(_causal.sink_window_groups(n, cc[2], cc[1]), chunk_tokens, device)
+        return masks[key]
+
+    def _stale_mask(self, cache, pos, C, tpf, device):
+        """The interval mask of a short chunk (``C`` tokens at ``pos``) in a wrapped ring: every query sees the keys
+        [0, pos + C) and [pos + chunk_tokens, cap) — not the stale keys behind it in its slot.  Groups of one frame's
+        tokens (>= 8: ValueError otherwise); cached per shape."""
+        from ... import causal as _causal
+        if tpf < 8:
+            raise ValueError(f"forward_chunk: a short last chunk in a full RollingKVCache needs at least 8 tokens per frame, "
+                             f"got {tpf}")
+        key = ("stale", pos, C, tpf, cache.cap, cache.chunk_tokens, str(device))
+        masks = self.__dict__.setdefault("_tf_masks", {})
+        if key not in masks:
+            if len(masks) > 64:
+                masks.clear()
+            vis = torch.ones(C // tpf, cache.cap // tpf, dtype=torch.bool)
+            vis[:, (pos + C) // tpf:(pos + cache.chunk_tokens) // tpf] = False
+            masks[key] = _causal.IntervalMask(vis, tpf, device)
+        return masks[key]
 
     def _rope_shifted(self, device, frame_offset):
         """The cos / sin tables with the FRAME columns moved up by ``frame_offset`` rows: frame f of a chunk then rotates
@@ -968,8 +1027,10 @@ class WanModel(nn.Module):
         (per-frame timesteps), q and k of both halves rotate with the SAME frame positions, and every self-attention
         runs under ``causal.IntervalMask(causal.teacher_forcing_groups(F / fpc, W), fpc h w)``: a clean chunk sees the
         clean chunks up to itself, noisy chunk I the clean chunks before it and itself — what ``forward_chunk`` attends
-        to at chunk I (both cut to W chunks back).  Cross-attention and the FFN are unchanged, ``y`` goes to both
-        halves, the head runs on the noisy rows only.  Returns the list of fp32 [C_out, F, H, W] for the noisy half.
+        to at chunk I (both cut to W chunks back; with ``sink_chunks`` = S > 0 the first S clean chunks stay visible:
+        ``teacher_forcing_groups(F / fpc, W, S)`` and the three-run kernels).  Cross-attention and the FFN are unchanged,
+        ``y`` goes to both halves, the head runs on the noisy rows only.  Returns the list of fp32 [C_out, F, H, W] for the
+        noisy half.
         ValueError without causal chunks, for a bounded ``window_size``, a block mask or policy, clips of different
         shapes, F no multiple of fpc, h w no multiple of 8 and a ``t`` of another shape."""
         cc = getattr(self, "_causal_chunks", None)
@@ -996,12 +1057,17 @@ class WanModel(nn.Module):
             raise ops.OmhError("WanModel.forward_teacher_forcing runs on the MI355X only (no CPU fallback): move the "
                                "model to a GPU device")
         from ... import causal as _causal
-        key = (F // fpc, cc[1], fpc * h * w, str(device))
+        sink = self._causal_sink()
+        key = (F // fpc, cc[1], fpc * h * w, str(device)) + ((sink,) if sink else ())
         masks = self.__dict__.setdefault("_tf_masks", {})
         if key not in masks:
             if len(masks) > 64:
                 masks.clear()
-            masks[key] = _causal.IntervalMask(_causal.teacher_forcing_groups(F // fpc, cc[1]), fpc * h * w, device)
+            if sink:                                       # clean sink | clean window | own chunk: three runs
+                masks[key] = _causal.IntervalMask(_causal.teacher_forcing_groups(F // fpc, cc[1], sink), fpc * h * w, device,
+                                                  runs=3)
+            else:
+                masks[key] = _causal.IntervalMask(_causal.teacher_forcing_groups(F // fpc, cc[1]), fpc * h * w, device)
         x = [torch.cat([c.to(n.device), n], dim=1) for c, n in zip(x_clean, x_noisy)]
         if y is not None:
             y = [torch.cat([v, v], dim=1) for v in y]
@@ -1027,7 +1093,10 @@ class WanModel(nn.Module):
         ``cache.length`` / tokens per frame), writes k and V^T at rows / columns [length, length + C) of its cache and
         attends over the keys [lo, length + C): lo = 0, or the first token of the look-back when ``set_causal_chunks``
         set ``left_chunks`` >= 0 (then ``cache.length`` must sit on a chunk boundary and the chunk may not exceed
-        ``frames_per_chunk``).  ``commit=True`` advances ``cache.length`` by C once, after the last block;
+        ``frames_per_chunk``).  With a ``causal.RollingKVCache`` (its geometry must equal the model's (fpc h w, W, S):
+        ValueError otherwise) k and V^T go to the chunk's slot and attention runs over every filled slot — the sink, the
+        window and the chunk itself, one contiguous key range; a plain ``KVCache`` under ``sink_chunks`` > 0 is a
+        ValueError.  ``commit=True`` advances ``cache.length`` by C once, after the last block;
         ``commit=False`` leaves the cache as it was (the rows behind ``length`` are scratch) — a denoising step of the
         current chunk.  Cross-attention, FFN and head as in ``forward``.  Tokens per chunk must be a multiple of 8 (the
         16-byte stores into the cache and the look-back offset): ValueError otherwise, and when the chunk does not fit.
@@ -1063,12 +1132,22 @@ class WanModel(nn.Module):
         cache.check_room(C)                                # ValueError past max_tokens
         lo = 0
         cc = getattr(self, "_causal_chunks", None)
+        rolling = getattr(cache, "rolling", False)
+        if rolling:
+            if cc is None or cc[1] < 0 or (cache.chunk_tokens, cache.left_chunks, cache.sink_chunks) != \
+                    (cc[0] * tpf, cc[1], self._causal_sink()):
+                raise ValueError(f"forward_chunk: a RollingKVCache of (chunk_tokens, left_chunks, sink_chunks) = "
+                                 f"({cache.chunk_tokens}, {cache.left_chunks}, {cache.sink_chunks}) on a model set to "
+                                 f"{None if cc is None else (cc[0] * tpf, cc[1], self._causal_sink())}")
+        elif self._causal_sink():
+            raise ValueError("forward_chunk: set_causal_chunks has sink_chunks > 0 — a plain KVCache never evicts and cannot "
+                             "keep a sink; use causal.RollingKVCache")
         if cc is not None:
             Ct = cc[0] * tpf
             if f > cc[0] or L0 % Ct:
                 raise ValueError(f"forward_chunk: a chunk of {f} frames at {L0} cached tokens does not fit chunks of "
                                  f"{cc[0]} frames ({Ct} tokens)")
-            if cc[1] >= 0:
+            if cc[1] >= 0 and not rolling:
                 lo = max(0, L0 // Ct - cc[1]) * Ct
         if frame_offset is None:
             if L0 % tpf:
@@ -1080,8 +1159,20 @@ class WanModel(nn.Module):
                              f"({self.freqs.shape[0]} frames)")
         xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, C, clip_fea, y)
         fc.chunk = None                                    # the cache IS the causal structure: plain attention over it
+        fc.interval = None
         fc.rope_cos, fc.rope_sin = self._rope_shifted(xs.device, frame_offset)
         fc.cache, fc.cache_lo = cache, lo
+        fc.cache_pos = fc.cache_hi = fc.cache_mask = None
+        if rolling:
+            # the chunk's slot; the keys are every filled slot.  Before the ring wraps they are [0, L0 + C), KVCache's range;
+            # afterwards all slots — one contiguous range, whatever chunk sits where
+            fc.cache_pos = cache.slot(L0 // Ct) * Ct
+            wrapped = L0 // Ct >= cache.slots
+            fc.cache_hi = cache.cap if wrapped else fc.cache_pos + C
+            if wrapped and C < Ct and fc.cache_pos + Ct < cache.cap:
+                fc.cache_mask = self._stale_mask(cache, fc.cache_pos, C, tpf, xs.device)
+            elif wrapped and C < Ct:                       # the last slot: the stale keys are the end of the range
+                fc.cache_hi = fc.cache_pos + C
         seq_lens = _dev_ints(lens, torch.long, xs.device)
         grid_sizes = _dev_ints(grids, torch.long, xs.device)
         context_lens = _dev_ints(ctx_lens, torch.long, xs.device)
@@ -1183,6 +1274,8 @@ class WanModel(nn.Module):
         fc.rope_cos, fc.rope_sin = self._rope(device)
         fc.seq_lens_host = list(lens)                                       # host copies: no device sync later
         fc.chunk = self._causal_rule(grids)
+        if fc.chunk is not None and self._causal_sink():                    # a sink: the interval kernels, not the staircase
+            fc.chunk, fc.interval = None, self._sink_mask(seq_len, fc.chunk[0], device)
         tf = getattr(self, "_tf_state", None)                               # forward_teacher_forcing: its mask and rotary table
         if tf is not None:
             fc.chunk, fc.interval = None, tf[0]
