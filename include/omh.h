@@ -322,6 +322,21 @@ int omh_flash_attn_bwd_band_d128(const omh_attn_bwd_args* args, int32_t window_l
    (the same kernels, the same bits); a q_lens that holds Lq everywhere gives those bits too. */
 int omh_flash_attn_bwd_varlen_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, int32_t window_left,
                                    int32_t window_right, omh_stream_t stream);
+/* Additive to ABI v12 as well: the backward of one chunk of queries against a key / value cache whose earlier rows are
+   constants (WanModel.forward_chunk(grad=True): self forcing).  `args` as for omh_flash_attn_bwd_d128 with o32 REQUIRED
+   and Lk = ALL visible keys (k, v: Lk rows per sample; lse and o32 from the forward over those Lk keys).  dq is the
+   gradient over all Lk keys.  dk / dv hold  Lk - own_lo  rows per sample (batch stride dk_bs, row stride dk_rs): row r is
+   the gradient of key own_lo + r.  Keys before own_lo get no gradient and cost no dK / dV work — the dK / dV pass runs
+   the plain kernels on k + own_lo rows, v + own_lo rows with Lk - own_lo keys and the lse / delta of the full range
+   (P = exp(s - lse) of a key does not depend on which other keys the pass visits).
+   own_lo: 0 <= own_lo < Lk (OMH_E_BADARG otherwise), a multiple of 8 (OMH_E_ALIGN: the 16-byte row loads);
+   own_lo == 0 IS omh_flash_attn_bwd_d128 (the same launches, the same bits).  k_lens must be NULL when own_lo > 0
+   (OMH_E_BADARG: every key of a cache is live; a per-sample length would have to move with the pointer).
+   Phases 0..3, out_bf16 and q_prescaled as there.  The workspace (omh_flash_attn_bwd_cached_workspace_bytes) is split
+   [dQ slabs | dK, dV slabs] by the plans of the shapes each pass really runs — dQ: Lq x Lk, dK / dV: Lq x (Lk - own_lo);
+   too small or NULL: no split.  No atomics: repeatable bit for bit. */
+int omh_flash_attn_bwd_cached_d128(const omh_attn_bwd_args* args, int32_t own_lo, omh_stream_t stream);
+int64_t omh_flash_attn_bwd_cached_workspace_bytes(const omh_attn_bwd_args* args, int32_t own_lo);
 
 /* ------------------------------------------------------------------------
  * Block-sparse attention, additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout changed).
@@ -610,6 +625,19 @@ int omh_cfg_unipc_step(const float* cond, const float* uncond, const float* x, c
                        int64_t n, float guide, float sigma, int32_t use_corr,
                        float ca_last, float ca_m1, float ca_m2, float ca_mt,
                        float pb_x, float pb_mt, float pb_m1, omh_stream_t stream);
+
+/* Additive to ABI v12 (OMH_ABI_VERSION unchanged): the few-step student's sampler update between two DiT calls of a
+ * chunk rollout (causal.self_forcing_rollout).  All tensors fp32 [B, n] contiguous, any n; sigma / sigma_next are
+ * DEVICE arrays [B] (no host synchronisation), sample b = flat index / n.
+ *   backward == 0:  x0     = x - sigma[b] * v                                         -> x0
+ *                   x_next = (1 - sigma_next[b]) * x0 + sigma_next[b] * eps           -> x_next   (when x_next != NULL;
+ *                   eps and sigma_next are then required)
+ *   backward != 0:  x0     = -sigma[b] * v     (v holds the gradient w.r.t. x0: the result is the gradient w.r.t. v;
+ *                   x, eps, sigma_next and x_next are not read and may be NULL)
+ * Every product and sum is rounded on its own (no fused multiply-add): the result equals the fp32 expression above
+ * evaluated left to right, bit for bit.  x0 may alias v or x; x_next may alias x or eps. */
+int omh_flow_x0_step(const float* v, const float* x, const float* eps, const float* sigma, const float* sigma_next,
+                     float* x0, float* x_next, int32_t B, int64_t n, int32_t backward, omh_stream_t stream);
 
 /* ----------------------------------------------------------------------
  * ABI v11.  Measurement, not product: TFLOP/s this GPU sustains on back-to-back

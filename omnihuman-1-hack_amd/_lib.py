@@ -222,6 +222,8 @@ _SIGS = {
     "omh_flash_attn_takes_bounded": (i32, [C.POINTER(AttnArgs)]),
     "omh_flash_attn_bwd_d128": (i32, [C.POINTER(AttnBwdArgs), vp]),
     "omh_flash_attn_bwd_workspace_bytes": (i64, [C.POINTER(AttnBwdArgs)]),
+    "omh_flash_attn_bwd_cached_d128": (i32, [C.POINTER(AttnBwdArgs), i32, vp]),
+    "omh_flash_attn_bwd_cached_workspace_bytes": (i64, [C.POINTER(AttnBwdArgs), i32]),
     "omh_flash_attn_bwd_band_d128": (i32, [C.POINTER(AttnBwdArgs), i32, i32, vp]),
     "omh_flash_attn_bwd_varlen_d128": (i32, [C.POINTER(AttnBwdArgs), vp, i32, i32, vp]),
     "omh_flash_attn_fwd_sparse_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(BlockMaskArgs), vp]),
@@ -312,6 +314,7 @@ _SIGS = {
     "omh_stream_destroy": (i32, [vp]),
     "omh_cfg_unipc_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, i32, f32, f32, f32, f32, f32,
                                  f32, f32, vp]),
+    "omh_flow_x0_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

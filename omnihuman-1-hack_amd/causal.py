@@ -25,7 +25,7 @@ import torch
 
 __all__ = ["chunk_causal_visible", "KVCache", "RollingKVCache", "sample", "IntervalMask", "interval_visible",
            "teacher_forcing_groups",
-           "sink_window_groups", "forcing_loss"]
+           "sink_window_groups", "forcing_loss", "self_forcing_rollout"]
 
 
 def chunk_causal_visible(Lq, Lk, chunk, left_chunks=-1, q_offset=0, qlen=None, klen=None):
@@ -185,7 +185,12 @@ class KVCache:
                the pad columns by P = 0 and needs them finite);
     ``length`` tokens committed so far (a host integer; ``WanModel.forward_chunk(commit=True)`` advances it).
 
-    ``cap`` = ``max_tokens``; nothing is evicted.  Rows / columns at or past ``length`` are scratch."""
+    ``cap`` = ``max_tokens``; nothing is evicted.  Rows / columns at or past ``length`` are scratch.
+
+    ``WanModel.forward_chunk(grad=True)`` reads the committed rows again in its backward, in place.  They stay what they
+    were as long as ``length`` never fell below them in between: ``mark()`` is a token of the cache's state and
+    ``intact(mark, n_tokens)`` says whether rows [0, n_tokens) are still the ones that were committed at that mark — False
+    once ``reset()`` or ``truncate()`` cut below ``n_tokens`` afterwards (whatever was committed since)."""
 
     def __init__(self, model, batch, max_tokens, device):
         batch, cap = int(batch), int(max_tokens)
@@ -195,6 +200,8 @@ class KVCache:
         self.batch, self.cap, self.dim = batch, cap, int(model.dim)
         self.pitch = (cap + 63) // 64 * 64
         self.length = 0
+        self._gen = 0                                      # counts the cuts (reset / truncate below the length)
+        self._cuts = []                                    # [(gen, length after the cut)], lengths strictly increasing
         n = len(model.blocks)
         self.k = [torch.zeros(batch, cap, self.dim, dtype=torch.bfloat16, device=device) for _ in range(n)]
         # 64 elements of slack behind the last row: a key tile that starts at a look-back offset may read that far past it
@@ -217,10 +224,26 @@ class KVCache:
         n_tokens = int(n_tokens)
         if not 0 <= n_tokens <= self.length:
             raise ValueError(f"KVCache.truncate({n_tokens}): the cache holds {self.length} tokens")
-        self.length = n_tokens
+        self._cut(n_tokens)
 
     def reset(self):
-        self.length = 0
+        self._cut(0)
+
+    def _cut(self, n_tokens):
+        if n_tokens < self.length:
+            self._gen += 1
+            while self._cuts and self._cuts[-1][1] >= n_tokens:      # a deeper cut makes the shallower ones before it moot
+                self._cuts.pop()
+            self._cuts.append((self._gen, n_tokens))
+        self.length = n_tokens
+
+    def mark(self):
+        """A token of the cache's state for ``intact``."""
+        return self._gen
+
+    def intact(self, mark, n_tokens):
+        """Are rows [0, n_tokens) still what was committed when ``mark()`` returned ``mark``."""
+        return not any(g > mark and n < n_tokens for g, n in self._cuts)
 
 
 class RollingKVCache:
@@ -388,3 +411,74 @@ def forcing_loss(model, latents, noise, sigmas, timesteps, context, mode="teache
         tokens = F * (latents[0].shape[2] // ph) * (latents[0].shape[3] // pw)
         out = model(x_t, timesteps.repeat_interleave(fpc, dim=1), context, tokens)
     return torch.stack([(o.float() - v.to(o.device).float()).square().mean() for o, v in zip(out, target)]).mean()
+
+
+def self_forcing_rollout(model, noise, context, *, frames_per_chunk, left_chunks=-1, sigmas, timesteps, exit_step,
+                         context_t=0.0, generator=None, cache=None):
+    """Roll a batch of clips out chunk by chunk with the few-step student sampler against a ``KVCache``, as at inference,
+    and keep the graph of the LAST denoising step of every chunk (self forcing).  ``noise``: a list of B clips
+    [C, F, H, W] of one shape, F a multiple of ``frames_per_chunk`` (ValueError otherwise); ``sigmas`` / ``timesteps``: the
+    n descending levels of the schedule (sequences or 1-D tensors of one length); ``exit_step``: an int in [0, n), or one
+    per chunk — the step whose output is kept.  The student is guidance-free: one cache of batch B, fresh or the caller's
+    (``cache``; it is reset).  For chunk I in order:
+
+    1. steps j < exit under ``no_grad``: ``forward_chunk(commit=False)``, ``ops.flow_x0_step`` to x0 and on to level
+       j + 1 with fresh ``torch.randn(generator=)`` noise;
+    2. step exit: ``forward_chunk(grad=True, commit=False)`` and x0_I = x - sigma v through ``ops.flow_x0_step``, attached;
+    3. except behind the last chunk: ``forward_chunk(x0_I.detach(), context_t, commit=True)`` under ``no_grad`` — the later
+       chunks attend to its keys and values as constants.
+
+    Returns the list of B clips, fp32 [C, F, H, W], attached to the graph (the loss is the caller's).  The cache must
+    stay as it is until ``backward()`` has run (a ``reset()`` in between makes the backward raise RuntimeError).  The
+    model's ``set_causal_chunks`` setting is restored on the way out."""
+    from . import ops
+    fpc, left_chunks = int(frames_per_chunk), int(left_chunks)
+    noise = list(noise)
+    if not noise or any(u.dim() != 4 for u in noise) or len({tuple(u.shape) for u in noise}) != 1:
+        raise ValueError("self_forcing_rollout: noise is a list of clips [C, F, H, W] of one shape")
+    B, F = len(noise), noise[0].shape[1]
+    if fpc < 1 or F % fpc:
+        raise ValueError(f"self_forcing_rollout: F = {F} latent frames are no multiple of frames_per_chunk = {frames_per_chunk}")
+    sig = [float(s) for s in (sigmas.tolist() if isinstance(sigmas, torch.Tensor) else sigmas)]
+    tms = [float(t) for t in (timesteps.tolist() if isinstance(timesteps, torch.Tensor) else timesteps)]
+    n, chunks = len(sig), F // fpc
+    if n < 1 or len(tms) != n:
+        raise ValueError(f"self_forcing_rollout: {n} sigmas and {len(tms)} timesteps; one non-empty schedule expected")
+    exits = [int(exit_step)] * chunks if isinstance(exit_step, int) else [int(e) for e in exit_step]
+    if len(exits) != chunks or any(not 0 <= e < n for e in exits):
+        raise ValueError(f"self_forcing_rollout: exit_step = {exit_step}; an int in [0, {n}) or one per chunk ({chunks}) expected")
+    if cache is not None and getattr(cache, "rolling", False):
+        raise ValueError("self_forcing_rollout: a RollingKVCache evicts what the backward reads; pass a KVCache "
+                         "(left_chunks bounds the look-back)")
+    pt, ph, pw = model.patch_size
+    dev = noise[0].device
+    tokens = (F // pt) * (noise[0].shape[2] // ph) * (noise[0].shape[3] // pw)
+    prev = getattr(model, "_causal_chunks", None)
+    model.set_causal_chunks(fpc, left_chunks)
+    try:
+        if cache is None:
+            cache = KVCache(model, B, tokens, dev)
+        else:
+            cache.reset()
+        lvl = lambda vals: [torch.full((B,), v, dtype=torch.float32, device=dev) for v in vals]
+        sig_d, t_d = lvl(sig), lvl(tms)
+        t_ctx = torch.full((B,), float(context_t), dtype=torch.float32, device=dev)
+        done = []
+        for I in range(chunks):
+            x = torch.stack([u[:, I * fpc:(I + 1) * fpc] for u in noise]).float().contiguous().detach()
+            for j in range(exits[I]):
+                with torch.no_grad():
+                    v = torch.stack(model.forward_chunk(list(x.unbind(0)), t_d[j], context, cache, commit=False))
+                    eps = torch.randn(x.shape, dtype=torch.float32, device=dev, generator=generator)
+                    _, x = ops.flow_x0_step(v, x, sig_d[j], eps, sig_d[j + 1])
+            j = exits[I]
+            v = torch.stack(model.forward_chunk(list(x.unbind(0)), t_d[j], context, cache, commit=False, grad=True))
+            x0 = ops.flow_x0_step(v, x, sig_d[j])
+            done.append(x0)
+            if I + 1 < chunks:
+                with torch.no_grad():
+                    model.forward_chunk(list(x0.detach().unbind(0)), t_ctx, context, cache, commit=True)
+        clip = torch.cat(done, dim=2)                                       # [B, C, F, H, W]
+        return list(clip.unbind(0))
+    finally:
+        model._causal_chunks = prev

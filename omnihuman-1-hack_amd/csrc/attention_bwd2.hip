@@ -1261,6 +1261,85 @@ int omh_launch_attn_bwd2(const omh_attn_bwd_args& a, hipStream_t s) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- cached keys (self forcing)
+// omh_flash_attn_bwd_cached_d128 (include/omh.h): dispatch over omh_launch_attn_bwd2 — no kernel of its own.  delta and dQ
+// run on the arguments as they are (all Lk keys); the dK / dV pass runs on a copy whose k / v point at row own_lo and
+// whose Lk is the number of own keys.  What the kernels assume and why it holds on the shifted copy: K and V are read
+// through buffer descriptors built from the pointer and klen = Lk rows (tile_src: rows past the end arrive as zeros), lse
+// and delta are indexed by (b, head, query) only, and P = exp2(s - lse) of one key needs nothing of the other keys; the
+// split plans and the slab layout are computed from the copy's own Lk (bwd2_plan), each pass with its own slice of the
+// workspace.  The 32-bit offset checks of omh_launch_attn_bwd2 run per pass on the shapes of that pass.
+static int bwd2_cached_check(const omh_attn_bwd_args* args, int32_t own_lo) {
+    if (!args) return OMH_E_BADARG;
+    const omh_attn_bwd_args& a = *args;
+    if (!(a.q && a.k && a.v && a.dout && a.lse && a.delta && a.dq && a.dk && a.dv) || !a.o32) return OMH_E_BADARG;
+    if (a.B <= 0 || a.H <= 0 || a.Lq <= 0 || a.Lk <= 0) return OMH_E_BADARG;
+    if (own_lo < 0 || own_lo >= a.Lk) return OMH_E_BADARG;
+    if (own_lo & 7) return OMH_E_ALIGN;
+    if (own_lo > 0 && a.k_lens) return OMH_E_BADARG;
+    if (a.phase < 0 || a.phase > 3) return OMH_E_BADARG;
+    if ((a.q_rs & 7) || (a.k_rs & 7) || (a.o_rs & 7) || (a.q_bs & 7) || (a.k_bs & 7) || (a.o_bs & 7) || (a.dq_rs & 3) ||
+        (a.dk_rs & 3) || (a.dq_bs & 3) || (a.dk_bs & 3))
+        return OMH_E_ALIGN;
+    if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.dout | (uintptr_t)a.dq | (uintptr_t)a.dk |
+         (uintptr_t)a.dv) & 15)
+        return OMH_E_ALIGN;
+    return 0;
+}
+// the dK / dV pass's view of the arguments: keys [own_lo, Lk) as a problem of its own
+static omh_attn_bwd_args bwd2_own_keys(const omh_attn_bwd_args& a, int32_t own_lo) {
+    omh_attn_bwd_args o = a;
+    o.k = (const uint16_t*)a.k + (int64_t)own_lo * a.k_rs;
+    o.v = (const uint16_t*)a.v + (int64_t)own_lo * a.k_rs;
+    o.Lk = a.Lk - own_lo;
+    return o;
+}
+extern "C" int64_t omh_flash_attn_bwd_cached_workspace_bytes(const omh_attn_bwd_args* args, int32_t own_lo) {
+    if (!args || !args->o32 || args->B <= 0 || args->H <= 0 || args->Lq <= 0 || args->Lk <= 0) return 0;
+    if (own_lo <= 0 || own_lo >= args->Lk) return own_lo == 0 ? omh_flash_attn_bwd_workspace_bytes(args) : 0;
+    int64_t n = 0;
+    if (args->phase == 0 || args->phase == 2) n += bwd2_ws_bytes(bwd2_plan(*args, true), 1);
+    if (args->phase == 0 || args->phase == 3) n += bwd2_ws_bytes(bwd2_plan(bwd2_own_keys(*args, own_lo), false), 2);
+    return n;
+}
+extern "C" int omh_flash_attn_bwd_cached_d128(const omh_attn_bwd_args* args, int32_t own_lo, omh_stream_t stream) {
+    const int rc0 = bwd2_cached_check(args, own_lo);
+    if (rc0) return rc0;
+    if (own_lo == 0) return omh_flash_attn_bwd_d128(args, stream);      // the plain call, its launches, its bits
+    hipStream_t s = (hipStream_t)stream;
+    omh_attn_bwd_args a = *args;
+    const omh_attn_bwd_args own = bwd2_own_keys(a, own_lo);
+    const bool run_q = a.phase == 0 || a.phase == 2, run_k = a.phase == 0 || a.phase == 3;
+    const int64_t need_q = run_q ? bwd2_ws_bytes(bwd2_plan(a, true), 1) : 0;
+    const int64_t need_k = run_k ? bwd2_ws_bytes(bwd2_plan(own, false), 2) : 0;
+    const bool ws_ok = a.workspace && !((uintptr_t)a.workspace & 15) && a.workspace_bytes >= need_q + need_k;
+    omh_clear_status();
+    int rc = 0;
+    if (a.phase == 0 || a.phase == 1) {
+        omh_attn_bwd_args p = a;
+        p.phase = 1; p.workspace = nullptr; p.workspace_bytes = 0;
+        rc = omh_launch_attn_bwd2(p, s);
+        if (rc) return rc;
+    }
+    if (run_q) {                                                     // dQ over all Lk keys
+        omh_attn_bwd_args p = a;
+        p.phase = 2;
+        p.workspace = ws_ok && need_q ? a.workspace : nullptr;
+        p.workspace_bytes = ws_ok ? need_q : 0;
+        rc = omh_launch_attn_bwd2(p, s);
+        if (rc) return rc;
+    }
+    if (run_k) {                                                     // dK / dV of the own keys only
+        omh_attn_bwd_args p = own;
+        p.phase = 3;
+        p.workspace = ws_ok && need_k ? (char*)a.workspace + need_q : nullptr;      // (need_q: a multiple of 64 KiB)
+        p.workspace_bytes = ws_ok ? need_k : 0;
+        rc = omh_launch_attn_bwd2(p, s);
+        if (rc) return rc;
+    }
+    return omh_launch_status();
+}
+
 // called by omh_flash_attn_bwd_band_d128 and omh_flash_attn_bwd_varlen_d128 (attention_bwd.hip) with validated arguments
 // and o32 set: the same phases as omh_launch_attn_bwd2, on the WIN instantiations of the HIP kernels (the w64 streams are
 // full-attention only); never split (the entries decline the workspace).  VLEN: the q_lens instantiations.

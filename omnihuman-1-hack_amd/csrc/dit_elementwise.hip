@@ -599,6 +599,58 @@ void cfg_unipc_kernel(const float* __restrict__ cond, const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------ few-step student sampler step (self forcing)
+// x0 = x - sigma[b] v, x_next = (1 - sigma'[b]) x0 + sigma'[b] eps over the flat [B * n] range: float4 per thread while
+// four whole elements remain, a scalar tail behind them.  A vector may straddle two samples (n is free), so the sample of
+// every lane is found from the flat index.  Each product and sum is rounded on its own (the build's
+// -ffp-contract=fast overrides contraction pragmas, so flow_x0_one passes every product through an empty asm statement,
+// which the compiler cannot fuse across): the bits of the fp32 expression.
+// BWD: x0 = -sigma[b] v (the gradient w.r.t. v from the one w.r.t. x0).
+template <bool BWD>
+__device__ __forceinline__ void flow_x0_one(float v, float x, float e, float s, float s2, bool nxt, float& x0, float& xn) {
+    if (BWD) { x0 = -s * v; xn = 0.f; return; }
+    float sv = s * v;
+    asm volatile("" : "+v"(sv));                                     // the rounded product, not an operand to fuse
+    x0 = x - sv;
+    float a = (1.f - s2) * x0, b = s2 * e;
+    asm volatile("" : "+v"(a), "+v"(b));
+    xn = nxt ? a + b : 0.f;
+}
+template <bool BWD>
+__global__ __launch_bounds__(256)
+void flow_x0_step_kernel(const float* v, const float* x, const float* eps, const float* __restrict__ sigma,
+                         const float* __restrict__ sigma_next, float* x0, float* x_next, int64_t n, int64_t total,
+                         int vec_ok) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool nxt = !BWD && x_next != nullptr;
+    const int64_t nvec = vec_ok ? total / 4 : 0;
+    for (int64_t i = tid; i < nvec; i += stride) {
+        const int64_t e0 = 4 * i;
+        const float4 vv = *(const float4*)(v + e0);
+        const float4 xv = BWD ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(x + e0);
+        const float4 ev = nxt ? *(const float4*)(eps + e0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float va[4] = {vv.x, vv.y, vv.z, vv.w}, xa[4] = {xv.x, xv.y, xv.z, xv.w}, ea[4] = {ev.x, ev.y, ev.z, ev.w};
+        float o0[4], o1[4];
+        int64_t b = e0 / n, r = e0 - b * n;                           // one division per vector: the lanes step from it
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            while (r >= n) { r -= n; ++b; }
+            flow_x0_one<BWD>(va[k], xa[k], ea[k], sigma[b], nxt ? sigma_next[b] : 0.f, nxt, o0[k], o1[k]);
+            ++r;
+        }
+        *(float4*)(x0 + e0) = make_float4(o0[0], o0[1], o0[2], o0[3]);
+        if (nxt) *(float4*)(x_next + e0) = make_float4(o1[0], o1[1], o1[2], o1[3]);
+    }
+    for (int64_t i = 4 * nvec + tid; i < total; i += stride) {       // the tail (everything, without 16-byte pointers)
+        const int64_t b = i / n;
+        float a0, a1;
+        flow_x0_one<BWD>(v[i], BWD ? 0.f : x[i], nxt ? eps[i] : 0.f, sigma[b], nxt ? sigma_next[b] : 0.f, nxt, a0, a1);
+        x0[i] = a0;
+        if (nxt) x_next[i] = a1;
+    }
+}
+
 inline int grid_for(int64_t n, int per_block) {
     int64_t g = (n + per_block - 1) / per_block;
     return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
@@ -779,6 +831,28 @@ extern "C" int omh_cfg_unipc_step(const float* cond, const float* uncond, const 
     hipLaunchKernelGGL(cfg_unipc_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, cond, uncond, x,
                        last, m1, m2, mt_out, xc_out, x_next, n, guide, sigma, use_corr, ca_last, ca_m1, ca_m2, ca_mt,
                        pb_x, pb_mt, pb_m1);
+    return omh_launch_status();
+}
+
+extern "C" int omh_flow_x0_step(const float* v, const float* x, const float* eps, const float* sigma, const float* sigma_next,
+                                float* x0, float* x_next, int32_t B, int64_t n, int32_t backward, omh_stream_t stream) {
+    if (!v || !sigma || !x0 || B <= 0 || n <= 0) return OMH_E_BADARG;
+    if (!backward && !x) return OMH_E_BADARG;
+    if (!backward && x_next && (!eps || !sigma_next)) return OMH_E_BADARG;
+    const int64_t total = (int64_t)B * n;
+    if (((uintptr_t)v | (uintptr_t)x | (uintptr_t)eps | (uintptr_t)x0 | (uintptr_t)x_next) & 3) return OMH_E_ALIGN;
+    // float4 accesses need 16-byte pointers (those that are read or written in this mode); else every element is "tail"
+    uintptr_t al = (uintptr_t)v | (uintptr_t)x0;
+    if (!backward) al |= (uintptr_t)x | (x_next ? ((uintptr_t)x_next | (uintptr_t)eps) : 0);
+    const int vec_ok = (al & 15) == 0;
+    omh_clear_status();
+    const int grid = grid_for((total + 3) / 4, 256);
+    if (backward)
+        hipLaunchKernelGGL(flow_x0_step_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, v, x, eps, sigma,
+                           sigma_next, x0, x_next, n, total, vec_ok);
+    else
+        hipLaunchKernelGGL(flow_x0_step_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, v, x, eps, sigma,
+                           sigma_next, x0, x_next, n, total, vec_ok);
     return omh_launch_status();
 }
 

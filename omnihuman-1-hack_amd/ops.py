@@ -14,7 +14,7 @@ from ._lib import (ATTN_ALLOW_SPLIT, ATTN_SHORT_KERNEL, BIAS_M, BIAS_N, BIAS_NON
                    EPI_GELU_BWD_BF16, EPI_GELU_ERF_BF16, EPI_RESID, AttnArgs, GemmArgs, OmhError, check, lib)
 
 __all__ = ["gemm", "flash_attn", "flash_attn_func", "layernorm_modulate", "rmsnorm_rope", "cast_bf16", "patchify", "unpatchify",
-           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw",
+           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw",
            "softmax_rows", "OmhError",
            "EPI_BF16", "EPI_F32", "EPI_GELU_BF16", "EPI_GELU_ERF_BF16", "EPI_RESID", "EPI_F32_ACCUM", "BIAS_NONE", "BIAS_N", "BIAS_M"]
 
@@ -315,7 +315,7 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
 
 def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_prescaled=False, out=None, o32=None,
                    phase=0, delta=None, split=True, window=(-1, -1), q_lens=None, block_mask=None, chunk_causal=None,
-                   interval_mask=None):
+                   interval_mask=None, own_lo=None, k_bs=None):
     """Fused attention backward (include/omh.h).  q, dout: bf16 [B*Lq, H*128]; k, v: bf16 [B*Lk, H*128] (row stride
     free); lse fp32 [B, H, Lq] from ``flash_attn_raw(..., lse=)``; k_lens int32 [B] or None.
     Returns fp32 dq [B*Lq, H*128], dk, dv [B*Lk, H*128] — or, with ``out=(dq, dk, dv)`` bf16 2-D tensors (row stride
@@ -336,8 +336,24 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     ``chunk_causal``: the forward's (chunk, left_chunks, q_offset) (omh_flash_attn_bwd_chunk_d128; requires ``o32``, any
     ``q_lens``; ValueError beside a bounded ``window`` or a block mask): zero gradients as under a block mask.
     ``interval_mask``: the forward's ``causal.IntervalMask`` (omh_flash_attn_bwd_interval_d128; requires ``o32``, any
-    ``q_lens``; ValueError beside any of the other three): zero gradients as under a block mask."""
+    ``q_lens``; ValueError beside any of the other three): zero gradients as under a block mask.
+    ``own_lo`` (omh_flash_attn_bwd_cached_d128; requires ``o32``; ValueError beside ``k_lens``, ``q_lens``, a bounded
+    ``window`` or any mask): the keys before row ``own_lo`` (a multiple of 8, 0 <= own_lo < Lk) are constants — a chunk of
+    queries against a key / value cache.  dq is over all Lk keys; dk, dv have Lk - own_lo rows per sample (returned
+    fp32 [B*(Lk - own_lo), H*128], or ``out``'s bf16 tensors of that many rows), row r for key own_lo + r; the earlier keys
+    cost no dK / dV work.  ``own_lo`` = 0 is the plain call, bit for bit.
+    ``k_bs``: the batch stride of k and v in elements when it is not Lk rows (keys that sit inside a larger buffer)."""
     _dev(q, k, v, dout, lse, k_lens, o32, q_lens)
+    if own_lo is not None:
+        own_lo = int(own_lo)
+        if o32 is None:
+            raise ValueError("flash_attn_bwd: own_lo needs the forward's fp32 output (o32=)")
+        if k_lens is not None or q_lens is not None or window[0] >= 0 or window[1] >= 0 or block_mask is not None or \
+                chunk_causal is not None or interval_mask is not None:
+            raise ValueError("flash_attn_bwd: own_lo excludes k_lens, q_lens, a bounded window and every mask")
+        if not 0 <= own_lo < Lk or own_lo % 8:
+            raise ValueError(f"flash_attn_bwd: own_lo = {own_lo}; a multiple of 8 in [0, Lk = {Lk}) is expected")
+    Lown = Lk - (own_lo or 0)                                      # rows of dk / dv per sample
     im = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal, device=q.device)
     if im is not None:
         assert o32 is not None, "flash_attn_bwd: interval_mask needs the forward's fp32 output (o32=)"
@@ -379,8 +395,8 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     assert delta.dtype == torch.float32 and delta.is_contiguous() and delta.numel() == B * H * Lq
     if out is None:
         dq = torch.empty(B * Lq, d, dtype=torch.float32, device=dev)
-        dk = torch.empty(B * Lk, d, dtype=torch.float32, device=dev)
-        dv = torch.empty(B * Lk, d, dtype=torch.float32, device=dev)
+        dk = torch.empty(B * Lown, d, dtype=torch.float32, device=dev)
+        dv = torch.empty(B * Lown, d, dtype=torch.float32, device=dev)
         bf = 0
     else:
         dq, dk, dv = out
@@ -391,8 +407,8 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     assert rs(k) == rs(v)
     a = _lib.AttnBwdArgs(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(qt), _p(dot), _p(kt), _p(lse), _p(delta),
                          _p(dq), _p(dk), _p(dv), _p(k_lens), B, H, Lq, Lk,
-                         Lq * rs(q), rs(q), Lk * rs(k), rs(k), Lq * rs(dout), rs(dout), Lq * dq.stride(0), dq.stride(0),
-                         Lk * dk.stride(0), dk.stride(0), d * ldq, d * ldk, ldq, ldk,
+                         Lq * rs(q), rs(q), Lk * rs(k) if k_bs is None else int(k_bs), rs(k), Lq * rs(dout), rs(dout),
+                         Lq * dq.stride(0), dq.stride(0), Lown * dk.stride(0), dk.stride(0), d * ldq, d * ldk, ldq, ldk,
                          float(scale if scale is not None else 128 ** -0.5), int(q_prescaled), bf, _p(o32), int(phase),
                          None, 0)
     if bm is not None:
@@ -420,6 +436,13 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     if window[0] >= 0 or window[1] >= 0:
         check(lib.omh_flash_attn_bwd_band_d128(C.byref(a), int(window[0]), int(window[1]), _stream()),
               "omh_flash_attn_bwd_band_d128")
+        return dq, dk, dv
+    if own_lo is not None:
+        need = lib.omh_flash_attn_bwd_cached_workspace_bytes(C.byref(a), own_lo) if split else 0
+        if need > 0:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), need
+        check(lib.omh_flash_attn_bwd_cached_d128(C.byref(a), own_lo, _stream()), "omh_flash_attn_bwd_cached_d128")
         return dq, dk, dv
     need = lib.omh_flash_attn_bwd_workspace_bytes(C.byref(a)) if split else 0     # partial sums of the split last round
     if need > 0:
@@ -641,6 +664,55 @@ def cfg_unipc_step(cond, uncond, x, last, m1, m2, mt_out, xc_out, x_next, guide,
 
 
 # ----------------------------------------------------------------------------- VAE kernels
+def flow_x0_step(v, x, sigma, eps=None, sigma_next=None):
+    """The few-step student's sampler update (omh_flow_x0_step): ``v`` (the model's output), ``x`` fp32 of one shape
+    [B, ...]; ``sigma`` fp32 [B] on the device.  Returns x0 = x - sigma_b v — and, with ``eps`` (fp32, the shape of x) and
+    ``sigma_next`` [B], the pair (x0, x_next = (1 - sigma_next_b) x0 + sigma_next_b eps).  Differentiable w.r.t. ``v``
+    through x0 (dv = -sigma_b g, the same entry); ``x`` and ``eps`` are treated as constants and x_next carries no graph."""
+    if torch.is_grad_enabled() and v.requires_grad:
+        x0 = _FlowX0Func.apply(v, x.detach(), sigma.detach())
+        if eps is None:
+            return x0
+        with torch.no_grad():
+            return x0, _flow_x0_raw(v.detach(), x, sigma, eps, sigma_next)[1]
+    with torch.no_grad():
+        x0, xn = _flow_x0_raw(v, x, sigma, eps, sigma_next)
+    return x0 if eps is None else (x0, xn)
+
+
+def _flow_x0_raw(v, x, sigma, eps=None, sigma_next=None, backward=False):
+    _dev(v, x, sigma, eps, sigma_next)
+    B = sigma.numel()
+    for t in (v, x, eps):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == v.shape, \
+                "flow_x0_step: contiguous fp32 tensors of one shape are expected"
+    assert v.numel() % B == 0 and v.numel() > 0 and (v.dim() == 1 or v.shape[0] == B), "flow_x0_step: v [B, ...], sigma [B]"
+    assert (eps is None) == (sigma_next is None), "flow_x0_step: eps and sigma_next come together"
+    for t in (sigma, sigma_next):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
+    x0 = torch.empty_like(v)
+    xn = torch.empty_like(v) if eps is not None else None
+    check(lib.omh_flow_x0_step(_p(v), _p(x), _p(eps), _p(sigma), _p(sigma_next), _p(x0), _p(xn), B, v.numel() // B,
+                               int(backward), _stream()), "omh_flow_x0_step")
+    return x0, xn
+
+
+class _FlowX0Func(torch.autograd.Function):
+    """x0 = x - sigma_b v with the gradient w.r.t. v only (``flow_x0_step``)."""
+
+    @staticmethod
+    def forward(ctx, v, x, sigma):
+        ctx.save_for_backward(sigma)
+        return _flow_x0_raw(v.detach(), x, sigma)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (sigma,) = ctx.saved_tensors
+        return _flow_x0_raw(g.contiguous().float(), None, sigma, backward=True)[0], None, None
+
+
 def conv_pair_supported(Tin, Hin, Win, Cin2, Tout, Hout, Wout, Cout, KT, KH, KW, stride_t=1, stride_hw=1, pad_h=0, pad_w=0,
                         up2=False):
     """Would omh_conv_cl_bf16 take this layer as a split-bf16 PAIR convolution (omh_conv_args.pair; ``Cin2`` = 2 x the real

@@ -1085,7 +1085,7 @@ class WanModel(nn.Module):
         # clean half's output is cut off here: no gradient enters through it)
         return [o if o.shape[1] == F * pt else o[:, F * pt:] for o in out]
 
-    def forward_chunk(self, x, t, context, cache, frame_offset=None, commit=True, clip_fea=None, y=None):
+    def forward_chunk(self, x, t, context, cache, frame_offset=None, commit=True, clip_fea=None, y=None, grad=False):
         """One chunk of a clip against the keys and values kept from the chunks before it (the rollout of the
         frame-causal model).  ``x``: the latents [C_in, f, H, W] of ONE chunk per sample, all of one shape (the last chunk
         of a clip may have fewer frames); ``cache``: a ``causal.KVCache`` of this model and batch.  Each block projects
@@ -1100,20 +1100,50 @@ class WanModel(nn.Module):
         ``commit=False`` leaves the cache as it was (the rows behind ``length`` are scratch) — a denoising step of the
         current chunk.  Cross-attention, FFN and head as in ``forward``.  Tokens per chunk must be a multiple of 8 (the
         16-byte stores into the cache and the look-back offset): ValueError otherwise, and when the chunk does not fit.
-        Inference only: RuntimeError with grad enabled and parameters or inputs that require it.
+        Inference only by default: RuntimeError with grad enabled and parameters or inputs that require it.
+
+        ``grad=True`` (self forcing: ``causal.self_forcing_rollout``): with grad enabled and a trainable parameter or an
+        input that requires grad the call is an autograd node chain like ``forward``'s (model_train.forward_chunk_train) —
+        the same launches, the bits of the inference call on the same cache state.  The gradient reaches every parameter
+        ``forward`` trains and x, t, context, y, clip_fea; the chunk's keys and values get theirs through its own rows
+        only — the cached rows [lo, length) are constants.  The chunk's own k and V are kept with the activations (the
+        next call overwrites them in the cache); the cached rows are read in place by the backward, which raises
+        RuntimeError when the cache was ``reset()`` or ``truncate()``d below them in between.  Activations are always
+        kept (a re-run would need the cache as it was): ``use_checkpoint`` is ignored and ``checkpoint_policy="always"``
+        is a ValueError, as are a ``RollingKVCache`` (its slots are evicted before the backward runs: use ``KVCache``
+        with ``left_chunks``), hence ``sink_chunks`` > 0, and a 2-D ``t``.  Without anything that requires grad it is the
+        inference call.
         Returns the list of fp32 [C_out, f, H, W]."""
+        if grad:
+            # (the refusals come before anything touches a device)
+            if getattr(cache, "rolling", False):
+                raise ValueError("forward_chunk(grad=True): a RollingKVCache evicts slots the backward still reads; use a "
+                                 "causal.KVCache with set_causal_chunks(frames_per_chunk, left_chunks)")
+            if self._causal_sink():
+                raise ValueError("forward_chunk(grad=True): sink_chunks > 0 needs a RollingKVCache, which has no gradient "
+                                 "path; use set_causal_chunks(frames_per_chunk, left_chunks) and a causal.KVCache")
+            if isinstance(t, torch.Tensor) and t.dim() != 1:
+                raise ValueError(f"forward_chunk: t of shape {tuple(t.shape)}; one timestep per sample, [B], is expected")
+            from .model_train import check_chunk_grad_policy
+            check_chunk_grad_policy(self)                  # checkpoint_policy="always": ValueError
         device = self.patch_embedding.weight.device
         if device.type != "cuda":
             raise ops.OmhError("WanModel.forward_chunk runs on the MI355X only (no CPU fallback): move the model "
                                "to a GPU device")
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
                                         or self._input_requires_grad(x, t, context, clip_fea, y, None)):
-            raise RuntimeError("forward_chunk is an inference path (no gradient flows through the cache): call it "
-                               "under torch.no_grad() with inputs that do not require grad")
+            if not grad:
+                raise RuntimeError("forward_chunk is an inference path (no gradient flows through the cache): call it "
+                                   "under torch.no_grad() with inputs that do not require grad")
+            if isinstance(context, ContextState):
+                raise ValueError("a ContextState is an inference-time cache: pass the raw context when training")
+            from .model_train import forward_chunk_train
+            return forward_chunk_train(self, list(x), t, context, cache, frame_offset, commit, clip_fea, y)
         with torch.no_grad():
             return self._forward_chunk(list(x), t, context, cache, frame_offset, commit, clip_fea, y)
 
-    def _forward_chunk(self, x, t, context, cache, frame_offset, commit, clip_fea, y):
+    def _chunk_geometry(self, x, t, cache, frame_offset):
+        """The argument rules of ``forward_chunk`` -> (C tokens of the chunk, first visible key lo, frame_offset)."""
         if t.dim() != 1:
             raise ValueError(f"forward_chunk: t of shape {tuple(t.shape)}; one timestep per sample, [B], is expected")
         if len({tuple(u.shape) for u in x}) != 1:
@@ -1157,6 +1187,15 @@ class WanModel(nn.Module):
         if frame_offset < 0 or frame_offset + f > self.freqs.shape[0]:
             raise ValueError(f"forward_chunk: frames [{frame_offset}, {frame_offset + f}) leave the rotary table "
                              f"({self.freqs.shape[0]} frames)")
+        return C, lo, frame_offset
+
+    def _forward_chunk(self, x, t, context, cache, frame_offset, commit, clip_fea, y):
+        C, lo, frame_offset = self._chunk_geometry(x, t, cache, frame_offset)
+        L0 = cache.length
+        rolling = getattr(cache, "rolling", False)
+        if rolling:
+            tpf = (x[0].shape[2] // self.patch_size[1]) * (x[0].shape[3] // self.patch_size[2])
+            Ct = self._causal_chunks[0] * tpf
         xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, C, clip_fea, y)
         fc.chunk = None                                    # the cache IS the causal structure: plain attention over it
         fc.interval = None
