@@ -89,23 +89,24 @@ struct AttnSplit {
 // test against the interval every live row sees whole).  A workgroup's work grows with its position, so the query tiles
 // of a head are handed out last tile first: the long ones start first and the launch ends on short ones.  The divisions
 // happen here, once per workgroup and once per row.  Never split.
-// IVL (with WIN): an interval mask (include/omh.h omh_interval_mask; omh_common.h IvlTab, the q_iv table) — again the
-// band's machinery, with TWO key intervals per row, read from the row of its group.  The workgroup reads the table rows
-// of the groups its live rows span (scalar loads, before the loop), runs the tiles inside the hull of their first
-// intervals, then — `gap` tiles further — those inside the hull of their second ones (one range when the two touch), and
-// masks per element only the tiles that are not inside an interval every one of those groups shares.  Never split.
+// RUNS > 0 (with WIN; "IVL" below): an interval mask with RUNS = 2 (include/omh.h omh_interval_mask) or 3
+// (omh_interval3_mask) key intervals per row (omh_common.h IvlTab, the q_iv table, rows of 2 RUNS ints) — again the band's
+// machinery, the intervals read from the row of the query's group.  The workgroup reads the table rows of the groups its
+// live rows span (scalar loads, before the loop), runs the tiles inside the hulls of their first, second, ... intervals —
+// up to RUNS ranges of tiles with a jump between them, one range where two touch (omh_ivl_tiles) — and masks per element
+// only the tiles that are not inside the intersection of the i-th intervals of those groups, any i.  Never split.
 // The query tiles keep their natural order: last tile first, CHK's order, lost time under teacher forcing.
-// IV3 (with IVL): the three-run form (omh_interval3_mask; omh_common.h Ivl3Span / omh_ivl3_tiles) — table rows of 6 ints,
-// THREE key intervals per row, up to three tile ranges with two jumps (`t_gap` behind tile n_first, `t_gap1` behind tile
-// n_second of the loop), and the unmasked body for a tile inside the intersection of the i-th intervals, any i.
-template <bool WIN, bool BLK = false, bool CHK = false, bool IVL = false, bool IV3 = false>
+// RUNS = 0: no interval mask.
+template <bool WIN, bool BLK = false, bool CHK = false, int RUNS = 0>
 __global__ __launch_bounds__(256, 2)
 void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk, const BlkList bl,
                                 const ChunkRule ck) {
     static_assert(!(WIN && BLK), "a block mask excludes the band");
     static_assert(!CHK || WIN, "the staircase runs on the band's masking");
+    constexpr bool IVL = RUNS > 0;
+    constexpr int NR = IVL ? RUNS : 2;                    // (the interval types need a run count where nothing uses them)
+    static_assert(RUNS == 0 || RUNS == 2 || RUNS == 3, "two-run and three-run tables");
     static_assert(!IVL || (WIN && !CHK), "an interval mask runs on the band's masking, in place of the other rules");
-    static_assert(!IV3 || IVL, "the three-run form is an interval mask");
     const IvlTab iv = omh_ivl_tab(bl);                    // IVL: the table arrives in the BlkList argument
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (KT_BYTES + VT_BYTES)];
 
@@ -132,9 +133,10 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     int t_first = 0, n_tiles = n_tiles_all;
     int band_shift = 0;                                   // WIN: key index of the band's centre for query row 0
     int whole_lo = 0, whole_hi = -1;                      // CHK: the keys EVERY live row of the workgroup sees
-    int whole1_lo = 0, whole1_hi = -1;                    // IVL: ... through its second interval (whole_lo / hi: the first)
-    int n_first = 0, t_gap = 0;                           // IVL: tiles of the first range, tiles skipped behind it
-    int whole2_lo = 0, whole2_hi = -1, n_second = 0, t_gap1 = 0;   // IV3: the third interval, tiles of the first two ranges, the second jump
+    int whole[2 * NR];                                    // IVL: [lo, hi] of those they all see through their i-th interval
+#pragma unroll
+    for (int i = 0; i < NR; ++i) { whole[2 * i] = 0; whole[2 * i + 1] = -1; }
+    IvlTiles<NR> plan = {};                               // IVL: the tile ranges of the loop
     if constexpr (WIN) {
         int qlen = p.q_lens ? p.q_lens[b] : p.Lq;
         qlen = min(max(qlen, 0), p.Lq);
@@ -143,24 +145,8 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         int lo, hi;
         if constexpr (IVL) {
             lo = 0; hi = -1;
-            if constexpr (IV3) {
-                if (q1 >= q0) {
-                    int w[6];
-                    const Ivl3Tiles it = omh_ivl3_tiles(iv, q0, q1, klen, KB, w);
-                    whole_lo = w[0]; whole_hi = w[1]; whole1_lo = w[2]; whole1_hi = w[3]; whole2_lo = w[4]; whole2_hi = w[5];
-                    t_first = it.t_first; n_first = it.n0; t_gap = it.gap0; n_second = it.n1; t_gap1 = it.gap1; n_tiles = it.n_tiles;
-                } else {
-                    n_tiles = 0;
-                }
-            } else
-            if (q1 >= q0) {
-                int w0[2], w1[2];
-                const IvlTiles it = omh_ivl_tiles(iv, q0, q1, klen, KB, w0, w1);
-                whole_lo = w0[0]; whole_hi = w0[1]; whole1_lo = w1[0]; whole1_hi = w1[1];
-                t_first = it.t_first; n_first = it.n0; t_gap = it.gap; n_tiles = it.n_tiles;
-            } else {
-                n_tiles = 0;
-            }
+            if (q1 >= q0) plan = omh_ivl_tiles<NR>(iv, q0, q1, klen, KB, whole);
+            t_first = plan.t_first; n_tiles = plan.n_tiles;
         } else if constexpr (CHK) {
             const int c0 = (ck.off + q0) / ck.chunk, c1 = (ck.off + max(q1, 0)) / ck.chunk;   // chunks of the first / last live row
             lo = ck.left < 0 ? 0 : max(0, (c0 - ck.left) * ck.chunk);
@@ -213,12 +199,9 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     const int q_row = qt * QB + wave * 32 + li;
     const int q_ld = min(q_row, p.Lq - 1);
     int key_lo = 0, key_hi = klen - 1;                    // WIN: this lane's (query row's) band of keys
-    IvlSpan span = {0, 0, 0, 0};                          // IVL: this lane's two intervals of keys
-    Ivl3Span span3 = {0, 0, 0, 0, 0, 0};                  // IV3: this lane's three intervals of keys
-    if constexpr (IV3) {
-        span3 = omh_ivl3_row(iv, q_row / iv.group, klen);
-    } else if constexpr (IVL) {
-        span = omh_ivl_row(iv, q_row / iv.group, klen);
+    IvlSpan<NR> span = {};                                // IVL: this lane's intervals of keys
+    if constexpr (IVL) {
+        span = omh_ivl_row<NR>(iv, q_row / iv.group, klen);
     } else if constexpr (CHK) {
         const int ci = (ck.off + q_row) / ck.chunk;                           // this row's chunk
         if (ck.left >= 0) key_lo = max(0, (ci - ck.left) * ck.chunk);
@@ -299,20 +282,14 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     const int krow_l = swap_bits23(li);
     for (int tt = 0; tt < n_tiles; ++tt) {
         const int buf = tt & 1;
-        int t = t_first + tt;
-        if constexpr (IVL) t += tt >= n_first ? t_gap : 0;
-        if constexpr (IV3) t += tt >= n_second ? t_gap1 : 0;
+        int t = IVL ? plan.tile(tt) : t_first + tt;
         if constexpr (BLK) {
             t = t_cur;
             OMH_GLOAD(t_nxt)
             t_cur = t_nxt;
             t_nxt = blk_tile(min(tt + 2, n_tiles - 1));   // a tile ahead of its loads
-        } else if constexpr (IV3) {
-            const int nx = min(tt + 1, n_tiles - 1);
-            OMH_GLOAD(t_first + nx + (nx >= n_first ? t_gap : 0) + (nx >= n_second ? t_gap1 : 0))
         } else if constexpr (IVL) {
-            const int nx = min(tt + 1, n_tiles - 1);
-            OMH_GLOAD(t_first + nx + (nx >= n_first ? t_gap : 0))
+            OMH_GLOAD(plan.tile(min(tt + 1, n_tiles - 1)))
         } else {
         OMH_GLOAD(t_first + min(tt + 1, n_tiles - 1))   // unconditional: keeps the staging registers out of scratch
         }
@@ -337,17 +314,20 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
         const int kv0 = t * KB;
         // CHK: a tile inside [whole_lo, whole_hi] needs no mask for a live row (rows at or past qlen are written as zeros
         // whatever they accumulate): most tiles of a long look-back
-        if (IVL && ((kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi) || (kv0 >= whole1_lo && kv0 + KB - 1 <= whole1_hi) ||
-                    (IV3 && kv0 >= whole2_lo && kv0 + KB - 1 <= whole2_hi))) {
-            // inside an interval every live row of the workgroup sees (cut at klen): nothing to mask
+        bool in_whole = false;                            // IVL: inside an interval every live row of the workgroup sees (cut at klen)
+        if constexpr (IVL) {
+#pragma unroll
+            for (int i = 0; i < NR; ++i) in_whole = in_whole || (kv0 >= whole[2 * i] && kv0 + KB - 1 <= whole[2 * i + 1]);
+        }
+        if (IVL && in_whole) {
+            // nothing to mask
         } else if constexpr (IVL) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kv0 + kb * 32 + ((r >> 3) << 4) + lh * 8 + (r & 7);
-                    if constexpr (IV3) s[kb][r] = span3.sees(key) ? s[kb][r] : -INFINITY;
-                    else if (!span.sees(key)) s[kb][r] = -INFINITY;
+                    s[kb][r] = span.sees(key) ? s[kb][r] : -INFINITY;
                 }
         } else
         if (WIN && !(CHK && kv0 >= whole_lo && kv0 + KB - 1 <= whole_hi)) {   // (key_hi <= klen - 1: the band mask covers the sequence end too)
@@ -628,91 +608,67 @@ extern "C" int omh_flash_attn_fwd_d128_bounded(const omh_attn_args* args, const 
     return flash_attn_fwd_d128(args, qk_norm2_max, stream);
 }
 
-// Additive to ABI v12: the forward under a block mask (include/omh.h).  The short-sequence kernel's BLK instantiation,
-// whatever the shape: no long-sequence stream, no split, no bounded stream.  A NULL mask is the plain entry.
+// The masked forward entries (block mask, staircase, interval masks; all additive to ABI v12): the short-sequence kernel's
+// instantiation for mask kind M (omh_common.h), whatever the shape — no long-sequence stream, no split, no bounded stream.
+// `mask_check(a, bl, ck)` checks the entry's mask against the shapes and fills the kernel argument it travels in.  The
+// order of the checks is part of the ABI: arguments, band unset, mask, q_lens.
+template <typename M, typename MaskCheck>
+static int attn_fwd_masked(const omh_attn_args* args, omh_stream_t stream, MaskCheck&& mask_check) {
+    const int rc0 = attn_fwd_check(args);
+    if (rc0) return rc0;
+    const omh_attn_args& a = *args;
+    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
+    BlkList bl = {};
+    ChunkRule ck = {};
+    const int rc1 = mask_check(a, bl, ck);
+    if (rc1) return rc1;
+    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
+    const int q_tiles = (a.Lq + QB - 1) / QB;
+    const int nwg = q_tiles * a.H * a.B;
+    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
+    omh_clear_status();
+    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<M::WIN, M::BLK, M::CHK, M::RUNS>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a,
+                       q_tiles, wk, bl, ck);
+    return omh_launch_status();
+}
+
+// the forward under a block mask (include/omh.h).  A NULL mask is the plain entry.
 extern "C" int omh_flash_attn_fwd_sparse_d128(const omh_attn_args* args, const omh_block_mask* mask, omh_stream_t stream) {
     if (!mask) return omh_flash_attn_fwd_d128(args, stream);
-    const int rc0 = attn_fwd_check(args);
-    if (rc0) return rc0;
-    const omh_attn_args& a = *args;
-    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
-    const int rc1 = omh_block_mask_check(mask, a.H, a.Lq, a.Lk);
-    if (rc1) return rc1;
-    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
-    const int q_tiles = (a.Lq + QB - 1) / QB;
-    const int nwg = q_tiles * a.H * a.B;
-    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
-    const BlkList bl = {mask->row_cnt, mask->row_idx, mask->heads, mask->q_blocks, mask->k_blocks};
-    omh_clear_status();
-    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles, wk, bl, ChunkRule{});
-    return omh_launch_status();
+    return attn_fwd_masked<MaskBlocks>(args, stream, [&](const omh_attn_args& a, BlkList& bl, ChunkRule&) {
+        bl = BlkList{mask->row_cnt, mask->row_idx, mask->heads, mask->q_blocks, mask->k_blocks};
+        return omh_block_mask_check(mask, a.H, a.Lq, a.Lk);
+    });
 }
 
-// Additive to ABI v12: the forward under the chunk-causal staircase (include/omh.h).  The short-sequence kernel's CHK
-// instantiation, whatever the shape: no long-sequence stream, no split, no bounded stream.
+// the forward under the chunk-causal staircase (include/omh.h)
 extern "C" int omh_flash_attn_fwd_chunk_d128(const omh_attn_args* args, const omh_chunk_causal* rule, omh_stream_t stream) {
     if (!rule) return OMH_E_BADARG;
-    const int rc0 = attn_fwd_check(args);
-    if (rc0) return rc0;
-    const omh_attn_args& a = *args;
-    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
-    ChunkRule ck;
-    const int rc1 = omh_chunk_rule(rule, a.Lq, a.Lk, &ck);
-    if (rc1) return rc1;
-    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
-    const int q_tiles = (a.Lq + QB - 1) / QB;
-    const int nwg = q_tiles * a.H * a.B;
-    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
-    omh_clear_status();
-    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<true, false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles, wk,
-                       BlkList{}, ck);
-    return omh_launch_status();
+    return attn_fwd_masked<MaskStairs>(args, stream, [&](const omh_attn_args& a, BlkList&, ChunkRule& ck) {
+        return omh_chunk_rule(rule, a.Lq, a.Lk, &ck);
+    });
 }
 
-// Additive to ABI v12: the forward under an interval mask (include/omh.h).  The short-sequence kernel's IVL
-// instantiation, whatever the shape: no long-sequence stream, no split, no bounded stream.
+// the forward under an interval mask of RUNS key intervals per row (include/omh.h: omh_interval_mask, omh_interval3_mask)
+template <int RUNS, typename Mask>
+static int attn_fwd_interval(const omh_attn_args* args, const Mask* mask, omh_stream_t stream) {
+    if (!mask) return OMH_E_BADARG;
+    return attn_fwd_masked<MaskIntervals<RUNS>>(args, stream, [&](const omh_attn_args& a, BlkList& bl, ChunkRule&) {
+        bl = omh_ivl_arg(mask->q_iv, mask->group, mask->q_groups, mask->k_groups);
+        return omh_interval_mask_check(mask, a.Lq, a.Lk);
+    });
+}
 extern "C" int omh_flash_attn_fwd_interval_d128(const omh_attn_args* args, const omh_interval_mask* mask, omh_stream_t stream) {
-    if (!mask) return OMH_E_BADARG;
-    const int rc0 = attn_fwd_check(args);
-    if (rc0) return rc0;
-    const omh_attn_args& a = *args;
-    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
-    const int rc1 = omh_interval_mask_check(mask, a.Lq, a.Lk);
-    if (rc1) return rc1;
-    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
-    const int q_tiles = (a.Lq + QB - 1) / QB;
-    const int nwg = q_tiles * a.H * a.B;
-    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
-    omh_clear_status();
-    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<true, false, false, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, q_tiles,
-                       wk, omh_ivl_arg(mask->q_iv, mask->group, mask->q_groups, mask->k_groups), ChunkRule{});
-    return omh_launch_status();
+    return attn_fwd_interval<2>(args, mask, stream);
 }
-
-// Additive to ABI v12: the forward under a three-run interval mask (include/omh.h): the IV3 instantiation, otherwise
-// omh_flash_attn_fwd_interval_d128.
 extern "C" int omh_flash_attn_fwd_interval3_d128(const omh_attn_args* args, const omh_interval3_mask* mask, omh_stream_t stream) {
-    if (!mask) return OMH_E_BADARG;
-    const int rc0 = attn_fwd_check(args);
-    if (rc0) return rc0;
-    const omh_attn_args& a = *args;
-    if (!omh_mask_window_unset(a.window_left, a.window_right)) return OMH_E_BADARG;
-    const int rc1 = omh_interval3_mask_check(mask, a.Lq, a.Lk);
-    if (rc1) return rc1;
-    if ((uintptr_t)a.q_lens & 3) return OMH_E_ALIGN;
-    const int q_tiles = (a.Lq + QB - 1) / QB;
-    const int nwg = q_tiles * a.H * a.B;
-    AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
-    omh_clear_status();
-    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<true, false, false, true, true>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a,
-                       q_tiles, wk, omh_ivl_arg(mask->q_iv, mask->group, mask->q_groups, mask->k_groups), ChunkRule{});
-    return omh_launch_status();
+    return attn_fwd_interval<3>(args, mask, stream);
 }
 
-// The two tables of an omh_interval_mask from its bool matrix (a host function: no device is touched).  Row g of q_iv:
-// the at most two runs of true in row g of vis, as half-open intervals; k_iv: the same for the columns.
-// (`max_runs` = 2 or 3: the row holds 2 max_runs ints; unused slots are empty intervals at the end of the last run)
-static int ivl_runs(const uint8_t* v, int n, int64_t stride, int32_t* out, int max_runs = 2) {
+// The two tables of an interval mask from its bool matrix (host functions: no device is touched).  Row g of q_iv: the at
+// most `max_runs` runs of true in row g of vis, as half-open intervals; k_iv: the same for the columns.
+// (the row holds 2 max_runs ints; unused slots are empty intervals at the end of the last run)
+static int ivl_runs(const uint8_t* v, int n, int64_t stride, int32_t* out, int max_runs) {
     int runs = 0;
     for (int i = 0; i < 2 * max_runs; ++i) out[i] = 0;
     for (int j = 0; j < n; ++j) {
@@ -727,20 +683,19 @@ static int ivl_runs(const uint8_t* v, int n, int64_t stride, int32_t* out, int m
     for (int r = runs > 0 ? runs : 1; r < max_runs; ++r) out[2 * r] = out[2 * r + 1] = out[2 * r - 1];   // hi <= lo = hi: empty
     return 0;
 }
-extern "C" int omh_interval_mask_tables(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv) {
+static int ivl_tables(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv, int max_runs) {
     if (!vis || !q_iv || !k_iv || q_groups < 1 || k_groups < 1) return OMH_E_BADARG;
     for (int g = 0; g < q_groups; ++g)
-        if (ivl_runs(vis + (int64_t)g * k_groups, k_groups, 1, q_iv + 4 * (int64_t)g)) return OMH_E_BADARG;
+        if (ivl_runs(vis + (int64_t)g * k_groups, k_groups, 1, q_iv + 2 * max_runs * (int64_t)g, max_runs)) return OMH_E_BADARG;
     for (int g = 0; g < k_groups; ++g)
-        if (ivl_runs(vis + g, q_groups, k_groups, k_iv + 4 * (int64_t)g)) return OMH_E_BADARG;
+        if (ivl_runs(vis + g, q_groups, k_groups, k_iv + 2 * max_runs * (int64_t)g, max_runs)) return OMH_E_BADARG;
     return 0;
 }
-// The three-run tables (rows of 6 ints) of an omh_interval3_mask: a fourth run in a row or a column is OMH_E_BADARG.
+// omh_interval_mask: rows of 4 ints, a third run in a row or a column is OMH_E_BADARG
+extern "C" int omh_interval_mask_tables(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv) {
+    return ivl_tables(vis, q_groups, k_groups, q_iv, k_iv, 2);
+}
+// omh_interval3_mask: rows of 6 ints, a fourth run is OMH_E_BADARG
 extern "C" int omh_interval_mask_tables3(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv) {
-    if (!vis || !q_iv || !k_iv || q_groups < 1 || k_groups < 1) return OMH_E_BADARG;
-    for (int g = 0; g < q_groups; ++g)
-        if (ivl_runs(vis + (int64_t)g * k_groups, k_groups, 1, q_iv + 6 * (int64_t)g, 3)) return OMH_E_BADARG;
-    for (int g = 0; g < k_groups; ++g)
-        if (ivl_runs(vis + g, q_groups, k_groups, k_iv + 6 * (int64_t)g, 3)) return OMH_E_BADARG;
-    return 0;
+    return ivl_tables(vis, q_groups, k_groups, q_iv, k_iv, 3);
 }

@@ -411,27 +411,32 @@ static int bwd2_check(const omh_attn_bwd_args& a) {
     return 0;
 }
 
-extern "C" int omh_flash_attn_bwd_band_d128(const omh_attn_bwd_args* args, int32_t window_left, int32_t window_right,
-                                            omh_stream_t stream) {
+// The masked entries' shared prologue and epilogue: the pointer rules, q_lens' alignment (NULL where the entry has none),
+// the round-3 argument rules, then `launch()` — the entry's mask check followed by its omh_launch_attn_bwd2_* call, 0 or
+// the error code.  The order of the checks is part of the ABI.
+template <typename Launch>
+static int bwd_masked_entry(const omh_attn_bwd_args* args, const int32_t* q_lens, Launch&& launch) {
     if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
+    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
     const int rc0 = bwd2_check(*args);
     if (rc0) return rc0;
-    omh_clear_status();
-    const int rc = omh_launch_attn_bwd2_band(*args, window_left, window_right, nullptr, (hipStream_t)stream);
+    const int rc = launch();
     return rc ? rc : omh_launch_status();
+}
+
+extern "C" int omh_flash_attn_bwd_band_d128(const omh_attn_bwd_args* args, int32_t window_left, int32_t window_right,
+                                            omh_stream_t stream) {
+    return omh_flash_attn_bwd_varlen_d128(args, nullptr, window_left, window_right, stream);
 }
 
 // the band entry with the forward's q_lens: the same argument rules; q_lens is a device pointer the kernels clamp to
 // [0, Lq] themselves (NULL: the band entry's kernels)
 extern "C" int omh_flash_attn_bwd_varlen_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, int32_t window_left,
                                               int32_t window_right, omh_stream_t stream) {
-    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
-    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
-    const int rc0 = bwd2_check(*args);
-    if (rc0) return rc0;
-    omh_clear_status();
-    const int rc = omh_launch_attn_bwd2_band(*args, window_left, window_right, q_lens, (hipStream_t)stream);
-    return rc ? rc : omh_launch_status();
+    return bwd_masked_entry(args, q_lens, [&] {
+        omh_clear_status();
+        return omh_launch_attn_bwd2_band(*args, window_left, window_right, q_lens, (hipStream_t)stream);
+    });
 }
 
 // the backward under a block mask (include/omh.h): the varlen entry's argument rules plus the mask's; a NULL mask IS the
@@ -439,61 +444,45 @@ extern "C" int omh_flash_attn_bwd_varlen_d128(const omh_attn_bwd_args* args, con
 extern "C" int omh_flash_attn_bwd_sparse_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_block_mask* mask,
                                               omh_stream_t stream) {
     if (!mask) return omh_flash_attn_bwd_varlen_d128(args, q_lens, -1, -1, stream);
-    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
-    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
-    const int rc0 = bwd2_check(*args);
-    if (rc0) return rc0;
-    const int rc1 = omh_block_mask_check(mask, args->H, args->Lq, args->Lk);
-    if (rc1) return rc1;
-    omh_clear_status();
-    const int rc = omh_launch_attn_bwd2_sparse(*args, q_lens, *mask, (hipStream_t)stream);
-    return rc ? rc : omh_launch_status();
+    return bwd_masked_entry(args, q_lens, [&] {
+        const int rc1 = omh_block_mask_check(mask, args->H, args->Lq, args->Lk);
+        if (rc1) return rc1;
+        omh_clear_status();
+        return omh_launch_attn_bwd2_sparse(*args, q_lens, *mask, (hipStream_t)stream);
+    });
 }
 
 // the backward under the chunk-causal staircase (include/omh.h): the varlen entry's argument rules plus the rule's
 extern "C" int omh_flash_attn_bwd_chunk_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_chunk_causal* rule,
                                              omh_stream_t stream) {
     if (!rule) return OMH_E_BADARG;
-    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
-    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
-    const int rc0 = bwd2_check(*args);
-    if (rc0) return rc0;
-    ChunkRule ck;
-    const int rc1 = omh_chunk_rule(rule, args->Lq, args->Lk, &ck);
-    if (rc1) return rc1;
-    omh_clear_status();
-    const int rc = omh_launch_attn_bwd2_chunk(*args, q_lens, ck, (hipStream_t)stream);
-    return rc ? rc : omh_launch_status();
+    return bwd_masked_entry(args, q_lens, [&] {
+        ChunkRule ck;
+        const int rc1 = omh_chunk_rule(rule, args->Lq, args->Lk, &ck);
+        if (rc1) return rc1;
+        omh_clear_status();
+        return omh_launch_attn_bwd2_chunk(*args, q_lens, ck, (hipStream_t)stream);
+    });
 }
 
-// the backward under an interval mask (include/omh.h): the varlen entry's argument rules plus the mask's
+// the backward under an interval mask (include/omh.h; two-run and three-run): the varlen entry's argument rules plus the mask's
+template <typename Mask, typename Launch>
+static int bwd_interval_entry(const omh_attn_bwd_args* args, const int32_t* q_lens, const Mask* mask, omh_stream_t stream, Launch launch) {
+    if (!mask) return OMH_E_BADARG;
+    return bwd_masked_entry(args, q_lens, [&] {
+        const int rc1 = omh_interval_mask_check(mask, args->Lq, args->Lk);
+        if (rc1) return rc1;
+        omh_clear_status();
+        return launch(*args, q_lens, *mask, (hipStream_t)stream);
+    });
+}
 extern "C" int omh_flash_attn_bwd_interval_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_interval_mask* mask,
                                                 omh_stream_t stream) {
-    if (!mask) return OMH_E_BADARG;
-    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
-    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
-    const int rc0 = bwd2_check(*args);
-    if (rc0) return rc0;
-    const int rc1 = omh_interval_mask_check(mask, args->Lq, args->Lk);
-    if (rc1) return rc1;
-    omh_clear_status();
-    const int rc = omh_launch_attn_bwd2_interval(*args, q_lens, *mask, (hipStream_t)stream);
-    return rc ? rc : omh_launch_status();
+    return bwd_interval_entry(args, q_lens, mask, stream, omh_launch_attn_bwd2_interval);
 }
-
-// the backward under a three-run interval mask (include/omh.h): the same rules on the IV3 instantiations
 extern "C" int omh_flash_attn_bwd_interval3_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_interval3_mask* mask,
                                                  omh_stream_t stream) {
-    if (!mask) return OMH_E_BADARG;
-    if (!args || !bwd_ptrs_set(*args) || !args->o32) return OMH_E_BADARG;
-    if ((uintptr_t)q_lens & 3) return OMH_E_ALIGN;
-    const int rc0 = bwd2_check(*args);
-    if (rc0) return rc0;
-    const int rc1 = omh_interval3_mask_check(mask, args->Lq, args->Lk);
-    if (rc1) return rc1;
-    omh_clear_status();
-    const int rc = omh_launch_attn_bwd2_interval3(*args, q_lens, *mask, (hipStream_t)stream);
-    return rc ? rc : omh_launch_status();
+    return bwd_interval_entry(args, q_lens, mask, stream, omh_launch_attn_bwd2_interval3);
 }
 
 extern "C" int omh_flash_attn_bwd_d128(const omh_attn_bwd_args* args, omh_stream_t stream) {

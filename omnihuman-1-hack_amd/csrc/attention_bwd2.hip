@@ -52,13 +52,10 @@ __device__ __forceinline__ uint4 ld16(const uint16_t* p, bool ok) {
 //         product): P = exp2(sc s), dS = P dp — the fma and the subtraction per score are gone
 //   MASK  1: keys key_base + 16 (r >> 3) + (r & 7) at or past `klen` get P = 0 (the dQ kernel's last key tile only);
 //         2: keys outside [key_lo, klen] get P = 0 (the band kernels: `klen` is then the row's last key of its band)
-//         3: keys outside [key_lo, key_lo + klen) U [lo1, lo1 + len1) get P = 0 (the interval-mask kernels: `klen` is then
-//            the LENGTH of the row's first interval; a length <= 0 is an empty interval)
-//         4: MASK 3 with a third interval [lo2, lo2 + len2) (the three-run interval-mask kernels)
-template <bool PRE, bool FOLD, int MASK>
+//         3: keys outside the intervals of `span` get P = 0 (the interval-mask kernels: the row's RUNS intervals)
+template <bool PRE, bool FOLD, int MASK, int RUNS = 2>
 __device__ __forceinline__ void p_and_ds(const f32x16& s, const f32x16& dp, float lv, float dl, int key_base, int klen,
-                                         float sc, bf16x8* pf, bf16x8* dsf, int key_lo = 0, int lo1 = 0, int len1 = 0,
-                                         int lo2 = 0, int len2 = 0) {
+                                         float sc, bf16x8* pf, bf16x8* dsf, int key_lo = 0, const IvlSpan<RUNS>& span = {}) {
     float p[16], ds[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -67,9 +64,7 @@ __device__ __forceinline__ void p_and_ds(const f32x16& s, const f32x16& dp, floa
         const int key = key_base + ((r >> 3) << 4) + (r & 7);
         if (MASK == 1) p[r] = (key < klen) ? p[r] : 0.f;
         if (MASK == 2) p[r] = (key >= key_lo && key <= klen) ? p[r] : 0.f;   // (a select: exp2 of a score outside may be inf)
-        if (MASK == 3) p[r] = ((unsigned)(key - key_lo) < (unsigned)klen || (unsigned)(key - lo1) < (unsigned)len1) ? p[r] : 0.f;
-        if (MASK == 4) p[r] = ((unsigned)(key - key_lo) < (unsigned)klen || (unsigned)(key - lo1) < (unsigned)len1 ||
-                               (unsigned)(key - lo2) < (unsigned)len2) ? p[r] : 0.f;
+        if (MASK == 3) p[r] = span.sees(key) ? p[r] : 0.f;
         ds[r] = p[r] * (FOLD ? dp[r] : dp[r] - dl);
     }
 #pragma unroll
@@ -228,20 +223,21 @@ struct BwdSplit {
 // CHK (with WIN and VLEN; omh_flash_attn_bwd_chunk_d128): the chunk-causal staircase (omh_common.h ChunkRule) in place of
 // the band — row i, chunk I = (off + i) / chunk, sees keys [(I - left) chunk, min(klen, (I + 1) chunk)).  Only the two
 // intervals differ (one division per workgroup, one per row, none in the loop); q_lens may be NULL (= Lq).
-// IVL (with WIN and VLEN; omh_flash_attn_bwd_interval_d128): an interval mask (omh_common.h IvlTab, the q_iv table) — each
-// row has the two key intervals of its group; the workgroup runs the key tiles inside the hull of its groups' first
-// intervals and, `t_gap` tiles further, inside the hull of their second ones (the forward's
-// flash_attn_fwd_d128_kernel<true, false, false, true> documents the ranges).  The table is read before the loop.
-// IV3 (with IVL; omh_flash_attn_bwd_interval3_d128): the three-run form — table rows of 6 ints, three key intervals per
-// row, up to three tile ranges (a second jump of `t_gap1` tiles behind tile n_second of the loop).
-template <bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, bool IVL = false, bool IV3 = false>
+// RUNS > 0 (with WIN and VLEN; "IVL" below; omh_flash_attn_bwd_interval_d128: 2, _interval3_d128: 3): an interval mask
+// (omh_common.h IvlTab, the q_iv table, rows of 2 RUNS ints) — each row has the RUNS key intervals of its group; the
+// workgroup runs the key tiles inside the hulls of its groups' first, second, ... intervals: up to RUNS ranges of tiles
+// with a jump between them (omh_ivl_tiles; the forward's flash_attn_fwd_d128_kernel documents the ranges).  The table is
+// read before the loop.  RUNS = 0: no interval mask.
+template <bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, int RUNS = 0>
 __global__ __launch_bounds__(256, 2)
 void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk, const int wl, const int wr,
                          const int32_t* __restrict__ q_lens, const BlkList bl, const ChunkRule ck) {
     static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
+    constexpr bool IVL = RUNS > 0;
+    constexpr int NR = IVL ? RUNS : 2;                               // (the interval types need a run count where nothing uses them)
+    static_assert(RUNS == 0 || RUNS == 2 || RUNS == 3, "two-run and three-run tables");
     static_assert(!CHK || (WIN && VLEN), "the staircase runs on the varlen band kernels' masking");
     static_assert(!IVL || (WIN && VLEN && !CHK), "an interval mask runs on the varlen band kernels' masking");
-    static_assert(!IV3 || IVL, "the three-run form is an interval mask");
     static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [2 stages][K tile | V tile]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
@@ -275,28 +271,14 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     if constexpr (BLK) { if (q_lens) qlen = min(max(q_lens[b], 0), p.Lq); }
     const bool q_ok = q_row < qlen;
     int key_lo = 0, key_hi = klen - 1;                               // WIN: this lane's (query row's) band of keys
-    IvlSpan span = {0, 0, 0, 0};                                     // IVL: this lane's two intervals of keys
-    int n_first = 0, t_gap = 0;                                      // IVL: tiles of the first range, tiles skipped behind it
-    Ivl3Span span3 = {0, 0, 0, 0, 0, 0};                             // IV3: this lane's three intervals of keys
-    int n_second = 0, t_gap1 = 0;                                    // IV3: tiles of the first two ranges, the second jump
-    if constexpr (IV3) {
+    IvlSpan<NR> span = {};                                           // IVL: this lane's intervals of keys
+    IvlTiles<NR> plan = {};                                          // IVL: the tile ranges of the loop
+    if constexpr (IVL) {
         const IvlTab iv = omh_ivl_tab(bl);                           // the table arrives in the BlkList argument
         const int q0 = qb * 128, q1 = min(q0 + 128, qlen) - 1;      // live query rows of this workgroup
-        n_tiles = 0;
-        if (q1 >= q0) {
-            const Ivl3Tiles it = omh_ivl3_tiles(iv, q0, q1, klen, TB, nullptr);
-            t_first = it.t_first; n_first = it.n0; t_gap = it.gap0; n_second = it.n1; t_gap1 = it.gap1; n_tiles = it.n_tiles;
-        }
-        span3 = omh_ivl3_row(iv, q_row / iv.group, klen);
-    } else if constexpr (IVL) {
-        const IvlTab iv = omh_ivl_tab(bl);                           // the table arrives in the BlkList argument
-        const int q0 = qb * 128, q1 = min(q0 + 128, qlen) - 1;      // live query rows of this workgroup
-        n_tiles = 0;
-        if (q1 >= q0) {
-            const IvlTiles it = omh_ivl_tiles(iv, q0, q1, klen, TB, nullptr, nullptr);
-            t_first = it.t_first; n_first = it.n0; t_gap = it.gap; n_tiles = it.n_tiles;
-        }
-        span = omh_ivl_row(iv, q_row / iv.group, klen);
+        if (q1 >= q0) plan = omh_ivl_tiles<NR>(iv, q0, q1, klen, TB, nullptr);
+        t_first = plan.t_first; n_tiles = plan.n_tiles;
+        span = omh_ivl_row<NR>(iv, q_row / iv.group, klen);
     } else if constexpr (WIN) {
         const int shift = klen - qlen;
         const int q0 = qb * 128, q1 = min(q0 + 128, qlen) - 1;      // live query rows of this workgroup
@@ -393,12 +375,7 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[kk], dp, 0, 0, 0);
             }
             bf16x8 pf[2], dsf[2];
-            if constexpr (MASK == 4)
-                p_and_ds<PRE, false, 4>(s, dp, l2, del, k0 + 32 * hb + lh * 8, span3.len0, sc, pf, dsf, span3.lo0, span3.lo1, span3.len1,
-                                        span3.lo2, span3.len2);
-            else
-            p_and_ds<PRE, false, MASK>(s, dp, l2, del, k0 + 32 * hb + lh * 8, MASK == 3 ? span.len0 : MASK == 2 ? key_hi : klen, sc, pf,
-                                       dsf, MASK == 3 ? span.lo0 : key_lo, span.lo1, span.len1);
+            p_and_ds<PRE, false, MASK, NR>(s, dp, l2, del, k0 + 32 * hb + lh * 8, MASK == 2 ? key_hi : klen, sc, pf, dsf, key_lo, span);
             // dQ^T += K^T dS^T   ([d][query], lane = query): K^T gathered from the row-major K tile
 #pragma unroll
             for (int a = 0; a < 2; ++a)
@@ -409,29 +386,16 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
                 }
         }
     };
-    if constexpr (IV3) {                                             // every tile masked against the rows' three intervals
-        auto tile_of = [&](int x) { return t_first + x + (x >= n_first ? t_gap : 0) + (x >= n_second ? t_gap1 : 0); };
+    if constexpr (IVL) {                                             // every tile masked against the rows' intervals
         for (int t = 0; t < n_tiles; ++t) {
             const unsigned char* kt = smem + (t & 1) * 2 * TILE_BYTES;
             if (t + 1 < n_tiles) {
                 const uint32_t nk = wave_lds + ((t + 1) & 1) * 2 * TILE_BYTES;
-                const int nx = tile_of(t + 1);
+                const int nx = plan.tile(t + 1);
                 tile_dma(ks, nx, nk);
                 tile_dma(vs, nx, nk + TILE_BYTES);
             }
-            tile_body(kt, kt + TILE_BYTES, tile_of(t) * TB, std::integral_constant<int, 4>());
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-    } else if constexpr (IVL) {                                      // every tile masked against the rows' two intervals
-        for (int t = 0; t < n_tiles; ++t) {
-            const unsigned char* kt = smem + (t & 1) * 2 * TILE_BYTES;
-            if (t + 1 < n_tiles) {
-                const uint32_t nk = wave_lds + ((t + 1) & 1) * 2 * TILE_BYTES;
-                const int nx = t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0);
-                tile_dma(ks, nx, nk);
-                tile_dma(vs, nx, nk + TILE_BYTES);
-            }
-            tile_body(kt, kt + TILE_BYTES, (t_first + t + (t >= n_first ? t_gap : 0)) * TB, std::integral_constant<int, 3>());
+            tile_body(kt, kt + TILE_BYTES, plan.tile(t) * TB, std::integral_constant<int, 3>());
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
     } else if constexpr (WIN) {                                      // every tile masked against the rows' bands
@@ -599,19 +563,19 @@ __device__ __forceinline__ void dkdv_store(const omh_attn_bwd_args& p, const Bwd
 // CHK (see attn_bwd2_dq_kernel): key j of chunk J = j / chunk is seen by the rows i with J chunk <= off + i < (J + left + 1)
 // chunk (no upper end for left < 0), cut at qlen; the workgroup walks the query tiles from its first live key's lower end
 // to its last live key's upper end.  One division per workgroup and one per key, none in the loop.
-// IVL (see attn_bwd2_dq_kernel): the k_iv table — each key has the two intervals of query rows of its group, cut at
-// qlen; the workgroup walks the query tiles inside the hull of its groups' first intervals and, `t_gap` tiles further,
-// inside the hull of their second ones.  A key group nobody sees runs no tile: dk = dv = 0.
-// IV3 (see attn_bwd2_dq_kernel): the three-run k_iv table — three intervals of query rows per key, up to three tile ranges.
-template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, bool IVL = false,
-          bool IV3 = false>
+// RUNS > 0 (see attn_bwd2_dq_kernel): the k_iv table — each key has the RUNS intervals of query rows of its group, cut at
+// qlen; the workgroup walks the query tiles inside the hulls of its groups' first, second, ... intervals (up to RUNS ranges
+// of tiles, omh_ivl_tiles).  A key group nobody sees runs no tile: dk = dv = 0.
+template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, int RUNS = 0>
 __global__ __launch_bounds__(64 * WAVES, 1)
 void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk, const int wl, const int wr,
                            const int32_t* __restrict__ q_lens, const BlkList bl, const ChunkRule ck) {
     static_assert(WIN || !VLEN, "q_lens is served by the band kernels");
+    constexpr bool IVL = RUNS > 0;
+    constexpr int NR = IVL ? RUNS : 2;                               // (the interval types need a run count where nothing uses them)
+    static_assert(RUNS == 0 || RUNS == 2 || RUNS == 3, "two-run and three-run tables");
     static_assert(!CHK || (WIN && VLEN), "the staircase runs on the varlen band kernels' masking");
     static_assert(!IVL || (WIN && VLEN && !CHK), "an interval mask runs on the varlen band kernels' masking");
-    static_assert(!IV3 || IVL, "the three-run form is an interval mask");
     static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
     constexpr int THREADS = 64 * WAVES;
     static_assert(WAVES * KPW == 4, "a workgroup covers 128 keys");
@@ -659,30 +623,15 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
             t_nxt = blk_tile(min(1, n_tiles - 1));
         }
     }
-    IvlSpan span = {0, 0, 0, 0};                                     // IVL: this lane's (key's) two intervals of queries
-    int n_first = 0, t_gap = 0;                                      // IVL: tiles of the first range, tiles skipped behind it
-    Ivl3Span span3 = {0, 0, 0, 0, 0, 0};                             // IV3: this lane's (key's) three intervals of queries
-    int n_second = 0, t_gap1 = 0;                                    // IV3: tiles of the first two ranges, the second jump
-    if constexpr (IV3) {
+    IvlSpan<NR> span = {};                                           // IVL: this lane's (key's) intervals of queries
+    IvlTiles<NR> plan = {};                                          // IVL: the tile ranges of the loop
+    if constexpr (IVL) {
         static_assert(KPW == 1, "one key per lane");
         const IvlTab iv = omh_ivl_tab(bl);                           // the table arrives in the BlkList argument
         const int k0 = kb * 128, k1 = min(k0 + 128, klen) - 1;      // live keys of this workgroup
-        n_tiles = 0;
-        if (k1 >= k0) {
-            const Ivl3Tiles it = omh_ivl3_tiles(iv, k0, k1, qlen, TB, nullptr);
-            t_first = it.t_first; n_first = it.n0; t_gap = it.gap0; n_second = it.n1; t_gap1 = it.gap1; n_tiles = it.n_tiles;
-        }
-        span3 = omh_ivl3_row(iv, (kb * 128 + wave * 32 + li) / iv.group, qlen);
-    } else if constexpr (IVL) {
-        static_assert(KPW == 1, "one key per lane");
-        const IvlTab iv = omh_ivl_tab(bl);                           // the table arrives in the BlkList argument
-        const int k0 = kb * 128, k1 = min(k0 + 128, klen) - 1;      // live keys of this workgroup
-        n_tiles = 0;
-        if (k1 >= k0) {
-            const IvlTiles it = omh_ivl_tiles(iv, k0, k1, qlen, TB, nullptr, nullptr);
-            t_first = it.t_first; n_first = it.n0; t_gap = it.gap; n_tiles = it.n_tiles;
-        }
-        span = omh_ivl_row(iv, (kb * 128 + wave * 32 + li) / iv.group, qlen);
+        if (k1 >= k0) plan = omh_ivl_tiles<NR>(iv, k0, k1, qlen, TB, nullptr);
+        t_first = plan.t_first; n_tiles = plan.n_tiles;
+        span = omh_ivl_row<NR>(iv, (kb * 128 + wave * 32 + li) / iv.group, qlen);
     } else if constexpr (WIN) {
         static_assert(KPW == 1, "one key per lane");
         const int shift = klen - qlen;
@@ -778,9 +727,9 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         const int t_sto = t_nxt;                                     // BLK: the tile being fetched during this iteration
         if (more) {
             const uint32_t nq = wave_lds + ((t + 1) & 1) * 2 * TILE_BYTES;
-            tile_dma<THREADS>(qs, BLK ? t_nxt : IV3 ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) + (t + 1 >= n_second ? t_gap1 : 0) : IVL ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) : t_first + t + 1, nq);
-            tile_dma<THREADS>(dos, BLK ? t_nxt : IV3 ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) + (t + 1 >= n_second ? t_gap1 : 0) : IVL ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) : t_first + t + 1, nq + TILE_BYTES);
-            stat_load(BLK ? t_nxt : IV3 ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) + (t + 1 >= n_second ? t_gap1 : 0) : IVL ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) : t_first + t + 1, gl, gd);
+            tile_dma<THREADS>(qs, BLK ? t_nxt : IVL ? plan.tile(t + 1) : t_first + t + 1, nq);
+            tile_dma<THREADS>(dos, BLK ? t_nxt : IVL ? plan.tile(t + 1) : t_first + t + 1, nq + TILE_BYTES);
+            stat_load(BLK ? t_nxt : IVL ? plan.tile(t + 1) : t_first + t + 1, gl, gd);
         }
         if constexpr (BLK) t_nxt = blk_tile(min(t + 2, n_tiles - 1));   // a tile ahead of its loads
         // One tile = two halves of 32 queries, each with three stages: A  S = Q K^T and dP = dO V^T (16 products,
@@ -838,18 +787,22 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         auto slice_b = [&](int hb, int i) {                          // scores 2i, 2i+1 of a half (p_and_ds FOLD, no mask)
             float p0 = __builtin_amdgcn_exp2f(PRE ? s[hb][2 * i] : s[hb][2 * i] * sc);
             float p1 = __builtin_amdgcn_exp2f(PRE ? s[hb][2 * i + 1] : s[hb][2 * i + 1] * sc);
-            if constexpr (IV3) {                                     // the lane's three intervals, their starts relative in the same way
-                const int q8 = (t_first + t + (t >= n_first ? t_gap : 0) + (t >= n_second ? t_gap1 : 0)) * TB + 8 * lh, rel0 = span3.lo0 - q8, rel1 = span3.lo1 - q8, rel2 = span3.lo2 - q8;
+            if constexpr (IVL) {                                     // the lane's intervals, their starts relative in the same way
+                const int q8 = plan.tile(t) * TB + 8 * lh;
                 const int o0 = 32 * hb + 16 * ((2 * i) >> 3) + ((2 * i) & 7), o1 = o0 + 1;
-                p0 = ((unsigned)(o0 - rel0) < (unsigned)span3.len0 || (unsigned)(o0 - rel1) < (unsigned)span3.len1 ||
-                      (unsigned)(o0 - rel2) < (unsigned)span3.len2) ? p0 : 0.f;
-                p1 = ((unsigned)(o1 - rel0) < (unsigned)span3.len0 || (unsigned)(o1 - rel1) < (unsigned)span3.len1 ||
-                      (unsigned)(o1 - rel2) < (unsigned)span3.len2) ? p1 : 0.f;
-            } else if constexpr (IVL) {                              // the lane's two intervals, their starts relative in the same way
-                const int q8 = (t_first + t + (t >= n_first ? t_gap : 0)) * TB + 8 * lh, rel0 = span.lo0 - q8, rel1 = span.lo1 - q8;
-                const int o0 = 32 * hb + 16 * ((2 * i) >> 3) + ((2 * i) & 7), o1 = o0 + 1;
-                p0 = ((unsigned)(o0 - rel0) < (unsigned)span.len0 || (unsigned)(o0 - rel1) < (unsigned)span.len1) ? p0 : 0.f;
-                p1 = ((unsigned)(o1 - rel0) < (unsigned)span.len0 || (unsigned)(o1 - rel1) < (unsigned)span.len1) ? p1 : 0.f;
+                if constexpr (RUNS == 2) {
+                    // spelled out for two runs: through the shifted span below the compiler parks loop constants in AGPRs and
+                    // orders the slices differently — 1.2 - 1.5 % of the two-run backward (profiles/ivl_unify_probe.txt)
+                    const int rel0 = span.lo[0] - q8, rel1 = span.lo[1] - q8;
+                    p0 = ((unsigned)(o0 - rel0) < (unsigned)span.len[0] || (unsigned)(o0 - rel1) < (unsigned)span.len[1]) ? p0 : 0.f;
+                    p1 = ((unsigned)(o1 - rel0) < (unsigned)span.len[0] || (unsigned)(o1 - rel1) < (unsigned)span.len[1]) ? p1 : 0.f;
+                } else {
+                    IvlSpan<NR> rel;
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) { rel.lo[r] = span.lo[r] - q8; rel.len[r] = span.len[r]; }
+                    p0 = rel.sees(o0) ? p0 : 0.f;
+                    p1 = rel.sees(o1) ? p1 : 0.f;
+                }
             } else if constexpr (WIN) {                              // (a select: exp2 of a score outside the band may be inf)
                 const int o0 = 32 * hb + 16 * ((2 * i) >> 3) + ((2 * i) & 7), o1 = o0 + 1;
                 p0 = (o0 >= rel_lo && o0 <= rel_hi) ? p0 : 0.f;
@@ -898,7 +851,7 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
         stage_c(1, 0);
         stage_c(1, 1);
         if (more && tid < 64)                                        // the other stage's statistics: last read a tile ago
-            stat_store(BLK ? t_sto : IV3 ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) + (t + 1 >= n_second ? t_gap1 : 0) : IVL ? t_first + t + 1 + (t + 1 >= n_first ? t_gap : 0) : t_first + t + 1, gl, gd, stat + ((t + 1) & 1) * 128);
+            stat_store(BLK ? t_sto : IVL ? plan.tile(t + 1) : t_first + t + 1, gl, gd, stat + ((t + 1) & 1) * 128);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
 #pragma unroll
@@ -1340,11 +1293,14 @@ extern "C" int omh_flash_attn_bwd_cached_d128(const omh_attn_bwd_args* args, int
     return omh_launch_status();
 }
 
-// called by omh_flash_attn_bwd_band_d128 and omh_flash_attn_bwd_varlen_d128 (attention_bwd.hip) with validated arguments
-// and o32 set: the same phases as omh_launch_attn_bwd2, on the WIN instantiations of the HIP kernels (the w64 streams are
-// full-attention only); never split (the entries decline the workspace).  VLEN: the q_lens instantiations.
-template <bool VLEN>
-static int launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, hipStream_t s) {
+// The masked backward: called by the masked entries of attention_bwd.hip with validated arguments, o32 set and a checked
+// mask.  The same phases as omh_launch_attn_bwd2, on the HIP kernels' instantiations for mask kind M (omh_common.h; the w64
+// streams are full-attention only); never split (the entries decline the workspace).  wl / wr: the band (-1, -1 under every
+// other mask); q_lens: NULL = Lq; bl_q / bl_k: the block lists or the interval table of the dQ / the dK, dV kernel; ck:
+// the staircase.
+template <typename M>
+static int launch_attn_bwd2_masked(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, const BlkList& bl_q,
+                                   const BlkList& bl_k, const ChunkRule& ck, hipStream_t s) {
     if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
         ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
         return OMH_E_SHAPE;
@@ -1357,160 +1313,57 @@ static int launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, con
     wl = wl < 0 ? -1 : (wl > wmax ? wmax : wl);
     wr = wr < 0 ? -1 : (wr > wmax ? wmax : wr);
     constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
+    const auto dq_gen = attn_bwd2_dq_kernel<false, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
+    const auto dq_pre = attn_bwd2_dq_kernel<true, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
+    const auto dkdv_gen = attn_bwd2_dkdv_kernel<4, 1, false, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
+    const auto dkdv_pre = attn_bwd2_dkdv_kernel<4, 1, true, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
     static bool attr_set = false;                                    // (one flag per instantiation of this function)
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)dq_gen, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)dq_pre, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
+        (void)hipFuncSetAttribute((const void*)dkdv_gen, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
+        (void)hipFuncSetAttribute((const void*)dkdv_pre, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
         attr_set = true;
     }
     if (a.phase == 0 || a.phase == 1) {
-        hipLaunchKernelGGL(attn_bwd2_delta_kernel<VLEN>, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, s, a, q_lens);
+        const dim3 grid((unsigned)((pairs + 15) / 16));
+        if (q_lens) hipLaunchKernelGGL(attn_bwd2_delta_kernel<true>, grid, dim3(256), 0, s, a, q_lens);
+        else hipLaunchKernelGGL(attn_bwd2_delta_kernel<false>, grid, dim3(256), 0, s, a, nullptr);
         if (a.phase == 1) return 0;
     }
     const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
     if (a.phase == 0 || a.phase == 2) {
         const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
+        hipLaunchKernelGGL((a.q_prescaled ? dq_pre : dq_gen), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, wl, wr, q_lens, bl_q, ck);
     }
     if (a.phase == 0 || a.phase == 3) {
         const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, VLEN>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, BlkList{}, ChunkRule{});
+        hipLaunchKernelGGL((a.q_prescaled ? dkdv_pre : dkdv_gen), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, wl, wr, q_lens, bl_k, ck);
     }
     return 0;
 }
 // q_lens == nullptr: the band kernels themselves (qlen = Lq), so that call is omh_flash_attn_bwd_band_d128 bit for bit
 int omh_launch_attn_bwd2_band(const omh_attn_bwd_args& a, int wl, int wr, const int32_t* q_lens, hipStream_t s) {
-    return q_lens ? launch_attn_bwd2_band<true>(a, wl, wr, q_lens, s) : launch_attn_bwd2_band<false>(a, wl, wr, nullptr, s);
+    return q_lens ? launch_attn_bwd2_masked<MaskBand<true>>(a, wl, wr, q_lens, BlkList{}, BlkList{}, ChunkRule{}, s)
+                  : launch_attn_bwd2_masked<MaskBand<false>>(a, wl, wr, nullptr, BlkList{}, BlkList{}, ChunkRule{}, s);
 }
-
-// called by omh_flash_attn_bwd_sparse_d128 (attention_bwd.hip) with validated arguments, o32 set and a checked mask: the
-// phases of omh_launch_attn_bwd2 on the BLK instantiations of the HIP kernels; never split.
+// the row lists for dQ, the column lists for dK / dV
 int omh_launch_attn_bwd2_sparse(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_block_mask& m, hipStream_t s) {
-    if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
-        ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
-        return OMH_E_SHAPE;
-    if (((uintptr_t)a.o32 & 15) || (a.o_rs & 3) || (a.o_bs & 3)) return OMH_E_ALIGN;
-    if (a.phase < 0 || a.phase > 3) return OMH_E_BADARG;
-    const int64_t pairs = (int64_t)a.B * a.Lq * a.H;
-    if (pairs >= 0x7fffffffLL) return OMH_E_SHAPE;
-    constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        attr_set = true;
-    }
-    if (a.phase == 0 || a.phase == 1) {
-        const dim3 grid((unsigned)((pairs + 15) / 16));
-        if (q_lens) hipLaunchKernelGGL(attn_bwd2_delta_kernel<true>, grid, dim3(256), 0, s, a, q_lens);
-        else hipLaunchKernelGGL(attn_bwd2_delta_kernel<false>, grid, dim3(256), 0, s, a, nullptr);
-        if (a.phase == 1) return 0;
-    }
-    const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
-    if (a.phase == 0 || a.phase == 2) {
-        const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
-        const BlkList bl = {m.row_cnt, m.row_idx, m.heads, m.q_blocks, m.k_blocks};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
-    }
-    if (a.phase == 0 || a.phase == 3) {
-        const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
-        const BlkList bl = {m.col_cnt, m.col_idx, m.heads, m.k_blocks, m.q_blocks};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, false, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, bl, ChunkRule{});
-    }
-    return 0;
+    return launch_attn_bwd2_masked<MaskBlocks>(a, -1, -1, q_lens, BlkList{m.row_cnt, m.row_idx, m.heads, m.q_blocks, m.k_blocks},
+                                               BlkList{m.col_cnt, m.col_idx, m.heads, m.k_blocks, m.q_blocks}, ChunkRule{}, s);
 }
-
-// called by omh_flash_attn_bwd_chunk_d128 (attention_bwd.hip) with validated arguments, o32 set and a normalised rule: the
-// phases of omh_launch_attn_bwd2 on the CHK instantiations of the HIP kernels; never split.
 int omh_launch_attn_bwd2_chunk(const omh_attn_bwd_args& a, const int32_t* q_lens, const ChunkRule& ck, hipStream_t s) {
-    if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
-        ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
-        return OMH_E_SHAPE;
-    if (((uintptr_t)a.o32 & 15) || (a.o_rs & 3) || (a.o_bs & 3)) return OMH_E_ALIGN;
-    if (a.phase < 0 || a.phase > 3) return OMH_E_BADARG;
-    const int64_t pairs = (int64_t)a.B * a.Lq * a.H;
-    if (pairs >= 0x7fffffffLL) return OMH_E_SHAPE;
-    constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        attr_set = true;
-    }
-    if (a.phase == 0 || a.phase == 1) {
-        const dim3 grid((unsigned)((pairs + 15) / 16));
-        if (q_lens) hipLaunchKernelGGL(attn_bwd2_delta_kernel<true>, grid, dim3(256), 0, s, a, q_lens);
-        else hipLaunchKernelGGL(attn_bwd2_delta_kernel<false>, grid, dim3(256), 0, s, a, nullptr);
-        if (a.phase == 1) return 0;
-    }
-    const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
-    if (a.phase == 0 || a.phase == 2) {
-        const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, BlkList{}, ck);
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, BlkList{}, ck);
-    }
-    if (a.phase == 0 || a.phase == 3) {
-        const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, BlkList{}, ck);
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, true, false, true>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, BlkList{}, ck);
-    }
-    return 0;
+    return launch_attn_bwd2_masked<MaskStairs>(a, -1, -1, q_lens, BlkList{}, BlkList{}, ck, s);
 }
-
-// called by omh_flash_attn_bwd_interval_d128 / _interval3_d128 (attention_bwd.hip) with validated arguments, o32 set and a
-// checked mask: the phases of omh_launch_attn_bwd2 on the IVL (IV3: three-run) instantiations of the HIP kernels; never split.
-template <bool IV3, typename Mask>
+// the q_iv table for dQ, the k_iv table for dK / dV
+template <int RUNS, typename Mask>
 static int launch_attn_bwd2_interval(const omh_attn_bwd_args& a, const int32_t* q_lens, const Mask& m, hipStream_t s) {
-    if (((int64_t)a.Lq + 4 * TB) * a.q_rs * 2 >= 0x7fffffffLL || ((int64_t)a.Lk + 4 * TB) * a.k_rs * 2 >= 0x7fffffffLL ||
-        ((int64_t)a.Lq + 4 * TB) * a.o_rs * 2 >= 0x7fffffffLL)
-        return OMH_E_SHAPE;
-    if (((uintptr_t)a.o32 & 15) || (a.o_rs & 3) || (a.o_bs & 3)) return OMH_E_ALIGN;
-    if (a.phase < 0 || a.phase > 3) return OMH_E_BADARG;
-    const int64_t pairs = (int64_t)a.B * a.Lq * a.H;
-    if (pairs >= 0x7fffffffLL) return OMH_E_SHAPE;
-    constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<false, true, true, false, false, true, IV3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dq_kernel<true, true, true, false, false, true, IV3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, false, true, true, false, false, true, IV3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_dkdv_kernel<4, 1, true, true, true, false, false, true, IV3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_KV);
-        attr_set = true;
-    }
-    if (a.phase == 0 || a.phase == 1) {
-        const dim3 grid((unsigned)((pairs + 15) / 16));
-        if (q_lens) hipLaunchKernelGGL(attn_bwd2_delta_kernel<true>, grid, dim3(256), 0, s, a, q_lens);
-        else hipLaunchKernelGGL(attn_bwd2_delta_kernel<false>, grid, dim3(256), 0, s, a, nullptr);
-        if (a.phase == 1) return 0;
-    }
-    const int k_blocks = (a.Lk + 127) / 128, q_blocks = (a.Lq + 127) / 128;
-    if (a.phase == 0 || a.phase == 2) {
-        const BwdSplit w = {q_blocks * a.H * a.B, 0, 1, nullptr};
-        const BlkList iv = omh_ivl_arg(m.q_iv, m.group, m.q_groups, m.k_groups);
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dq_kernel<true, true, true, false, false, true, IV3>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, iv, ChunkRule{});
-        else hipLaunchKernelGGL((attn_bwd2_dq_kernel<false, true, true, false, false, true, IV3>), dim3(w.n_regular), dim3(256), LDS_DQ, s, a, q_blocks, w, -1, -1, q_lens, iv, ChunkRule{});
-    }
-    if (a.phase == 0 || a.phase == 3) {
-        const BwdSplit w = {k_blocks * a.H * a.B, 0, 1, nullptr};
-        const BlkList iv = omh_ivl_arg(m.k_iv, m.group, m.k_groups, m.q_groups);
-        if (a.q_prescaled) hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, true, true, true, false, false, true, IV3>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, iv, ChunkRule{});
-        else hipLaunchKernelGGL((attn_bwd2_dkdv_kernel<4, 1, false, true, true, false, false, true, IV3>), dim3(w.n_regular), dim3(256), LDS_KV, s, a, k_blocks, w, -1, -1, q_lens, iv, ChunkRule{});
-    }
-    return 0;
+    return launch_attn_bwd2_masked<MaskIntervals<RUNS>>(a, -1, -1, q_lens, omh_ivl_arg(m.q_iv, m.group, m.q_groups, m.k_groups),
+                                                        omh_ivl_arg(m.k_iv, m.group, m.k_groups, m.q_groups), ChunkRule{}, s);
 }
 int omh_launch_attn_bwd2_interval(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval_mask& m, hipStream_t s) {
-    return launch_attn_bwd2_interval<false>(a, q_lens, m, s);
+    return launch_attn_bwd2_interval<2>(a, q_lens, m, s);
 }
 int omh_launch_attn_bwd2_interval3(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval3_mask& m, hipStream_t s) {
-    return launch_attn_bwd2_interval<true>(a, q_lens, m, s);
+    return launch_attn_bwd2_interval<3>(a, q_lens, m, s);
 }

@@ -185,12 +185,14 @@ static inline int omh_chunk_rule(const omh_chunk_causal* c, int Lq, int Lk, Chun
     return 0;
 }
 
-// ---- interval masks (include/omh.h omh_interval_mask; attention.hip, attention_bwd2.hip) ----
-// What an IVL kernel gets: ONE of the two tables — row g of `iv` holds the (at most two) intervals [lo0, hi0) U [lo1, hi1)
-// of groups of the OTHER axis that group g of the workgroup's axis sees (q_iv: forward and dQ; k_iv: dK / dV), in groups
-// of `group` positions; `n` rows, `other` groups on the other axis.
+// ---- interval masks (include/omh.h omh_interval_mask / omh_interval3_mask; attention.hip, attention_bwd2.hip) ----
+// What an IVL kernel gets: ONE of the two tables — row g of `iv` holds the (at most RUNS) intervals [lo0, hi0) U [lo1, hi1)
+// ... of groups of the OTHER axis that group g of the workgroup's axis sees (q_iv: forward and dQ; k_iv: dK / dV), in
+// groups of `group` positions; `n` rows, `other` groups on the other axis.  RUNS (2: omh_interval_mask, 3:
+// omh_interval3_mask) is a template argument of the kernels and of every helper below: one implementation, two
+// instantiations (a two-run mask through the three-run kernels costs 7 % forward, 15 % backward: DESIGN.md 4.2g).
 struct IvlTab {
-    const int32_t* iv;    // [n][4] (the three-run form below: [n][6])
+    const int32_t* iv;    // [n][2 RUNS]
     int group, n, other;
 };
 // The IVL kernels take their table in the BlkList argument (no kernel has both): a further kernel argument would change
@@ -201,16 +203,10 @@ static_assert(sizeof(BlkList) == 2 * sizeof(void*) + 4 * sizeof(int) && sizeof(I
 static_assert(std::is_same<decltype(BlkList::idx), decltype(IvlTab::iv)>::value && std::is_same<decltype(BlkList::heads), int>::value &&
               std::is_same<decltype(BlkList::lists), int>::value && std::is_same<decltype(BlkList::stride), int>::value,
               "omh_ivl_arg / omh_ivl_tab map idx, heads, lists, stride to iv, group, n, other");
-// 0 or the error code (the tables themselves live on the device: the kernels clamp what they read to [0, other])
-static inline int omh_interval_mask_check(const omh_interval_mask* m, int Lq, int Lk) {
-    if (!m || !m->q_iv || !m->k_iv || m->group < 8 || m->reserved != 0) return OMH_E_BADARG;
-    if ((int64_t)Lq + Lk >= (1LL << 28)) return OMH_E_SHAPE;
-    if (m->q_groups != (Lq + m->group - 1) / m->group || m->k_groups != (Lk + m->group - 1) / m->group) return OMH_E_BADARG;
-    if (((uintptr_t)m->q_iv | (uintptr_t)m->k_iv) & 3) return OMH_E_ALIGN;
-    return 0;
-}
-// the same rules for the three-run mask (its tables have rows of 6 ints; the kernels know the stride from their instantiation)
-static inline int omh_interval3_mask_check(const omh_interval3_mask* m, int Lq, int Lk) {
+// 0 or the error code, for either public struct (the same fields; the tables themselves live on the device: the kernels
+// clamp what they read to [0, other] and know the row stride from their instantiation)
+template <typename Mask>
+static inline int omh_interval_mask_check(const Mask* m, int Lq, int Lk) {
     if (!m || !m->q_iv || !m->k_iv || m->group < 8 || m->reserved != 0) return OMH_E_BADARG;
     if ((int64_t)Lq + Lk >= (1LL << 28)) return OMH_E_SHAPE;
     if (m->q_groups != (Lq + m->group - 1) / m->group || m->k_groups != (Lk + m->group - 1) / m->group) return OMH_E_BADARG;
@@ -219,115 +215,117 @@ static inline int omh_interval3_mask_check(const omh_interval3_mask* m, int Lq, 
 }
 #if defined(__HIPCC__)
 __device__ __forceinline__ IvlTab omh_ivl_tab(const BlkList& bl) { return IvlTab{bl.idx, bl.heads, bl.lists, bl.stride}; }
-// One position's (or one workgroup's) view of the other axis: two intervals of positions [lo, lo + len), len <= 0: empty.
+// One position's (or one workgroup's) view of the other axis: RUNS intervals of positions [lo, lo + len), len <= 0: empty.
+// (Every loop over the runs is fully unrolled and indexes with constants: the arrays are registers, never scratch.)
+template <int RUNS>
 struct IvlSpan {
-    int lo0, len0, lo1, len1;
+    int lo[RUNS], len[RUNS];
+    // (bitwise: a compare per run and an OR between them, no short-circuit branches per element — what the compiler makes of
+    // || over three runs in the forward)
     __device__ __forceinline__ bool sees(int x) const {
-        return (unsigned)(x - lo0) < (unsigned)len0 || (unsigned)(x - lo1) < (unsigned)len1;
-    }
-};
-// row g of the table in positions, cut at `end` (the live length of the other axis)
-__device__ __forceinline__ IvlSpan omh_ivl_row(const IvlTab& tb, int g, int end) {
-    const int32_t* __restrict__ r = tb.iv + 4 * (int64_t)min(max(g, 0), tb.n - 1);
-    const int a0 = min(max(r[0], 0), tb.other), a1 = min(max(r[1], 0), tb.other);
-    const int b0 = min(max(r[2], 0), tb.other), b1 = min(max(r[3], 0), tb.other);
-    IvlSpan s;
-    s.lo0 = a0 * tb.group; s.len0 = max(min(a1 * tb.group, end) - s.lo0, 0);
-    s.lo1 = b0 * tb.group; s.len1 = max(min(b1 * tb.group, end) - s.lo1, 0);
-    return s;
-}
-// The tiles of `tile` positions a workgroup whose live positions are x0 .. x1 (x1 >= x0) runs: the hull of its groups'
-// first intervals and the hull of their second ones, as tile ranges [t_first, t_first + n0) and, `gap` tiles further,
-// n_tiles - n0 more; one range when they touch.  whole0 / whole1 (may be NULL): the positions EVERY one of those groups
-// sees through its first / second interval ([lo, hi], hi < lo: none).  Scalar reads, once per workgroup.
-struct IvlTiles { int t_first, n0, gap, n_tiles; };
-__device__ __forceinline__ IvlTiles omh_ivl_tiles(const IvlTab& tb, int x0, int x1, int end, int tile, int* whole0, int* whole1) {
-    const int g0 = x0 / tb.group, g1 = x1 / tb.group;
-    int alo = 1 << 30, ahi = 0, blo = 1 << 30, bhi = 0;              // hulls, [lo, hi)
-    int w0lo = 0, w0hi = 1 << 30, w1lo = 0, w1hi = 1 << 30;          // intersections, [lo, hi)
-    for (int g = g0; g <= g1; ++g) {
-        const IvlSpan s = omh_ivl_row(tb, __builtin_amdgcn_readfirstlane(g), end);
-        if (s.len0 > 0) { alo = min(alo, s.lo0); ahi = max(ahi, s.lo0 + s.len0); }
-        if (s.len1 > 0) { blo = min(blo, s.lo1); bhi = max(bhi, s.lo1 + s.len1); }
-        w0lo = max(w0lo, s.lo0); w0hi = min(w0hi, s.lo0 + s.len0);
-        w1lo = max(w1lo, s.lo1); w1hi = min(w1hi, s.lo1 + s.len1);
-    }
-    if (whole0) { whole0[0] = w0lo; whole0[1] = w0hi - 1; }
-    if (whole1) { whole1[0] = w1lo; whole1[1] = w1hi - 1; }
-    if (ahi <= alo) { alo = blo; ahi = bhi; blo = 1 << 30; bhi = 0; }   // only second intervals: they are the one range
-    IvlTiles t = {0, 0, 0, 0};
-    if (ahi <= alo) return t;
-    const int a0 = alo / tile, a1 = (ahi - 1) / tile + 1;
-    t.t_first = a0;
-    if (bhi <= blo) { t.n0 = t.n_tiles = a1 - a0; return t; }
-    const int b0 = blo / tile, b1 = (bhi - 1) / tile + 1;
-    if (b0 <= a1) { t.n0 = t.n_tiles = max(a1, b1) - a0; return t; }
-    t.n0 = a1 - a0; t.gap = b0 - a1; t.n_tiles = t.n0 + (b1 - b0);
-    return t;
-}
-// ---- the three-run form (include/omh.h omh_interval3_mask): rows of 6 ints, lo0, hi0, lo1, hi1, lo2, hi2.  The same
-// rules with one more (lo, len) pair and one more jump; kept beside the two-run form, which stays as it is so that its
-// kernels keep their instruction streams.  The table travels in the BlkList argument in the same way.
-struct Ivl3Span {
-    int lo0, len0, lo1, len1, lo2, len2;
-    __device__ __forceinline__ bool sees(int x) const {
-        // (bitwise: three compares and two ORs per element, no short-circuit branches)
-        return ((unsigned)(x - lo0) < (unsigned)len0) | ((unsigned)(x - lo1) < (unsigned)len1) | ((unsigned)(x - lo2) < (unsigned)len2);
-    }
-};
-// row g of the [n][6] table in positions, cut at `end`
-__device__ __forceinline__ Ivl3Span omh_ivl3_row(const IvlTab& tb, int g, int end) {
-    const int32_t* __restrict__ r = tb.iv + 6 * (int64_t)min(max(g, 0), tb.n - 1);
-    const int a0 = min(max(r[0], 0), tb.other), a1 = min(max(r[1], 0), tb.other);
-    const int b0 = min(max(r[2], 0), tb.other), b1 = min(max(r[3], 0), tb.other);
-    const int c0 = min(max(r[4], 0), tb.other), c1 = min(max(r[5], 0), tb.other);
-    Ivl3Span s;
-    s.lo0 = a0 * tb.group; s.len0 = max(min(a1 * tb.group, end) - s.lo0, 0);
-    s.lo1 = b0 * tb.group; s.len1 = max(min(b1 * tb.group, end) - s.lo1, 0);
-    s.lo2 = c0 * tb.group; s.len2 = max(min(c1 * tb.group, end) - s.lo2, 0);
-    return s;
-}
-// The tiles a workgroup whose live positions are x0 .. x1 runs: the hulls of its groups' first, second and third
-// intervals (their lower ends ascend: every row's do), empty ones dropped, neighbours that touch or overlap in tile units
-// merged — up to three ranges.  Tile x of the loop, x in [0, n_tiles), is  t_first + x + (x >= n0 ? gap0 : 0) +
-// (x >= n1 ? gap1 : 0);  n0 <= n1 <= n_tiles count the tiles of the first range and of the first two.  whole (may be NULL):
-// [lo, hi] of the positions EVERY one of those groups sees through its i-th interval, i = 0, 1, 2 (hi < lo: none).
-struct Ivl3Tiles { int t_first, n0, gap0, n1, gap1, n_tiles; };
-__device__ __forceinline__ Ivl3Tiles omh_ivl3_tiles(const IvlTab& tb, int x0, int x1, int end, int tile, int* whole) {
-    const int g0 = x0 / tb.group, g1 = x1 / tb.group;
-    int hlo[3] = {1 << 30, 1 << 30, 1 << 30}, hhi[3] = {0, 0, 0};    // hulls, [lo, hi)
-    int wlo[3] = {0, 0, 0}, whi[3] = {1 << 30, 1 << 30, 1 << 30};    // intersections, [lo, hi)
-    for (int g = g0; g <= g1; ++g) {
-        const Ivl3Span s = omh_ivl3_row(tb, __builtin_amdgcn_readfirstlane(g), end);
-        const int lo[3] = {s.lo0, s.lo1, s.lo2}, len[3] = {s.len0, s.len1, s.len2};
+        bool in = (unsigned)(x - lo[0]) < (unsigned)len[0];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (len[i] > 0) { hlo[i] = min(hlo[i], lo[i]); hhi[i] = max(hhi[i], lo[i] + len[i]); }
-            wlo[i] = max(wlo[i], lo[i]); whi[i] = min(whi[i], lo[i] + len[i]);
+        for (int i = 1; i < RUNS; ++i) in = in | ((unsigned)(x - lo[i]) < (unsigned)len[i]);
+        return in;
+    }
+};
+// row g of the [n][2 RUNS] table in positions, cut at `end` (the live length of the other axis)
+template <int RUNS>
+__device__ __forceinline__ IvlSpan<RUNS> omh_ivl_row(const IvlTab& tb, int g, int end) {
+    const int32_t* __restrict__ r = tb.iv + 2 * RUNS * (int64_t)min(max(g, 0), tb.n - 1);
+    int a[RUNS], b[RUNS];                                            // [a, b) in groups, clamped
+#pragma unroll
+    for (int i = 0; i < RUNS; ++i) { a[i] = min(max(r[2 * i], 0), tb.other); b[i] = min(max(r[2 * i + 1], 0), tb.other); }
+    IvlSpan<RUNS> s;
+#pragma unroll
+    for (int i = 0; i < RUNS; ++i) { s.lo[i] = a[i] * tb.group; s.len[i] = max(min(b[i] * tb.group, end) - s.lo[i], 0); }
+    return s;
+}
+// The tiles of `tile` positions a workgroup runs: up to RUNS ranges of consecutive tiles.  tile(x), x in [0, n_tiles), is
+// the x-th of them: n[j] counts the tiles of the first j + 1 ranges and gap[j] the tiles skipped behind them (a jump that
+// does not exist has n[j] = n_tiles, gap[j] = 0).  The one place that knows the jump formula.
+template <int RUNS>
+struct IvlTiles {
+    int t_first, n_tiles, n[RUNS - 1], gap[RUNS - 1];
+    __device__ __forceinline__ int tile(int x) const {
+        int t = t_first + x;
+#pragma unroll
+        for (int j = 0; j < RUNS - 1; ++j) t += x >= n[j] ? gap[j] : 0;
+        return t;
+    }
+};
+// The plan of a workgroup whose live positions are x0 .. x1 (x1 >= x0): the hulls of its groups' first, second, ...
+// intervals (their lower ends ascend: every row's do), empty ones dropped, neighbours that touch or overlap in tile units
+// merged.  whole (may be NULL; 2 RUNS ints): [lo, hi] of the positions EVERY one of those groups sees through its i-th
+// interval (hi < lo: none).  Scalar reads, once per workgroup.
+template <int RUNS>
+__device__ __forceinline__ IvlTiles<RUNS> omh_ivl_tiles(const IvlTab& tb, int x0, int x1, int end, int tile, int* whole) {
+    const int g0 = x0 / tb.group, g1 = x1 / tb.group;
+    int hlo[RUNS], hhi[RUNS], wlo[RUNS], whi[RUNS];                  // hulls and intersections, [lo, hi)
+#pragma unroll
+    for (int i = 0; i < RUNS; ++i) hlo[i] = 1 << 30;
+#pragma unroll
+    for (int i = 0; i < RUNS; ++i) hhi[i] = 0;
+#pragma unroll
+    for (int i = 0; i < RUNS; ++i) wlo[i] = 0;
+#pragma unroll
+    for (int i = 0; i < RUNS; ++i) whi[i] = 1 << 30;
+    for (int g = g0; g <= g1; ++g) {
+        const IvlSpan<RUNS> s = omh_ivl_row<RUNS>(tb, __builtin_amdgcn_readfirstlane(g), end);
+#pragma unroll
+        for (int i = 0; i < RUNS; ++i) {
+            if (s.len[i] > 0) { hlo[i] = min(hlo[i], s.lo[i]); hhi[i] = max(hhi[i], s.lo[i] + s.len[i]); }
+            wlo[i] = max(wlo[i], s.lo[i]); whi[i] = min(whi[i], s.lo[i] + s.len[i]);
         }
     }
     if (whole) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { whole[2 * i] = wlo[i]; whole[2 * i + 1] = whi[i] - 1; }
+        for (int i = 0; i < RUNS; ++i) { whole[2 * i] = wlo[i]; whole[2 * i + 1] = whi[i] - 1; }
     }
-    int s0 = 0, e0 = 0, s1 = 0, e1 = 0, s2 = 0, e2 = 0, nr = 0;      // merged tile ranges [s, e), ascending (scalars: no indexing)
+    int rs[RUNS], re[RUNS], nr = 0;                                  // merged tile ranges [rs, re), ascending
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < RUNS; ++i) { rs[i] = 0; re[i] = 0; }
+#pragma unroll
+    for (int i = 0; i < RUNS; ++i) {
         if (hhi[i] <= hlo[i]) continue;
         const int a = hlo[i] / tile, b = (hhi[i] - 1) / tile + 1;
-        if (nr == 0) { s0 = a; e0 = b; nr = 1; }
-        else if (nr == 1) { if (a <= e0) e0 = max(e0, b); else { s1 = a; e1 = b; nr = 2; } }
-        else { if (a <= e1) e1 = max(e1, b); else { s2 = a; e2 = b; nr = 3; } }
+#pragma unroll
+        for (int j = 0; j < RUNS; ++j)                               // nr == j: range j - 1 grows, or range j opens
+            if (j == RUNS - 1 || nr == j) {
+                if (j > 0 && a <= re[j - 1]) re[j - 1] = max(re[j - 1], b); else { rs[j] = a; re[j] = b; nr = j + 1; }
+                break;
+            }
     }
-    Ivl3Tiles t = {0, 0, 0, 0, 0, 0};
+    IvlTiles<RUNS> t = {};
     if (nr == 0) return t;
-    t.t_first = s0;
-    t.n0 = t.n1 = t.n_tiles = e0 - s0;
-    if (nr >= 2) { t.gap0 = s1 - e0; t.n1 = t.n_tiles = t.n0 + (e1 - s1); }
-    if (nr == 3) { t.gap1 = s2 - e1; t.n_tiles = t.n1 + (e2 - s2); }
+    t.t_first = rs[0];
+    t.n_tiles = re[0] - rs[0];
+#pragma unroll
+    for (int j = 0; j < RUNS - 1; ++j) t.n[j] = t.n_tiles;
+#pragma unroll
+    for (int j = 1; j < RUNS; ++j)
+        if (nr > j) {
+            t.gap[j - 1] = rs[j] - re[j - 1];
+            t.n_tiles = t.n[j - 1] + (re[j] - rs[j]);
+#pragma unroll
+            for (int jj = j; jj < RUNS - 1; ++jj) t.n[jj] = t.n_tiles;
+        }
     return t;
 }
 #endif
+
+// ---- which mask a kernel instantiation carries: the template arguments of the masked launchers, by name ----
+// (attention.hip: flash_attn_fwd_d128_kernel<WIN, BLK, CHK, RUNS>; attention_bwd2.hip: the dQ and dK / dV kernels'
+// <.., WIN, VLEN, BLK, CHK, RUNS>.  VLEN — q_lens — exists in the backward only: the forward's band kernel reads q_lens itself.)
+template <bool WIN_, bool VLEN_, bool BLK_, bool CHK_, int RUNS_>
+struct MaskKind {
+    static constexpr bool WIN = WIN_, VLEN = VLEN_, BLK = BLK_, CHK = CHK_;
+    static constexpr int RUNS = RUNS_;
+};
+template <bool VLEN> using MaskBand = MaskKind<true, VLEN, false, false, 0>;     // the band, with or without q_lens
+using MaskBlocks = MaskKind<false, false, true, false, 0>;                       // omh_block_mask
+using MaskStairs = MaskKind<true, true, false, true, 0>;                         // omh_chunk_causal
+template <int RUNS> using MaskIntervals = MaskKind<true, true, false, false, RUNS>;   // omh_interval_mask (2), omh_interval3_mask (3)
 
 // ---- split of a launch's last, partly filled round of workgroups (host side; attention.hip, attention_bwd2.hip) ----
 // A launch of `nwg` equal workgroups on `slots` resident slots takes ceil(nwg / slots) rounds; its last round holds

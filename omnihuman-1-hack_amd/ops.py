@@ -202,6 +202,11 @@ def _chunk_causal(chunk_causal, window=(-1, -1), block_mask=None):
     return _lib.ChunkCausalArgs(min(chunk, big), -1 if left < 0 else min(left, big), min(off, big), 0)
 
 
+# IntervalMask.runs -> the forward and the backward entry
+_INTERVAL_ENTRIES = {2: ("omh_flash_attn_fwd_interval_d128", "omh_flash_attn_bwd_interval_d128"),
+                     3: ("omh_flash_attn_fwd_interval3_d128", "omh_flash_attn_bwd_interval3_d128")}
+
+
 def _interval_mask(interval_mask, Lq, Lk, window=(-1, -1), block_mask=None, chunk_causal=None, device=None):
     """``interval_mask`` (None or a ``causal.IntervalMask``) checked against this call, with its tables on ``device`` (the
     operands' device; the callers that only have pointers pass None: a mask that is on a GPU already stays there, one on
@@ -261,11 +266,8 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
         check(lib.omh_flash_attn_fwd_chunk_d128(C.byref(a), C.byref(cc), _stream()), "omh_flash_attn_fwd_chunk_d128")
         return
     if im is not None:
-        m = im.c_struct()
-        if im.runs == 3:
-            check(lib.omh_flash_attn_fwd_interval3_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_interval3_d128")
-            return
-        check(lib.omh_flash_attn_fwd_interval_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_interval_d128")
+        m, entry = im.c_struct(), _INTERVAL_ENTRIES[im.runs][0]
+        check(getattr(lib, entry)(C.byref(a), C.byref(m), _stream()), entry)
         return
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
     ws = None
@@ -421,13 +423,8 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
               "omh_flash_attn_bwd_chunk_d128")
         return dq, dk, dv
     if im is not None:
-        m = im.c_struct()
-        if im.runs == 3:
-            check(lib.omh_flash_attn_bwd_interval3_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
-                  "omh_flash_attn_bwd_interval3_d128")
-            return dq, dk, dv
-        check(lib.omh_flash_attn_bwd_interval_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
-              "omh_flash_attn_bwd_interval_d128")
+        m, entry = im.c_struct(), _INTERVAL_ENTRIES[im.runs][1]
+        check(getattr(lib, entry)(C.byref(a), _p(q_lens), C.byref(m), _stream()), entry)
         return dq, dk, dv
     if q_lens is not None:
         check(lib.omh_flash_attn_bwd_varlen_d128(C.byref(a), _p(q_lens), int(window[0]), int(window[1]), _stream()),

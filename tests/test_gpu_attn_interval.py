@@ -36,6 +36,38 @@ def _tf(n, W=-1):
     return lambda c: c.teacher_forcing_groups(n, W)
 
 
+# Tables written by hand (not built from a matrix), (number of groups, row) pairs: rows with an EMPTY first slot and a live
+# later one, bounds below 0 and above the other axis's group count (the kernels clamp them), and — group 8, Lq = 200,
+# Lk = 328 — inside the first 128-row workgroup key tiles 1 and 2 (keys 64..191) between its two ranges, inside the first
+# 128-key workgroup query tile 1 between its two.  HAND_K says of the key groups what HAND_Q says of the query groups.
+HAND_Q = [(4, [-3, 6, 24, 30]), (4, [4, 6, 30, 30]), (4, [3, 3, 26, 46]), (4, [2, 2, 24, 26]), (4, [7, 7, 8, 17]),
+          (5, [0, 4, 8, 17])]
+HAND_K = [(4, [0, 4, 20, 99]), (2, [-2, 8, 8, 8]), (2, [0, 0, 0, 0]), (9, [9, 9, 16, 25]), (7, [0, 0, 0, 0]),
+          (2, [0, 4, 12, 16]), (4, [0, 4, 8, 12]), (11, [8, 12, 12, 12])]
+
+
+def hand_rows(pairs):
+    return torch.tensor([row for n, row in pairs for _ in range(n)], dtype=torch.int32)
+
+
+def table_matrix(rows, other):
+    """The bool matrix [len(rows), other] a table says, read as the kernels read it: bounds clamped to [0, other]."""
+    m = torch.zeros(rows.shape[0], other, dtype=torch.bool)
+    for g, row in enumerate(rows.tolist()):
+        for lo, hi in zip(row[0::2], row[1::2]):
+            m[g, min(max(lo, 0), other):min(max(hi, 0), other)] = True
+    return m
+
+
+def hand_mask(causal, device="cpu"):
+    """The IntervalMask of the matrix HAND_Q says, with the hand-written tables in place of the ones built from it."""
+    q_rows, k_rows = hand_rows(HAND_Q), hand_rows(HAND_K)
+    mask = causal.IntervalMask(table_matrix(q_rows, k_rows.shape[0]), 8)
+    mask._host = (q_rows, k_rows)
+    mask._move(torch.device(device))
+    return mask
+
+
 CASES = [
     # B, H, Lq, Lk, k_lens, q_lens, group, matrix
     (1, 2, 256, 256, None, None, 64, _tf(2)),                                    # interval ends on tile edges
@@ -47,8 +79,9 @@ CASES = [
     (2, 2, 320, 320, [280, 168], None, 56, lambda c: torch.ones(6, 6).tril()),   # the staircase, W = -1
     (1, 2, 300, 300, None, None, 300, lambda c: torch.tensor([[1]])),            # full attention
     (1, 12, 6240, 6240, None, None, 1560, _tf(2)),                               # a real chunk, 12 heads through xcd_remap
+    (1, 2, 200, 328, None, None, 8, None),                                       # hand_mask: tables no matrix builds
 ]
-DEAD_KEYS, BLIND, STAIRS, FULL = 4, 5, 6, 7
+DEAD_KEYS, BLIND, STAIRS, FULL, HAND = 4, 5, 6, 7, 9
 _CACHE = {}
 
 
@@ -57,7 +90,7 @@ def _case(idx, causal):
     if idx in _CACHE:
         return _CACHE[idx]
     B, H, Lq, Lk, klens, qlens, group, make = CASES[idx]
-    mask = causal.IntervalMask(make(causal), group, "cuda")
+    mask = hand_mask(causal, "cuda") if idx == HAND else causal.IntervalMask(make(causal), group, "cuda")
     g = torch.Generator(device="cuda").manual_seed(400 + idx)
     q, k, v = (torch.randn(B, L, H, 128, device="cuda", generator=g).bfloat16() for L in (Lq, Lk, Lk))
     do = torch.randn(B, Lq, H, 128, device="cuda", generator=g).bfloat16()
@@ -105,6 +138,22 @@ def test_cases_hold_what_they_are_for(causal):
         B, H, Lq, Lk, klens, qlens, group, make = CASES[idx]
         m = causal.IntervalMask(make(causal), group)
         assert bool(((m.q_iv[:, 3] > m.q_iv[:, 2]) & (m.q_iv[:, 2] > m.q_iv[:, 1])).any())
+    # the hand-written tables: both say one matrix, no matrix builds them, and they hold what their comment promises
+    B, H, Lq, Lk, klens, qlens, group, make = CASES[HAND]
+    m = hand_mask(causal)
+    built = causal.IntervalMask(m.vis, group)
+    assert (m.q_groups, m.k_groups) == ((Lq + group - 1) // group, (Lk + group - 1) // group) == (25, 41)
+    assert torch.equal(table_matrix(m.k_iv, m.q_groups), m.vis.t())
+    assert not torch.equal(m.q_iv, built.q_iv) and not torch.equal(m.k_iv, built.k_iv)
+    for t, other in ((m.q_iv, m.k_groups), (m.k_iv, m.q_groups)):
+        assert bool(((t[:, 1] <= t[:, 0]) & (t[:, 3] > t[:, 2])).any())            # an empty first slot, a live second one
+        assert bool((t < 0).any()) and bool((t > other).any())                     # bounds the kernels clamp
+        assert bool((t[:, 0] <= t[:, 2]).all())                                    # rows ascend
+    vis = causal.interval_visible(m, Lq, Lk)
+    assert bool(vis.any(1).all())                                                  # no live row is blind
+    assert bool(vis[:128, :64].any()) and not bool(vis[:128, 64:192].any()) and bool(vis[:128, 192:].any())
+    assert bool(vis[:64, :128].any()) and not bool(vis[64:128, :128].any()) and bool(vis[128:, :128].any())
+    assert Lq % 128 != 0 and (Lk + 63) // 64 == 6 and Lk % 64 != 0
 
 
 @pytest.mark.parametrize("idx", range(len(CASES)))

@@ -55,6 +55,41 @@ def random_three_runs(seed, nq=9, nk=24):
     raise AssertionError("no three-run matrix drawn")
 
 
+# Tables written by hand (not built from a matrix), (number of groups, row) pairs: rows with EMPTY earlier slots and a live
+# later one, bounds below 0 and above the other axis's group count (the kernels clamp them), and — group 8, Lq = 200,
+# Lk = 328 — the first 128-row workgroup runs key tiles 0, 2 and 4..5 (both jumps, a whole tile skipped at each), the second
+# tiles 0..2 (two ranges that touch) and 5; the first 128-key workgroup runs query tiles 0 and 2..3 around an empty middle
+# hull.  HAND_K says of the key groups what HAND_Q says of the query groups.
+HAND_Q = [(4, [-3, 6, 17, 22, 36, 99]), (4, [4, 6, 22, 22, 36, 41]), (4, [3, 3, 18, 20, 33, 46]), (4, [2, 2, 20, 20, 34, 38]),
+          (4, [7, 7, 8, 17, 17, 17]), (5, [0, 4, 8, 17, 40, 41])]
+HAND_K = [(4, [0, 4, 4, 4, 20, 99]), (2, [-2, 8, 8, 8, 8, 8]), (2, [0, 0, 0, 0, 0, 0]), (9, [9, 9, 9, 9, 16, 25]),
+          (1, [0, 4, 4, 4, 4, 4]), (2, [0, 0, 0, 4, 8, 12]), (2, [0, 4, 4, 4, 4, 4]), (11, [0, 0, 0, 0, 0, 0]),
+          (1, [8, 12, 12, 12, 12, 12]), (2, [8, 16, 16, 16, 16, 16]), (2, [0, 16, 16, 16, 16, 16]), (2, [-7, 12, 12, 12, 12, 12]),
+          (1, [0, 12, 12, 12, 20, 30])]
+
+
+def hand_rows(pairs):
+    return torch.tensor([row for n, row in pairs for _ in range(n)], dtype=torch.int32)
+
+
+def table_matrix(rows, other):
+    """The bool matrix [len(rows), other] a table says, read as the kernels read it: bounds clamped to [0, other]."""
+    m = torch.zeros(rows.shape[0], other, dtype=torch.bool)
+    for g, row in enumerate(rows.tolist()):
+        for lo, hi in zip(row[0::2], row[1::2]):
+            m[g, min(max(lo, 0), other):min(max(hi, 0), other)] = True
+    return m
+
+
+def hand_mask(causal, device="cpu"):
+    """The IntervalMask of the matrix HAND_Q says, with the hand-written tables in place of the ones built from it."""
+    q_rows, k_rows = hand_rows(HAND_Q), hand_rows(HAND_K)
+    mask = causal.IntervalMask(table_matrix(q_rows, k_rows.shape[0]), 8, runs=3)
+    mask._host = (q_rows, k_rows)
+    mask._move(torch.device(device))
+    return mask
+
+
 def _tf(n, W, S):
     return lambda c: c.teacher_forcing_groups(n, W, S)
 
@@ -69,8 +104,9 @@ CASES = [
     (2, 2, 560, 560, [560, 400], None, 56, lambda c: c.teacher_forcing_groups(5)),   # two runs: the bits of runs=2
     (1, 2, 240, 240, None, None, 40, lambda c: c.sink_window_groups(6, 1, 1)),   # two runs that merge: the bits of runs=2
     (1, 2, 300, 300, None, None, 300, lambda c: torch.tensor([[1]])),            # full attention: the plain kernel's bits
+    (1, 2, 200, 328, None, None, 8, None),                                       # hand_mask: tables no matrix builds
 ]
-MERGE, JUMPS, RANDOM, GROUP8, WORKLOAD, TWO_A, TWO_B, FULL = range(8)
+MERGE, JUMPS, RANDOM, GROUP8, WORKLOAD, TWO_A, TWO_B, FULL, HAND = range(9)
 _CACHE = {}
 
 
@@ -79,7 +115,7 @@ def _case(idx, causal):
     if idx in _CACHE:
         return _CACHE[idx]
     B, H, Lq, Lk, klens, qlens, group, make = CASES[idx]
-    mask = causal.IntervalMask(make(causal), group, "cuda", runs=3)
+    mask = hand_mask(causal, "cuda") if idx == HAND else causal.IntervalMask(make(causal), group, "cuda", runs=3)
     g = torch.Generator(device="cuda").manual_seed(700 + idx)
     q, k, v = (torch.randn(B, L, H, 128, device="cuda", generator=g).bfloat16() for L in (Lq, Lk, Lk))
     do = torch.randn(B, Lq, H, 128, device="cuda", generator=g).bfloat16()
@@ -151,6 +187,28 @@ def test_cases_hold_what_they_are_for(causal):
         assert not bool(three(table(idx)[0].q_iv).any())
     with pytest.raises(ValueError):                                               # and they do not hold the others
         causal.IntervalMask(CASES[MERGE][7](causal), 40)
+    # the hand-written tables: both say one matrix, no matrix builds them, and they hold what their comment promises
+    B, H, Lq, Lk, klens, qlens, group, make = CASES[HAND]
+    m = hand_mask(causal)
+    built = causal.IntervalMask(m.vis, group, runs=3)
+    assert (m.q_groups, m.k_groups) == ((Lq + group - 1) // group, (Lk + group - 1) // group) == (25, 41)
+    assert torch.equal(table_matrix(m.k_iv, m.q_groups), m.vis.t())
+    assert not torch.equal(m.q_iv, built.q_iv) and not torch.equal(m.k_iv, built.k_iv)
+    for t, other in ((m.q_iv, m.k_groups), (m.k_iv, m.q_groups)):
+        assert bool(((t[:, 1] <= t[:, 0]) & (t[:, 3] <= t[:, 2]) & (t[:, 5] > t[:, 4])).any())   # two empty slots, a live third
+        assert bool(((t[:, 1] > t[:, 0]) & (t[:, 3] <= t[:, 2]) & (t[:, 5] > t[:, 4])).any())    # an empty middle slot
+        assert bool((t < 0).any()) and bool((t > other).any())                     # bounds the kernels clamp
+        assert bool(((t[:, 0] <= t[:, 2]) & (t[:, 2] <= t[:, 4])).all())           # rows ascend
+    assert bool(three(m.q_iv).any())
+    vis = causal.interval_visible(m, Lq, Lk)
+    assert bool(vis.any(1).all())                                                  # no live row is blind
+    seen = [bool(vis[:128, 64 * t:64 * t + 64].any()) for t in range(6)]           # key tiles of the first query workgroup
+    assert seen == [True, False, True, False, True, True]
+    seen = [bool(vis[128:, 64 * t:64 * t + 64].any()) for t in range(6)]           # ... of the second
+    assert seen == [True, True, True, False, False, True]
+    seen = [bool(vis[64 * t:64 * t + 64, :128].any()) for t in range(4)]           # query tiles of the first key workgroup
+    assert seen == [True, False, True, True]
+    assert Lq % 128 != 0 and (Lk + 63) // 64 == 6 and Lk % 64 != 0
 
 
 @pytest.mark.parametrize("idx", range(len(CASES)))
