@@ -169,74 +169,89 @@ def flash_attn_takes_bounded(B, H, Lq, Lk, q_rs, k_rs, o_rs, ldv, window=(-1, -1
     return bool(lib.omh_flash_attn_takes_bounded(C.byref(a)))
 
 
-def _block_mask(block_mask, H, Lq, Lk, window=(-1, -1)):
-    """``block_mask`` (None, a ``sparse.BlockMask`` or a bool tensor) as a BlockMask on the current device, checked
-    against this call: ValueError for a band beside it, a head count other than 1 or H, or other block counts."""
-    if block_mask is None:
-        return None
-    from .sparse import BlockMask
-    if window[0] >= 0 or window[1] >= 0:
-        raise ValueError("a block mask excludes causal / a bounded window (it is not an intersection)")
-    bm = block_mask if isinstance(block_mask, BlockMask) else BlockMask(block_mask, Lq, Lk)
-    if bm.heads not in (1, H):
-        raise ValueError(f"block mask with {bm.heads} heads on a call with {H} (1 or {H} expected)")
-    if (bm.q_blocks, bm.k_blocks) != ((Lq + 127) // 128, (Lk + 127) // 128):
-        raise ValueError(f"block mask of {bm.q_blocks} x {bm.k_blocks} blocks on a call with Lq = {Lq}, Lk = {Lk} "
-                         f"({(Lq + 127) // 128} x {(Lk + 127) // 128} expected)")
-    return bm.to(torch.device("cuda", torch.cuda.current_device()))
+class AttnMask:
+    """The key restriction of one attention call, resolved by ``attn_mask``: ``kind`` is "full", "band" (``window`` =
+    (left, right); (-1, -1) for every other kind), "block", "chunk" or "interval", and ``rule`` the ``sparse.BlockMask``, the
+    ``_lib.ChunkCausalArgs`` or the ``causal.IntervalMask`` of the last three (None otherwise), on the device it runs on."""
+    __slots__ = ("kind", "window", "rule")
+
+    def __init__(self, kind, window=(-1, -1), rule=None):
+        self.kind, self.window, self.rule = kind, window, rule
+
+    def c_struct(self):
+        """What a masked entry takes beside its omh_attn_args (the rule's tensors must stay alive for the call)."""
+        return self.rule if self.kind == "chunk" else self.rule.c_struct()
 
 
-def _chunk_causal(chunk_causal, window=(-1, -1), block_mask=None):
-    """``chunk_causal`` (None or (chunk, left_chunks, q_offset)) as an omh_chunk_causal: ValueError for a band or a block
-    mask beside it (a mask is not combined with anything), a chunk below 1 or a negative offset."""
-    if chunk_causal is None:
-        return None
-    if window[0] >= 0 or window[1] >= 0:
-        raise ValueError("chunk_causal excludes causal / a bounded window (it is not an intersection)")
+# (kind, runs of an interval mask) -> the forward and the backward entry
+_MASK_ENTRIES = {("block", 0): ("omh_flash_attn_fwd_sparse_d128", "omh_flash_attn_bwd_sparse_d128"),
+                 ("chunk", 0): ("omh_flash_attn_fwd_chunk_d128", "omh_flash_attn_bwd_chunk_d128"),
+                 ("interval", 2): ("omh_flash_attn_fwd_interval_d128", "omh_flash_attn_bwd_interval_d128"),
+                 ("interval", 3): ("omh_flash_attn_fwd_interval3_d128", "omh_flash_attn_bwd_interval3_d128")}
+
+
+# what flash_attn_bwd's "needs o32" assert calls each kind
+_NEEDS_O32 = {"band": "a bounded window", "block": "a block mask", "chunk": "chunk_causal", "interval": "interval_mask"}
+
+
+def attn_mask(window=(-1, -1), block_mask=None, chunk_causal=None, interval_mask=None, *, H, Lq, Lk, device=None):
+    """The four mask keywords of the attention calls as one ``AttnMask``, checked against a call with ``H`` heads, ``Lq``
+    queries and ``Lk`` keys.  ``window`` = (left, right), a side < 0 unbounded; ``block_mask``: a ``sparse.BlockMask`` or a
+    bool block tensor; ``chunk_causal`` = (chunk, left_chunks, q_offset); ``interval_mask``: a ``causal.IntervalMask``.
+    ValueError for more than one of them (a mask is not combined with anything), a block mask of another head count
+    than 1 or H or of other block counts, chunk < 1 or q_offset < 0, an interval mask that is no IntervalMask or has
+    group counts other than ceil(Lq / group) x ceil(Lk / group).  The tables go to ``device``; None: a mask that is on a
+    GPU already stays there and one on the CPU goes to the current device."""
+    on = (window[0] >= 0 or window[1] >= 0, block_mask is not None, chunk_causal is not None, interval_mask is not None)
+    if not any(on):
+        return AttnMask("full")
+    if sum(on) > 1:
+        given = [name for name, x in zip(("causal / a bounded window", "a block mask", "chunk_causal", "interval_mask"), on) if x]
+        raise ValueError(f"{given[-1]} excludes {' / '.join(given[:-1])} (it is not an intersection)")
     if block_mask is not None:
-        raise ValueError("chunk_causal excludes a block mask (it is not an intersection)")
-    chunk, left, off = (int(x) for x in chunk_causal)
-    if chunk <= 0 or off < 0:
-        raise ValueError(f"chunk_causal = ({chunk}, {left}, {off}): chunk >= 1 and q_offset >= 0 expected")
-    big = 2 ** 31 - 1
-    return _lib.ChunkCausalArgs(min(chunk, big), -1 if left < 0 else min(left, big), min(off, big), 0)
-
-
-# IntervalMask.runs -> the forward and the backward entry
-_INTERVAL_ENTRIES = {2: ("omh_flash_attn_fwd_interval_d128", "omh_flash_attn_bwd_interval_d128"),
-                     3: ("omh_flash_attn_fwd_interval3_d128", "omh_flash_attn_bwd_interval3_d128")}
-
-
-def _interval_mask(interval_mask, Lq, Lk, window=(-1, -1), block_mask=None, chunk_causal=None, device=None):
-    """``interval_mask`` (None or a ``causal.IntervalMask``) checked against this call, with its tables on ``device`` (the
-    operands' device; the callers that only have pointers pass None: a mask that is on a GPU already stays there, one on
-    the CPU goes to the current device): ValueError for a band, a block mask or ``chunk_causal`` beside it (a mask is not
-    combined with anything), or group counts other than ceil(Lq / group) x ceil(Lk / group)."""
-    if interval_mask is None:
-        return None
-    from .causal import IntervalMask
-    if window[0] >= 0 or window[1] >= 0:
-        raise ValueError("interval_mask excludes causal / a bounded window (it is not an intersection)")
-    if block_mask is not None:
-        raise ValueError("interval_mask excludes a block mask (it is not an intersection)")
-    if chunk_causal is not None:
-        raise ValueError("interval_mask excludes chunk_causal (it is not an intersection)")
-    if not isinstance(interval_mask, IntervalMask):
-        raise ValueError("interval_mask: a causal.IntervalMask expected (it holds the group size and the device tables)")
-    g = interval_mask.group
-    if (interval_mask.q_groups, interval_mask.k_groups) != ((Lq + g - 1) // g, (Lk + g - 1) // g):
-        raise ValueError(f"interval mask of {interval_mask.q_groups} x {interval_mask.k_groups} groups of {g} on a call with "
-                         f"Lq = {Lq}, Lk = {Lk} ({(Lq + g - 1) // g} x {(Lk + g - 1) // g} expected)")
+        from .sparse import BlockMask
+        kind, rule = "block", block_mask if isinstance(block_mask, BlockMask) else BlockMask(block_mask, Lq, Lk)
+        if rule.heads not in (1, H):
+            raise ValueError(f"block mask with {rule.heads} heads on a call with {H} (1 or {H} expected)")
+        if (rule.q_blocks, rule.k_blocks) != ((Lq + 127) // 128, (Lk + 127) // 128):
+            raise ValueError(f"block mask of {rule.q_blocks} x {rule.k_blocks} blocks on a call with Lq = {Lq}, Lk = {Lk} "
+                             f"({(Lq + 127) // 128} x {(Lk + 127) // 128} expected)")
+    elif chunk_causal is not None:
+        chunk, left, off = (int(x) for x in chunk_causal)
+        if chunk <= 0 or off < 0:
+            raise ValueError(f"chunk_causal = ({chunk}, {left}, {off}): chunk >= 1 and q_offset >= 0 expected")
+        big = 2 ** 31 - 1
+        return AttnMask("chunk", rule=_lib.ChunkCausalArgs(min(chunk, big), -1 if left < 0 else min(left, big), min(off, big), 0))
+    elif interval_mask is not None:
+        from .causal import IntervalMask
+        kind, rule = "interval", interval_mask
+        if not isinstance(rule, IntervalMask):
+            raise ValueError("interval_mask: a causal.IntervalMask expected (it holds the group size and the device tables)")
+        g = rule.group
+        if (rule.q_groups, rule.k_groups) != ((Lq + g - 1) // g, (Lk + g - 1) // g):
+            raise ValueError(f"interval mask of {rule.q_groups} x {rule.k_groups} groups of {g} on a call with "
+                             f"Lq = {Lq}, Lk = {Lk} ({(Lq + g - 1) // g} x {(Lk + g - 1) // g} expected)")
+    else:
+        return AttnMask("band", (int(window[0]), int(window[1])))
     if device is None:
-        if interval_mask.device.type == "cuda":
-            return interval_mask
-        device = torch.device("cuda", torch.cuda.current_device())
-    return interval_mask.to(device)
+        device = rule.device if rule.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    return AttnMask(kind, rule=rule.to(device))
+
+
+def _resolved(mask, window, block_mask, chunk_causal, interval_mask, H, Lq, Lk, beside=None):
+    """``mask`` (an ``AttnMask`` a caller resolved already: ValueError beside any of the four keywords), or the keywords'
+    own, with its tables on the device of the tensor ``beside``."""
+    if mask is None:
+        return attn_mask(window, block_mask, chunk_causal, interval_mask, H=H, Lq=Lq, Lk=Lk,
+                         device=None if beside is None else beside.device)
+    if window[0] >= 0 or window[1] >= 0 or block_mask is not None or chunk_causal is not None or interval_mask is not None:
+        raise ValueError("mask= is the resolved form of window, block_mask, chunk_causal and interval_mask: pass it alone")
+    return mask
 
 
 def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale,
                    lse=None, q_prescaled=0, o32=None, flags=0, q_lens=None, window=(-1, -1), qk_norm2_max=None,
-                   block_mask=None, chunk_causal=None, interval_mask=None):
+                   block_mask=None, chunk_causal=None, interval_mask=None, mask=None):
     """``flags``: ATTN_SHORT_KERNEL | ATTN_ALLOW_SPLIT (include/omh.h, ABI v8): the training step pins the short-sequence
     kernel (forward and re-run take the same one) and lets it split its last round of workgroups over the keys.
     ``q_lens`` (ABI v10): int32 [B] device pointer; output rows past a sample's query length are written as zero.
@@ -252,21 +267,14 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
     ``interval_mask``: a ``causal.IntervalMask`` — up to two key intervals per group of query rows
     (omh_flash_attn_fwd_interval_d128, include/omh.h): the short-sequence kernel over the tiles inside each workgroup's
     two ranges, never split; ValueError beside a band, a block mask or ``chunk_causal``.  A mask built with ``runs=3``
-    goes to the three-run entries (omh_flash_attn_fwd_interval3_d128; ``flash_attn_bwd``: ..._bwd_interval3_d128)."""
-    im = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal)
-    cc = _chunk_causal(chunk_causal, window, block_mask)
-    bm = _block_mask(block_mask, H, Lq, Lk, window)
+    goes to the three-run entries (omh_flash_attn_fwd_interval3_d128; ``flash_attn_bwd``: ..._bwd_interval3_d128).
+    ``mask``: the four keywords before it as one ``AttnMask`` a caller resolved already (``attn_mask``); ValueError beside
+    any of them.  Without it they are resolved here, first of all (``attn_mask`` lists what it refuses)."""
+    mask = _resolved(mask, window, block_mask, chunk_causal, interval_mask, H, Lq, Lk)
     a = AttnArgs(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale, lse,
-                 int(q_prescaled), None, 0, o32, int(flags), q_lens, int(window[0]), int(window[1]))
-    if bm is not None:
-        m = bm.c_struct()
-        check(lib.omh_flash_attn_fwd_sparse_d128(C.byref(a), C.byref(m), _stream()), "omh_flash_attn_fwd_sparse_d128")
-        return
-    if cc is not None:
-        check(lib.omh_flash_attn_fwd_chunk_d128(C.byref(a), C.byref(cc), _stream()), "omh_flash_attn_fwd_chunk_d128")
-        return
-    if im is not None:
-        m, entry = im.c_struct(), _INTERVAL_ENTRIES[im.runs][0]
+                 int(q_prescaled), None, 0, o32, int(flags), q_lens, mask.window[0], mask.window[1])
+    if mask.rule is not None:
+        m, entry = mask.c_struct(), _MASK_ENTRIES[mask.kind, getattr(mask.rule, "runs", 0)][0]
         check(getattr(lib, entry)(C.byref(a), C.byref(m), _stream()), entry)
         return
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
@@ -283,7 +291,7 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
                scale: Optional[float] = None, out: Optional[torch.Tensor] = None, q_lens: Optional[torch.Tensor] = None,
                window=(-1, -1), block_mask=None, lse: Optional[torch.Tensor] = None, chunk_causal=None,
-               interval_mask=None):
+               interval_mask=None, mask=None):
     """q [B,Lq,H,128], k [B,Lk,H,128] bf16; vt [B,H*128,ldv] bf16 (V transposed,
     ldv >= roundup(Lk,64)); k_lens / q_lens int32 [B] or None.  Returns [B,Lq,H,128] bf16 (rows past q_lens: zero).
     ``window`` = (left, right): flash-attn's bottom-right aligned band (causal = (-1, 0)); (-1, -1): full attention.
@@ -294,13 +302,13 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
     no key are zero (lse = -inf).  ValueError together with a bounded ``window`` or a ``block_mask``.
     ``interval_mask``: a ``causal.IntervalMask`` (see ``flash_attn_raw``): query i sees key j iff the mask's matrix holds
     True at [i // group, j // group] (and j < k_lens[b], i < q_lens[b]); rows that see no key are zero (lse = -inf).
-    ValueError together with any of the other three."""
+    ValueError together with any of the other three.  ``mask``: as in ``flash_attn_raw``."""
     _dev(q, k, vt, k_lens, out, q_lens, lse)
     if q_lens is not None:
         assert q_lens.dtype == torch.int32 and q_lens.numel() == q.shape[0]
     B, Lq, H, D = q.shape
     Lk = k.shape[1]
-    interval_mask = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal, device=q.device)   # the tables beside q
+    mask = _resolved(mask, window, block_mask, chunk_causal, interval_mask, H, Lq, Lk, q)             # the tables beside q
     assert D == 128 and k.shape == (B, Lk, H, D) and vt.shape[0] == B and vt.shape[1] == H * D
     assert q.dtype == k.dtype == vt.dtype == torch.bfloat16
     assert q.stride(3) == 1 and q.stride(2) == D and k.stride(3) == 1 and k.stride(2) == D and vt.stride(2) == 1
@@ -310,14 +318,13 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_lens: Optio
         out = torch.empty(B, Lq, H, D, dtype=torch.bfloat16, device=q.device)
     flash_attn_raw(_p(q), _p(k), _p(vt), _p(out), _p(k_lens), B, H, Lq, Lk, q.stride(0), q.stride(1), k.stride(0),
                    k.stride(1), vt.stride(0), out.stride(0), out.stride(1), vt.stride(1),
-                   float(scale if scale is not None else D ** -0.5), q_lens=_p(q_lens), window=window,
-                   block_mask=block_mask, lse=_p(lse), chunk_causal=chunk_causal, interval_mask=interval_mask)
+                   float(scale if scale is not None else D ** -0.5), q_lens=_p(q_lens), lse=_p(lse), mask=mask)
     return out
 
 
 def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_prescaled=False, out=None, o32=None,
                    phase=0, delta=None, split=True, window=(-1, -1), q_lens=None, block_mask=None, chunk_causal=None,
-                   interval_mask=None, own_lo=None, k_bs=None):
+                   interval_mask=None, own_lo=None, k_bs=None, mask=None):
     """Fused attention backward (include/omh.h).  q, dout: bf16 [B*Lq, H*128]; k, v: bf16 [B*Lk, H*128] (row stride
     free); lse fp32 [B, H, Lq] from ``flash_attn_raw(..., lse=)``; k_lens int32 [B] or None.
     Returns fp32 dq [B*Lq, H*128], dk, dv [B*Lk, H*128] — or, with ``out=(dq, dk, dv)`` bf16 2-D tensors (row stride
@@ -344,27 +351,23 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     queries against a key / value cache.  dq is over all Lk keys; dk, dv have Lk - own_lo rows per sample (returned
     fp32 [B*(Lk - own_lo), H*128], or ``out``'s bf16 tensors of that many rows), row r for key own_lo + r; the earlier keys
     cost no dK / dV work.  ``own_lo`` = 0 is the plain call, bit for bit.
-    ``k_bs``: the batch stride of k and v in elements when it is not Lk rows (keys that sit inside a larger buffer)."""
+    ``k_bs``: the batch stride of k and v in elements when it is not Lk rows (keys that sit inside a larger buffer).
+    ``mask``: ``window`` and the three masks as one resolved ``AttnMask`` (``attn_mask``); ValueError beside any of them."""
     _dev(q, k, v, dout, lse, k_lens, o32, q_lens)
     if own_lo is not None:
         own_lo = int(own_lo)
         if o32 is None:
             raise ValueError("flash_attn_bwd: own_lo needs the forward's fp32 output (o32=)")
         if k_lens is not None or q_lens is not None or window[0] >= 0 or window[1] >= 0 or block_mask is not None or \
-                chunk_causal is not None or interval_mask is not None:
+                chunk_causal is not None or interval_mask is not None or (mask is not None and mask.kind != "full"):
             raise ValueError("flash_attn_bwd: own_lo excludes k_lens, q_lens, a bounded window and every mask")
         if not 0 <= own_lo < Lk or own_lo % 8:
             raise ValueError(f"flash_attn_bwd: own_lo = {own_lo}; a multiple of 8 in [0, Lk = {Lk}) is expected")
     Lown = Lk - (own_lo or 0)                                      # rows of dk / dv per sample
-    im = _interval_mask(interval_mask, Lq, Lk, window, block_mask, chunk_causal, device=q.device)
-    if im is not None:
-        assert o32 is not None, "flash_attn_bwd: interval_mask needs the forward's fp32 output (o32=)"
-    cc = _chunk_causal(chunk_causal, window, block_mask)
-    if cc is not None:
-        assert o32 is not None, "flash_attn_bwd: chunk_causal needs the forward's fp32 output (o32=)"
-    bm = _block_mask(block_mask, H, Lq, Lk, window)
-    if bm is not None:
-        assert o32 is not None, "flash_attn_bwd: a block mask needs the forward's fp32 output (o32=)"
+    mask = _resolved(mask, window, block_mask, chunk_causal, interval_mask, H, Lq, Lk, q)
+    if o32 is None:
+        what = "q_lens" if mask.kind == "full" and q_lens is not None else _NEEDS_O32.get(mask.kind)
+        assert what is None, f"flash_attn_bwd: {what} needs the forward's fp32 output (o32=)"
     d = H * 128
     for t in (q, k, v, dout):
         assert t.dtype == torch.bfloat16 and t.stride(-1) == 1 and t.shape[-1] == d
@@ -375,10 +378,7 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
     ldq, ldk = (Lq + 63) // 64 * 64, (Lk + 63) // 64 * 64
     qt = dot = kt = None
     if q_lens is not None:
-        assert o32 is not None, "flash_attn_bwd: q_lens needs the forward's fp32 output (o32=)"
         assert q_lens.dtype == torch.int32 and q_lens.numel() == B and q_lens.is_contiguous()
-    if window[0] >= 0 or window[1] >= 0:
-        assert o32 is not None, "flash_attn_bwd: a bounded window needs the forward's fp32 output (o32=)"
     if o32 is None:
         def padded(L, ld):                     # only the pad columns need the zeros (the transpose writes the rest)
             t = torch.empty(B, d, ld, dtype=torch.bfloat16, device=dev)
@@ -413,25 +413,16 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
                          Lq * dq.stride(0), dq.stride(0), Lown * dk.stride(0), dk.stride(0), d * ldq, d * ldk, ldq, ldk,
                          float(scale if scale is not None else 128 ** -0.5), int(q_prescaled), bf, _p(o32), int(phase),
                          None, 0)
-    if bm is not None:
-        m = bm.c_struct()
-        check(lib.omh_flash_attn_bwd_sparse_d128(C.byref(a), _p(q_lens), C.byref(m), _stream()),
-              "omh_flash_attn_bwd_sparse_d128")
-        return dq, dk, dv
-    if cc is not None:
-        check(lib.omh_flash_attn_bwd_chunk_d128(C.byref(a), _p(q_lens), C.byref(cc), _stream()),
-              "omh_flash_attn_bwd_chunk_d128")
-        return dq, dk, dv
-    if im is not None:
-        m, entry = im.c_struct(), _INTERVAL_ENTRIES[im.runs][1]
+    if mask.rule is not None:
+        m, entry = mask.c_struct(), _MASK_ENTRIES[mask.kind, getattr(mask.rule, "runs", 0)][1]
         check(getattr(lib, entry)(C.byref(a), _p(q_lens), C.byref(m), _stream()), entry)
         return dq, dk, dv
     if q_lens is not None:
-        check(lib.omh_flash_attn_bwd_varlen_d128(C.byref(a), _p(q_lens), int(window[0]), int(window[1]), _stream()),
+        check(lib.omh_flash_attn_bwd_varlen_d128(C.byref(a), _p(q_lens), mask.window[0], mask.window[1], _stream()),
               "omh_flash_attn_bwd_varlen_d128")
         return dq, dk, dv
-    if window[0] >= 0 or window[1] >= 0:
-        check(lib.omh_flash_attn_bwd_band_d128(C.byref(a), int(window[0]), int(window[1]), _stream()),
+    if mask.kind == "band":
+        check(lib.omh_flash_attn_bwd_band_d128(C.byref(a), mask.window[0], mask.window[1], _stream()),
               "omh_flash_attn_bwd_band_d128")
         return dq, dk, dv
     if own_lo is not None:
@@ -454,7 +445,7 @@ class _FlashAttnFunc(torch.autograd.Function):
     omh_flash_attn_bwd_* call backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, k_lens, q_lens, scale, window, block_mask=None, chunk_causal=None, interval_mask=None):
+    def forward(ctx, q, k, v, k_lens, q_lens, scale, mask):
         _dev(q, k, v, k_lens, q_lens)
         B, Lq, H, D = q.shape
         Lk = k.shape[1]
@@ -474,11 +465,9 @@ class _FlashAttnFunc(torch.autograd.Function):
         lse = torch.empty(B, H, Lq, dtype=torch.float32, device=dev)
         # pinned to the short-sequence kernel, as the training step pins it (never split: this flag alone)
         flash_attn_raw(_p(q), _p(k), _p(vt), _p(o), _p(k_lens), B, H, Lq, Lk, Lq * d, d, Lk * d, d, d * Lp, Lq * d, d, Lp,
-                       scale, lse=_p(lse), o32=_p(o32), flags=ATTN_SHORT_KERNEL, q_lens=_p(q_lens), window=window,
-                       block_mask=block_mask, chunk_causal=chunk_causal, interval_mask=interval_mask)
+                       scale, lse=_p(lse), o32=_p(o32), flags=ATTN_SHORT_KERNEL, q_lens=_p(q_lens), mask=mask)
         ctx.save_for_backward(q, k, v, o, lse, o32, k_lens, q_lens)
-        ctx.scale, ctx.window, ctx.block_mask, ctx.chunk_causal = scale, window, block_mask, chunk_causal
-        ctx.interval_mask = interval_mask
+        ctx.scale, ctx.mask = scale, mask
         return o
 
     @staticmethod
@@ -491,16 +480,15 @@ class _FlashAttnFunc(torch.autograd.Function):
                torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device),
                torch.empty(B * Lk, d, dtype=torch.bfloat16, device=q.device))
         flash_attn_bwd(q.view(B * Lq, d), k.view(B * Lk, d), v.view(B * Lk, d), o.view(B * Lq, d), do.view(B * Lq, d), lse,
-                       k_lens, B, H, Lq, Lk, scale=ctx.scale, out=out, o32=o32, window=ctx.window, q_lens=q_lens,
-                       block_mask=ctx.block_mask, chunk_causal=ctx.chunk_causal, interval_mask=ctx.interval_mask)
+                       k_lens, B, H, Lq, Lk, scale=ctx.scale, out=out, o32=o32, q_lens=q_lens, mask=ctx.mask)
         need = ctx.needs_input_grad
         return (out[0].view(B, Lq, H, D) if need[0] else None, out[1].view(B, Lk, H, D) if need[1] else None,
-                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None, None, None, None)
+                out[2].view(B, Lk, H, D) if need[2] else None, None, None, None, None)
 
 
 def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: Optional[torch.Tensor] = None,
                     q_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None, window=(-1, -1),
-                    block_mask=None, chunk_causal=None, interval_mask=None):
+                    block_mask=None, chunk_causal=None, interval_mask=None, mask=None):
     """Differentiable attention (a ``torch.autograd.Function``): q [B,Lq,H,128], k, v [B,Lk,H,128] bf16 (V row-major: the
     padded V^T the kernel reads is built here, by the transpose kernel); k_lens / q_lens int32 [B] or None; ``window`` =
     (left, right) as in ``flash_attn``.  Returns [B,Lq,H,128] bf16 — the bits of ``flash_attn`` on the same inputs
@@ -511,17 +499,10 @@ def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: O
     the block-list kernels, omh_flash_attn_*_sparse_d128; ValueError beside a bounded ``window``).  ``chunk_causal`` =
     (chunk, left_chunks, q_offset) as in ``flash_attn`` (omh_flash_attn_*_chunk_d128, honouring q_lens / k_lens; ValueError
     beside a bounded ``window`` or a ``block_mask``).  ``interval_mask``: a ``causal.IntervalMask`` as in ``flash_attn``
-    (omh_flash_attn_*_interval_d128, honouring q_lens / k_lens; ValueError beside any of the other three)."""
-    window = (int(window[0]) if window[0] >= 0 else -1, int(window[1]) if window[1] >= 0 else -1)
-    if interval_mask is not None:
-        interval_mask = _interval_mask(interval_mask, q.shape[1], k.shape[1], window, block_mask, chunk_causal, device=q.device)
-    if chunk_causal is not None:
-        _chunk_causal(chunk_causal, window, block_mask)
-        chunk_causal = tuple(int(x) for x in chunk_causal)
-    if block_mask is not None:
-        block_mask = _block_mask(block_mask, q.shape[2], q.shape[1], k.shape[1], window)
-    return _FlashAttnFunc.apply(q, k, v, k_lens, q_lens, float(scale if scale is not None else 128 ** -0.5), window,
-                                block_mask, chunk_causal, interval_mask)
+    (omh_flash_attn_*_interval_d128, honouring q_lens / k_lens; ValueError beside any of the other three).
+    ``mask``: as in ``flash_attn_raw``; resolved once, here, and kept for the backward."""
+    mask = _resolved(mask, window, block_mask, chunk_causal, interval_mask, q.shape[2], q.shape[1], k.shape[1], q)
+    return _FlashAttnFunc.apply(q, k, v, k_lens, q_lens, float(scale if scale is not None else 128 ** -0.5), mask)
 
 
 def layernorm_modulate_raw(x, y, rows, dim, eps, mul_const, mul0, mul1, mul1_stride, add0, add1, add1_stride,

@@ -79,20 +79,15 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     if causal:
         wr = 0
     window = (wl if wl >= 0 else -1, wr if wr >= 0 else -1)
-    if block_mask is not None and window != (-1, -1):
-        raise ValueError("flash_attention: block_mask excludes causal / a bounded window_size")
-    if chunk_causal is not None:
-        if window != (-1, -1) or block_mask is not None:
-            raise ValueError("flash_attention: chunk_causal excludes causal / a bounded window_size / block_mask")
-        chunk_causal = tuple(int(x) for x in chunk_causal)
-        if len(chunk_causal) != 3 or chunk_causal[0] <= 0 or chunk_causal[2] < 0:
-            raise ValueError("flash_attention: chunk_causal = (chunk >= 1, left_chunks, q_offset >= 0) expected")
-    if interval_mask is not None:
-        if window != (-1, -1) or block_mask is not None or chunk_causal is not None:
-            raise ValueError("flash_attention: interval_mask excludes causal / a bounded window_size / block_mask / chunk_causal")
-        if not hasattr(interval_mask, "q_iv"):
-            raise ValueError("flash_attention: interval_mask must be a causal.IntervalMask")
-    if window != (-1, -1) and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+    # one of the five kinds, or a ValueError before anything touches a device (ops.attn_mask); a block policy stands in for
+    # the mask it chooses below, from q and k
+    policy = block_mask if isinstance(block_mask, _sparse.DynamicBlockPolicy) else None
+    resolve = lambda bm: ops.attn_mask(window, bm, chunk_causal, interval_mask, H=q.shape[2], Lq=q.shape[1], Lk=k.shape[1],
+                                       device=q.device)
+    mask = resolve(None if policy is not None else block_mask)
+    if policy is not None and mask.kind != "full":
+        raise ValueError("flash_attention: block_mask excludes causal / a bounded window_size / chunk_causal / interval_mask")
+    if mask.kind == "band" and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         raise NotImplementedError("flash_attention on gfx950: causal / window_size are forward-only through this wrapper; "
                                   "the differentiable band is ops.flash_attn_func(window=)")
     B, Lq, N, D = q.shape
@@ -104,13 +99,12 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         q = q * q_scale
     kl = None if k_lens is None else k_lens.to(device=q.device, dtype=torch.int32).contiguous()
     ql = None if q_lens is None else q_lens.to(device=q.device, dtype=torch.int32).contiguous()
-    if isinstance(block_mask, _sparse.DynamicBlockPolicy):
-        block_mask = _sparse.block_mask_from_qk(q.detach().to(torch.bfloat16), k.detach().to(torch.bfloat16), block_mask, ql, kl,
-                                                (softmax_scale if softmax_scale is not None else D ** -0.5) * math.log2(math.e))
+    if policy is not None:
+        mask = resolve(_sparse.block_mask_from_qk(q.detach().to(torch.bfloat16), k.detach().to(torch.bfloat16), policy, ql, kl,
+                                                  (softmax_scale if softmax_scale is not None else D ** -0.5) * math.log2(math.e)))
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         o = ops.flash_attn_func(q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), kl, ql,
-                                scale=softmax_scale, window=window, block_mask=block_mask, chunk_causal=chunk_causal,
-                                interval_mask=interval_mask)
+                                scale=softmax_scale, mask=mask)
         return o.type(out_dtype)
     qb = q.to(torch.bfloat16).contiguous()
     kb = k.to(torch.bfloat16).contiguous()
@@ -119,8 +113,7 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     vt[:, :, :Lk] = v.to(torch.bfloat16).reshape(B, Lk, N * D).transpose(1, 2)   # layout change only
     # q_lens (attention.py:55-60,79): the reference cuts the queries past q_lens[b] out of the packed batch — and can only
     # un-flatten the result when every q_lens[b] == Lq (attention.py:110); here those rows come back as zeros
-    o = ops.flash_attn(qb, kb, vt, kl, scale=softmax_scale, q_lens=ql, window=window, block_mask=block_mask,
-                       chunk_causal=chunk_causal, interval_mask=interval_mask)
+    o = ops.flash_attn(qb, kb, vt, kl, scale=softmax_scale, q_lens=ql, mask=mask)
     return o.type(out_dtype)
 
 

@@ -174,15 +174,19 @@ class _FwdCtx:
     """Per-forward shared state handed to every block."""
     __slots__ = ("B", "S", "dim", "e0", "seq_lens32", "ctx_lens32", "grid32", "rope_cos", "rope_sin", "ctx",
                  "Lc", "n_img", "seq_lens_host", "ctx_lens_host", "kv", "split_k",
-                 # chunk: (tokens per chunk, left_chunks, 0) under WanModel.set_causal_chunks, else None / unset;
+                 # chunk: (tokens per chunk, left_chunks, 0) under WanModel.set_causal_chunks, else None;
                  # cache, cache_layer, cache_lo: WanModel.forward_chunk (a causal.KVCache, the running block, first key)
                  "chunk", "cache", "cache_layer", "cache_lo",
                  # rpb: rows of the sequence that share one row of e0 (seq_len, or h * w with a per-frame t);
-                 # interval: a causal.IntervalMask every self-attention runs under (forward_teacher_forcing), else unset
+                 # interval: a causal.IntervalMask every self-attention runs under (forward_teacher_forcing), else None
                  "rpb", "interval",
                  # cache_pos, cache_hi, cache_mask: forward_chunk on a causal.RollingKVCache (the chunk's slot, the end of
-                 # the filled slots, the mask over stale keys of a short last chunk), else None / unset
+                 # the filled slots, the resolved ops.AttnMask over stale keys of a short last chunk), else None
                  "cache_pos", "cache_hi", "cache_mask")
+
+    def __init__(self):
+        self.kv = self.chunk = self.cache = self.cache_layer = self.cache_lo = self.rpb = self.interval = None
+        self.cache_pos = self.cache_hi = self.cache_mask = None
 
 
 class ContextState:
@@ -248,33 +252,30 @@ class WanSelfAttention(nn.Module):
 
     def _dynamic_mask(self, q, k, B, S, lens32):
         """The block mask the layer's policy chooses for this call's q and k (bf16 [B*S, dim], q already carrying
-        softmax_scale * log2(e)), built on the device: sparse.block_mask_from_rows.  None without a policy."""
-        pol = self._block_policy
-        if pol is None:
-            return None
-        if self._block_mask is not None:
-            raise ValueError("the layer has both a static block mask and a block policy")
-        if self.window_size[0] >= 0 or self.window_size[1] >= 0:
-            raise ValueError(f"a block policy excludes window_size={tuple(self.window_size)} (it is not an intersection)")
-        bm = _sparse().block_mask_from_rows(q, k, B, self.num_heads, S, S, self.dim, self.dim, pol, 1.0, None, lens32)
+        softmax_scale * log2(e)), built on the device: sparse.block_mask_from_rows."""
+        bm = _sparse().block_mask_from_rows(q, k, B, self.num_heads, S, S, self.dim, self.dim, self._block_policy, 1.0, None,
+                                            lens32)
         self.last_block_mask = bm
         return bm
 
-    def _mask_for(self, S):
-        """The block mask of a self-attention over S (padded) positions, or None; ValueError when it was built for
-        another number of blocks or the layer also has a bounded window."""
-        bm = self._block_mask
-        if bm is None:
+    def _call_mask(self, fc, device, chosen=None):
+        """The ``ops.AttnMask`` of a self-attention over fc.S (padded) positions, resolved on ``device``: the layer's band,
+        its block mask, or the context's staircase / interval mask.  Under a block policy the mask is chosen after q and k
+        exist: None then, and the call again with ``chosen`` = ``_dynamic_mask``'s BlockMask resolves it.  ValueError for
+        two restrictions at once (they are not intersected) and for a block mask of other block or head counts."""
+        window, bm, policy = tuple(self.window_size), self._block_mask, self._block_policy
+        if bm is not None and policy is not None:
+            raise ValueError("the layer has both a static block mask and a block policy")
+        blocks, banded = bm is not None or policy is not None, window[0] >= 0 or window[1] >= 0
+        if blocks and banded:
+            raise ValueError(f"a block mask / policy excludes window_size={window} (it is not an intersection)")
+        if (blocks or banded) and (fc.chunk is not None or fc.interval is not None):
+            raise ValueError(f"{'causal chunks' if fc.chunk is not None else 'teacher forcing'} exclude(s) a block mask, a "
+                             "block policy and a bounded window_size")
+        if policy is not None and chosen is None:
             return None
-        if self.window_size[0] >= 0 or self.window_size[1] >= 0:
-            raise ValueError(f"a block mask excludes window_size={tuple(self.window_size)} (it is not an intersection)")
-        nb = (S + 127) // 128
-        if bm.q_blocks != nb or bm.k_blocks != nb:
-            raise ValueError(f"the attention block mask has {bm.q_blocks} x {bm.k_blocks} blocks; seq_len = {S} needs "
-                             f"{nb} x {nb} (ceil(seq_len / 128))")
-        if bm.heads not in (1, self.num_heads):
-            raise ValueError(f"the attention block mask has {bm.heads} heads; 1 or {self.num_heads} expected")
-        return bm
+        return ops.attn_mask(window, bm if chosen is None else chosen, fc.chunk, fc.interval, H=self.num_heads, Lq=fc.S,
+                             Lk=fc.S, device=device)
 
     # packed weights ---------------------------------------------------------
     def _w_qk(self):
@@ -299,19 +300,12 @@ class WanSelfAttention(nn.Module):
 
     def _attend(self, h, fc: "_FwdCtx"):
         """h bf16 [B*S, dim] -> attention output bf16 [B*S, dim] (before o-proj)."""
-        if getattr(fc, "cache", None) is not None:
-            return self._attend_cached(h, fc)
+        if fc.cache is not None:
+            (wqk, bqk), (wv, bv) = self._w_qk(), self._w("v")
+            return self._attend_cached(h, fc, ptr(wqk), ptr(bqk), ptr(wv), ptr(bv))
         B, S, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
         R = B * S
-        bmask = self._mask_for(S)
-        chunk = getattr(fc, "chunk", None)                 # WanModel.set_causal_chunks: the staircase kernels
-        if chunk is not None and (bmask is not None or self._block_policy is not None or self.window_size[0] >= 0
-                                  or self.window_size[1] >= 0):
-            raise ValueError("causal chunks exclude a block mask, a block policy and a bounded window_size")
-        ivl = getattr(fc, "interval", None)                # WanModel.forward_teacher_forcing: the interval-mask kernels
-        if ivl is not None and (bmask is not None or self._block_policy is not None or self.window_size[0] >= 0
-                                or self.window_size[1] >= 0):
-            raise ValueError("teacher forcing excludes a block mask, a block policy and a bounded window_size")
+        mask = self._call_mask(fc, h.device)               # None: a block policy, which chooses below
         # q|k projection kept in bf16 (fp32 accumulate): the normalisation statistics are taken in fp32 from
         # it; measured effect on the 30-layer output < 1e-3 relative RMS, and it halves this step's traffic
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
@@ -344,12 +338,10 @@ class WanSelfAttention(nn.Module):
         wq, wk = self._norm_w("norm_q"), self._norm_w("norm_k")          # q and k: one launch (two column segments)
         # where the long-sequence attention stream runs, the norm kernel also emits max |q|^2, |k|^2 per (sample, head): the
         # stream then needs no running max (a bound on this call's scores: ops.flash_attn_raw, qk_norm2_max)
-        window = tuple(self.window_size)
         nmax = None
-        # (a block mask runs the short-sequence kernel over its lists: no long-sequence stream, so no bound either)
-        # (nor does the staircase: the short-sequence kernel too)
-        if chunk is None and ivl is None and bmask is None and self._block_policy is None and D == 128 and d <= 5120 and \
-                ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, window):
+        # (a block, staircase or interval mask runs the short-sequence kernel: no long-sequence stream, so no bound either)
+        if mask is not None and mask.rule is None and D == 128 and d <= 5120 and \
+                ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, mask.window):
             nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
         self.last_qk_norm2_max = nmax                                    # (read by tools/attn_bound_values.py)
         norm_args = (ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(wq) if wq is not None else None,
@@ -360,8 +352,8 @@ class WanSelfAttention(nn.Module):
         else:
             ops.rmsnorm_rope_bf16_pair_raw(*norm_args, out_scale0=q_scale, out_scale1=1.0)
         del qk
-        if self._block_policy is not None:             # the mask is chosen from the q and k this call attends with
-            bmask = self._dynamic_mask(q, k, B, S, fc.seq_lens32)
+        if mask is None:                               # the mask is chosen from the q and k this call attends with
+            mask = self._call_mask(fc, h.device, self._dynamic_mask(q, k, B, S, fc.seq_lens32))
         if not fused:
             # V^T[b] = Wv h_b^T + bv  ->  [B, dim, Sp]   (pad columns stay zero)
             wv, bv = self._w("v")
@@ -370,32 +362,35 @@ class WanSelfAttention(nn.Module):
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
-                           d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1, window=window,
-                           qk_norm2_max=ptr(nmax) if nmax is not None else None, block_mask=bmask, chunk_causal=chunk,
-                           interval_mask=ivl)
+                           d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1,
+                           qk_norm2_max=ptr(nmax) if nmax is not None else None, mask=mask)
         return o
 
-    def _attend_cached(self, h, fc: "_FwdCtx"):
+    def _attend_cached(self, h, fc: "_FwdCtx", wqk, bqk, wv, bv, extras=False):
         """``_attend`` for WanModel.forward_chunk: h holds the rows of ONE chunk per sample.  q, k, v are projected for
-        these rows only; k (normalised, rotated) lands in rows [length, length + C) of this layer's cache and V^T in the
+        these rows only (``wqk`` / ``bqk``, ``wv`` / ``bv``: pointers to the q | k and the v weights and biases the caller
+        uses); k (normalised, rotated) lands in rows [length, length + C) of this layer's cache and V^T in the
         same columns, straight from the V^T product (ldc = the cache pitch); plain attention then runs with Lq = C over the
         keys [lo, length + C) of the cache — a pointer offset, no copy.  The launches of ``_attend`` at seq_len = C
         otherwise, so on an empty cache the result has its bits.
         A ``causal.RollingKVCache``: the chunk's rows go to ``fc.cache_pos`` (its slot) and the keys are [0, fc.cache_hi) —
         every filled slot; softmax attention does not depend on the order of its keys, and they carry absolute rotary
         positions.  ``fc.cache_mask`` (a short last chunk in a wrapped ring): the interval kernel skips the stale keys
-        behind the chunk in its slot."""
+        behind the chunk in its slot.
+        ``extras`` (forward_chunk(grad=True), model_train.py): ``lse`` and ``o32`` are asked for on top (the choice of the
+        kernel does not depend on them), and the chunk's own k rows and V (row-major, what the backward reads) are copied
+        out: the next denoising step and the commit pass overwrite them in the cache.
+        Returns o; with ``extras`` (o, qk, q, k_own, v_own, lse, o32)."""
         B, C, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
         cache, lo = fc.cache, fc.cache_lo
         kc, vtc = cache.k[fc.cache_layer], cache.vt[fc.cache_layer]
         L0, cap, pitch = cache.length, cache.cap, cache.pitch
         hi = L0 + C
-        if getattr(fc, "cache_pos", None) is not None:
+        if fc.cache_pos is not None:
             L0, hi = fc.cache_pos, fc.cache_hi             # (L0: where this chunk's rows go)
         R = B * C
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
-        wqk, bqk = self._w_qk()
-        ops.gemm_raw(ptr(h), ptr(wqk), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(bqk), bias_mode=BIAS_N)
+        ops.gemm_raw(ptr(h), wqk, ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=bqk, bias_mode=BIAS_N)
         q = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         wq, wk = self._norm_w("norm_q"), self._norm_w("norm_k")
         for b in range(B):                                 # one launch per sample: its k rows sit at their own place in the cache
@@ -404,21 +399,24 @@ class WanSelfAttention(nn.Module):
                                            self.eps, int(self.qk_norm), ptr(fc.rope_cos), ptr(fc.rope_sin),
                                            fc.rope_cos.shape[0], D, ptr(fc.grid32, 3 * b), C,
                                            out_scale0=D ** -0.5 * 1.4426950408889634, out_scale1=1.0)
-        del qk
-        wv, bv = self._w("v")
-        ops.gemm_raw(ptr(wv), ptr(h), ptr(vtc, L0), d, C, d, d, d, pitch, EPI_BF16, bias=ptr(bv), bias_mode=BIAS_M, batch=B,
+        ops.gemm_raw(wv, ptr(h), ptr(vtc, L0), d, C, d, d, d, pitch, EPI_BF16, bias=bv, bias_mode=BIAS_M, batch=B,
                      strideA=0, strideB=C * d, strideC=d * pitch)
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
-        Lk = hi - lo
-        if getattr(fc, "cache_mask", None) is not None:
-            ops.flash_attn_raw(ptr(q), ptr(kc, lo * d), ptr(vtc, lo), ptr(o), None, B, N, C, Lk, C * d, d, cap * d, d,
-                               d * pitch, C * d, d, pitch, D ** -0.5, q_prescaled=1, interval_mask=fc.cache_mask)
+        lse = torch.empty(B, N, C, dtype=torch.float32, device=h.device) if extras else None
+        o32 = torch.empty(R, d, dtype=torch.float32, device=h.device) if extras else None
+        # without a mask, pinned to the short-sequence kernel: its V^T reads end at most 63 columns past the last key (the
+        # cache keeps that much slack behind its last row); a chunk of queries does not reach the long-sequence dispatch at
+        # 12 heads
+        ops.flash_attn_raw(ptr(q), ptr(kc, lo * d), ptr(vtc, lo), ptr(o), None, B, N, C, hi - lo, C * d, d, cap * d, d,
+                           d * pitch, C * d, d, pitch, D ** -0.5, lse=ptr(lse) if extras else None, q_prescaled=1,
+                           o32=ptr(o32) if extras else None, flags=0 if fc.cache_mask is not None else ops.ATTN_SHORT_KERNEL,
+                           mask=fc.cache_mask)
+        if not extras:
             return o
-        # pinned to the short-sequence kernel: its V^T reads end at most 63 columns past the last key (the cache keeps
-        # that much slack behind its last row); a chunk of queries does not reach the long-sequence dispatch at 12 heads
-        ops.flash_attn_raw(ptr(q), ptr(kc, lo * d), ptr(vtc, lo), ptr(o), None, B, N, C, Lk, C * d, d, cap * d, d,
-                           d * pitch, C * d, d, pitch, D ** -0.5, q_prescaled=1, flags=ops.ATTN_SHORT_KERNEL)
-        return o
+        k_own = kc[:, L0:L0 + C].clone()                   # [B, C, d]
+        v_own = torch.empty(B, C, d, dtype=torch.bfloat16, device=h.device)
+        ops.transpose_bf16_raw(ptr(vtc, L0), ptr(v_own), d, C, pitch, d, batch=B, bs_in=d * pitch, bs_out=C * d)
+        return o, qk, q, k_own.view(R, d), v_own.view(R, d), lse, o32
 
     def forward(self, x, seq_lens, grid_sizes, freqs, _fc: Optional["_FwdCtx"] = None):
         """Reference signature (model.py:132): x [B, L, C] -> [B, L, C] fp32."""
@@ -436,7 +434,7 @@ class WanT2VCrossAttention(WanSelfAttention):
 
     def _context_kv(self, fc: "_FwdCtx", kname="k", vname="v", nname="norm_k", lo=0, hi=None):
         """K (normalised, bf16 [B*L, dim]) and V^T ([B, dim, Lp]) of context rows [lo, hi)."""
-        kv = getattr(fc, "kv", None)
+        kv = fc.kv
         if kv is not None and (id(self), kname) in kv:
             return kv[(id(self), kname)]
         B, d = fc.B, self.dim
@@ -559,7 +557,7 @@ class WanAttentionBlock(nn.Module):
             mod = mod.float()
         e0 = fc.e0
         xp, six_d = ptr(x), 6 * d
-        rpb = getattr(fc, "rpb", None) or S                # rows per row of e0: the sequence, or a frame (per-frame t)
+        rpb = fc.rpb or S                                  # rows per row of e0: the sequence, or a frame (per-frame t)
 
         def ln_mod(shift_i, scale_i):
             h = torch.empty(R, d, dtype=torch.bfloat16, device=x.device)
@@ -960,7 +958,7 @@ class WanModel(nn.Module):
     def _stale_mask(self, cache, pos, C, tpf, device):
         """The interval mask of a short chunk (``C`` tokens at ``pos``) in a wrapped ring: every query sees the keys
         [0, pos + C) and [pos + chunk_tokens, cap) — not the stale keys behind it in its slot.  Groups of one frame's
-        tokens (>= 8: ValueError otherwise); cached per shape."""
+        tokens (>= 8: ValueError otherwise); resolved (an ``ops.AttnMask``) and cached per shape."""
         from ... import causal as _causal
         if tpf < 8:
             raise ValueError(f"forward_chunk: a short last chunk in a full RollingKVCache needs at least 8 tokens per frame, "
@@ -972,7 +970,8 @@ class WanModel(nn.Module):
                 masks.clear()
             vis = torch.ones(C // tpf, cache.cap // tpf, dtype=torch.bool)
             vis[:, (pos + C) // tpf:(pos + cache.chunk_tokens) // tpf] = False
-            masks[key] = _causal.IntervalMask(vis, tpf, device)
+            masks[key] = ops.attn_mask(interval_mask=_causal.IntervalMask(vis, tpf, device), H=self.num_heads, Lq=C,
+                                       Lk=cache.cap, device=device)
         return masks[key]
 
     def _rope_shifted(self, device, frame_offset):
@@ -1189,6 +1188,13 @@ class WanModel(nn.Module):
                              f"({self.freqs.shape[0]} frames)")
         return C, lo, frame_offset
 
+    def _chunk_ctx(self, fc, cache, lo, frame_offset):
+        """An embedded context as that of one chunk against ``cache`` from key ``lo`` on, at ``frame_offset``."""
+        fc.chunk = fc.interval = None                      # the cache IS the causal structure: plain attention over it
+        fc.rope_cos, fc.rope_sin = self._rope_shifted(fc.e0.device, frame_offset)
+        fc.cache, fc.cache_lo = cache, lo
+        fc.cache_pos = fc.cache_hi = fc.cache_mask = None
+
     def _forward_chunk(self, x, t, context, cache, frame_offset, commit, clip_fea, y):
         C, lo, frame_offset = self._chunk_geometry(x, t, cache, frame_offset)
         L0 = cache.length
@@ -1197,11 +1203,7 @@ class WanModel(nn.Module):
             tpf = (x[0].shape[2] // self.patch_size[1]) * (x[0].shape[3] // self.patch_size[2])
             Ct = self._causal_chunks[0] * tpf
         xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, C, clip_fea, y)
-        fc.chunk = None                                    # the cache IS the causal structure: plain attention over it
-        fc.interval = None
-        fc.rope_cos, fc.rope_sin = self._rope_shifted(xs.device, frame_offset)
-        fc.cache, fc.cache_lo = cache, lo
-        fc.cache_pos = fc.cache_hi = fc.cache_mask = None
+        self._chunk_ctx(fc, cache, lo, frame_offset)
         if rolling:
             # the chunk's slot; the keys are every filled slot.  Before the ring wraps they are [0, L0 + C), KVCache's range;
             # afterwards all slots — one contiguous range, whatever chunk sits where

@@ -304,24 +304,19 @@ _side2 = {}
 _ALWAYS_COPY_DX = os.environ.get("OMH_BLOCK_DX_COPY", "0") == "1"
 
 
-def _attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, out, o32, q_prescaled, window=(-1, -1), block_mask=None,
-              chunk_causal=None, interval_mask=None, own_lo=None):
+def _attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, out, o32, q_prescaled, mask=None, own_lo=None):
     """ops.flash_attn_bwd on the block's pre-scaled q, bf16 gradients into ``out`` — as one call, or (OMH_ATTN_BWD_SPLIT)
-    as delta -> {dQ on this stream, dK / dV on a second one} -> join.  ``window``: the self-attention's band (the
-    band kernels; o32 required).  ``block_mask``: the self-attention's block mask (the block-list kernels; o32 required).
-    ``chunk_causal``: the self-attention's staircase (WanModel.set_causal_chunks; the chunk kernels; o32 required).
-    ``interval_mask``: the self-attention's interval mask (WanModel.forward_teacher_forcing; o32 required).
+    as delta -> {dQ on this stream, dK / dV on a second one} -> join.  ``mask``: the self-attention's resolved
+    ``ops.AttnMask`` (band, block mask, staircase or interval mask: o32 required); None: full attention.
     ``own_lo``: the keys before it are a cache's constants (forward_chunk(grad=True); omh_flash_attn_bwd_cached_d128;
     o32 required): dk / dv of ``out`` hold the Lk - own_lo own rows."""
     split = _ATTN_SPLIT == "1" or (_ATTN_SPLIT == "auto" and B * N * ((Lq + 127) // 128) > 512)
     if not (split and o32 is not None):
         return ops.flash_attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, q_prescaled=q_prescaled, out=out, o32=o32,
-                                  window=window, block_mask=block_mask, chunk_causal=chunk_causal,
-                                  interval_mask=interval_mask, own_lo=own_lo)
+                                  mask=mask, own_lo=own_lo)
     dev = q.device
     delta = torch.empty(B, N, Lq, dtype=torch.float32, device=dev)
-    kw = dict(q_prescaled=q_prescaled, out=out, o32=o32, delta=delta, window=window, block_mask=block_mask,
-              chunk_causal=chunk_causal, interval_mask=interval_mask, own_lo=own_lo)
+    kw = dict(q_prescaled=q_prescaled, out=out, o32=o32, delta=delta, mask=mask, own_lo=own_lo)
     ops.flash_attn_bwd(q, k, v, o, do, lse, lens, B, N, Lq, Lk, scale, phase=1, **kw)
     main = torch.cuda.current_stream(dev)
     s2 = _side2.get(dev)
@@ -683,45 +678,6 @@ def _vt_buffer(model, key, B, d, Lp, L, dev, keep):
     return t
 
 
-def _cached_self_attention(sa, fc, idx, h1, wqkv, bqkv):
-    """The self-attention of ``WanSelfAttention._attend_cached`` (model.py) for the training form of forward_chunk: the
-    same launches in the same order on the packed q | k | v weights — q‖k projection, RMSNorm + RoPE per sample with k
-    written into rows [length, length + C) of the layer's cache, the V^T product into the same columns, plain
-    short-kernel attention over the keys [lo, length + C) — with ``lse`` and ``o32`` asked for on top (the choice of the
-    kernel does not depend on them), so the output has the inference call's bits.  The chunk's own k rows and V (row-major,
-    what the backward reads) are copied out: the next denoising step and the commit pass overwrite them in the cache.
-    Returns (qk, q, k_own, v_own, o, lse, o32)."""
-    B, C, d, N, D = fc.B, fc.S, sa.dim, sa.num_heads, sa.head_dim
-    dev = h1.device
-    cache, lo = fc.cache, fc.cache_lo
-    kc, vtc = cache.k[idx], cache.vt[idx]
-    L0, cap, pitch = cache.length, cache.cap, cache.pitch
-    R, Lk = B * C, L0 + C - lo
-    bf = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
-    qk = bf(R, 2 * d)
-    ops.gemm_raw(ptr(h1), ptr(wqkv), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(bqkv), bias_mode=BIAS_N)
-    q = bf(R, d)
-    wq, wk = sa._norm_w("norm_q"), sa._norm_w("norm_k")
-    for b in range(B):                                     # one launch per sample: its k rows sit at their own place in the cache
-        ops.rmsnorm_rope_bf16_pair_raw(ptr(qk, b * C * 2 * d), 2 * d, d, ptr(q, b * C * d), ptr(kc, (b * cap + L0) * d), C, d,
-                                       ptr(wq) if wq is not None else None, ptr(wk) if wk is not None else None,
-                                       sa.eps, int(sa.qk_norm), ptr(fc.rope_cos), ptr(fc.rope_sin),
-                                       fc.rope_cos.shape[0], D, ptr(fc.grid32, 3 * b), C,
-                                       out_scale0=D ** -0.5 * LOG2E, out_scale1=1.0)
-    ops.gemm_raw(ptr(wqkv, 2 * d * d), ptr(h1), ptr(vtc, L0), d, C, d, d, d, pitch, EPI_BF16, bias=ptr(bqkv, 2 * d),
-                 bias_mode=BIAS_M, batch=B, strideA=0, strideB=C * d, strideC=d * pitch)
-    o = bf(R, d)
-    lse = torch.empty(B, N, C, dtype=torch.float32, device=dev)
-    o32 = torch.empty(R, d, dtype=torch.float32, device=dev)
-    ops.flash_attn_raw(ptr(q), ptr(kc, lo * d), ptr(vtc, lo), ptr(o), None, B, N, C, Lk, C * d, d, cap * d, d,
-                       d * pitch, C * d, d, pitch, D ** -0.5, lse=ptr(lse), q_prescaled=1, o32=ptr(o32),
-                       flags=ops.ATTN_SHORT_KERNEL)
-    k_own = kc[:, L0:L0 + C].clone()                       # [B, C, d]
-    v_own = bf(B, C, d)
-    ops.transpose_bf16_raw(ptr(vtc, L0), ptr(v_own), d, C, pitch, d, batch=B, bs_in=d * pitch, bs_out=C * d)
-    return qk, q, k_own.view(R, d), v_own.view(R, d), o, lse, o32
-
-
 def _cached_kv(S, idx, B, Sq, d):
     """K and V (row-major) of ALL keys a cached chunk saw, [B * Lk, d] each, and the number of cached rows in front of the
     chunk's own: the cached rows are read from the cache in place (copy / transpose of V^T), the own rows are the
@@ -745,7 +701,7 @@ def _cached_kv(S, idx, B, Sq, d):
 
 
 # ----------------------------------------------------------------------------- block forward (training)
-def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
+def _block_forward(model, blk, idx, st, x0, P, keep, need=True, mask=None):
     """The inference block (model.py:279-330 on libomh.so, WanAttentionBlock.forward of this package) with the
     residual stream out of place and the backward's extra tensors emitted by the producing epilogues.  x0 fp32
     [B, S, d] is left untouched.  Returns (x3, S) — S holds what ``_block_backward`` reads.  ``need = False`` (the
@@ -763,7 +719,7 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
         mod = mod.float()
     mod = mod.contiguous()
     e0 = fc.e0
-    rpb = getattr(fc, "rpb", None) or Sq                 # rows per row of e0: the sequence, or a frame (per-frame t)
+    rpb = fc.rpb or Sq                                   # rows per row of e0: the sequence, or a frame (per-frame t)
     six = 6 * d
     i2v = hasattr(ca, "k_img")
     n_img = 257 if i2v else 0
@@ -812,11 +768,13 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
     h1 = ln_mod(x0, 0, 1)
     wqkv, bqkv = P["wqkv"], P["bqkv"]
     f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-    if getattr(fc, "cache", None) is not None:              # WanModel.forward_chunk(grad=True): the launches of _attend_cached
+    if fc.cache is not None:                                # WanModel.forward_chunk(grad=True): _attend_cached's launches
         if not _ATTN_BWD2:
             raise NotImplementedError("OMH_ATTN_BWD=v1 has no cached backward: forward_chunk(grad=True) needs the default kernels")
-        qk, q, k, v_own, o, lse_sa, o32_sa = _cached_self_attention(sa, fc, idx, h1, wqkv, bqkv)
-        vt, bmask = None, None
+        fc.cache_layer = idx
+        o, qk, q, k, v_own, lse_sa, o32_sa = sa._attend_cached(h1, fc, ptr(wqkv), ptr(bqkv), ptr(wqkv, 2 * d * d),
+                                                                ptr(bqkv, 2 * d), extras=True)
+        vt = None
         S.update(v_own=v_own, cached=(fc.cache, fc.cache_lo, fc.cache.length, fc.cache.mark()))
     else:
         qk = bf(R, 2 * d)                                       # q | k projection, bf16 like the inference path
@@ -834,31 +792,17 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, bmask=None):
         o = bf(R, d)
         lse_sa = f32(B, N, Sq) if need else None
         o32_sa = f32(R, d) if (_ATTN_BWD2 and need) else None     # the output before its rounding: delta of the backward
-        win = tuple(sa.window_size)                             # the band (model.py:151-156): its backward needs o32
-        if need and not _ATTN_BWD2 and (win[0] >= 0 or win[1] >= 0):
-            raise NotImplementedError(f"OMH_ATTN_BWD=v1 has no band backward: window_size={win} needs the default kernels")
-        if bmask is None:                                       # (else: the checkpoint re-run, handed the forward's own mask)
-            bmask = sa._mask_for(Sq)                            # WanModel.set_attention_block_mask: the block-list kernels
-            if sa._block_policy is not None:                    # set_attention_block_policy: chosen from this call's q and k
-                bmask = sa._dynamic_mask(q, k, B, Sq, fc.seq_lens32)
-        if need and not _ATTN_BWD2 and bmask is not None:
-            raise NotImplementedError("OMH_ATTN_BWD=v1 has no block-mask backward: the mask needs the default kernels")
-        chunk = getattr(fc, "chunk", None)                      # WanModel.set_causal_chunks: the staircase kernels
-        if chunk is not None and (bmask is not None or win[0] >= 0 or win[1] >= 0):
-            raise ValueError("causal chunks exclude a block mask, a block policy and a bounded window_size")
-        if need and not _ATTN_BWD2 and chunk is not None:
-            raise NotImplementedError("OMH_ATTN_BWD=v1 has no chunk-causal backward: the mask needs the default kernels")
-        ivl = getattr(fc, "interval", None)                     # WanModel.forward_teacher_forcing: the interval-mask kernels
-        if ivl is not None and (bmask is not None or win[0] >= 0 or win[1] >= 0):
-            raise ValueError("teacher forcing excludes a block mask, a block policy and a bounded window_size")
-        if need and not _ATTN_BWD2 and ivl is not None:
-            raise NotImplementedError("OMH_ATTN_BWD=v1 has no interval-mask backward: the mask needs the default kernels")
+        if mask is None:                                        # (else: the checkpoint re-run, handed the forward's own mask)
+            mask = sa._call_mask(fc, dev)                       # band, block mask, staircase or interval mask — or a block
+            if mask is None:                                    # policy, which chooses from this call's q and k
+                mask = sa._call_mask(fc, dev, sa._dynamic_mask(q, k, B, Sq, fc.seq_lens32))
+        if need and not _ATTN_BWD2 and mask.kind != "full":     # (their backwards need o32)
+            raise NotImplementedError(f"OMH_ATTN_BWD=v1 has no {mask.kind} backward: the default kernels are needed")
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, Sq, Sq, Sq * d, d, Sq * d, d, d * Sp,
                            Sq * d, d, Sp, D ** -0.5, lse=ptr(lse_sa) if need else None, q_prescaled=1,
-                           o32=ptr(o32_sa) if o32_sa is not None else None, flags=_ATTN_FLAGS, window=win, block_mask=bmask,
-                           chunk_causal=chunk, interval_mask=ivl)
+                           o32=ptr(o32_sa) if o32_sa is not None else None, flags=_ATTN_FLAGS, mask=mask)
     x1, y1 = resid(x0, o, P["wo"], sa.o.bias.detach(), 2, True)
-    S.update(h1=h1, qk=qk, q=q, k=k, vt=vt, o=o, lse_sa=lse_sa, y1=y1, x1=x1, o32_sa=o32_sa, bmask=bmask)
+    S.update(h1=h1, qk=qk, q=q, k=k, vt=vt, o=o, lse_sa=lse_sa, y1=y1, x1=x1, o32_sa=o32_sa, mask=mask)
     # ---- cross-attention: x2 = x1 + o(attn(norm3(x1), context))                                     model.py:313
     h3 = bf(R, d)
     if blk.cross_attn_norm:
@@ -921,7 +865,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     eps = blk.eps
     mod = blk.modulation.detach().float().contiguous()
     e0 = fc.e0
-    rpb = getattr(fc, "rpb", None) or Sq                 # rows per row of e0: the sequence, or a frame (per-frame t)
+    rpb = fc.rpb or Sq                                   # rows per row of e0: the sequence, or a frame (per-frame t)
     six = 6 * d
     i2v = hasattr(ca, "k_img")
     n_img = 257 if i2v else 0
@@ -1181,8 +1125,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     else:
         v = ops.transpose_bf16_batched(S["vt"], Sq)                   # [B*S, d]
         _attn_bwd(q, k, v, o, do, S["lse_sa"], fc.seq_lens32, B, N, Sq, Sq, D ** -0.5,
-                  (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, tuple(sa.window_size), S["bmask"],
-                  getattr(fc, "chunk", None), getattr(fc, "interval", None))
+                  (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, S["mask"])
     qk = S["qk"]
     rms_bwd(ptr(qk), True, 2 * d, ptr(dqkv), 3 * d, R, [sa._norm_w("norm_q"), sa._norm_w("norm_k")], sa.qk_norm, True,
             ["self_attn.norm_q.weight", "self_attn.norm_k.weight"], sa, n_seg=2, seg_x=d, seg_dy=d)   # q and k: one launch
@@ -1282,7 +1225,7 @@ class _BlockFn(torch.autograd.Function):
             out, S = _block_forward(model, blk, idx, st, x0, st.packs[idx], keep, need=keep)
         ctx.model, ctx.st, ctx.idx = model, st, idx
         ctx.kept = S if keep else None
-        ctx.bmask = S["bmask"]                               # the backward (and its re-run of the block) uses this mask
+        ctx.mask = S["mask"]                                 # the backward (and its re-run of the block) uses this mask
         ctx.save_for_backward(x0)
         return out
 
@@ -1305,7 +1248,7 @@ class _BlockFn(torch.autograd.Function):
                 raise RuntimeError("forward_chunk(grad=True): the backward of a chunk runs once (its kept activations are "
                                    "released; the block cannot be re-run against the cache as it is now)")
             if S is None:                                    # use_checkpoint: re-run the forward's kernels on its input
-                _, S = _block_forward(model, blk, idx, st, x0, P, False, bmask=ctx.bmask)
+                _, S = _block_forward(model, blk, idx, st, x0, P, False, mask=ctx.mask)
             # The block backward updates the incoming gradient IN PLACE.  That is only legal when the buffer belongs to
             # this node: autograd hands a node the producer's own tensor when the block output has ONE consumer (the next
             # block / the head allocate a fresh dx), but a caller that also taps block outputs (the reference's
@@ -1380,7 +1323,7 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model, st, grids, *params):
         with torch.no_grad():
-            out = model.head(x.detach(), st.e, getattr(st.fc, "rpb", None))
+            out = model.head(x.detach(), st.e, st.fc.rpb)
             outs = model.unpatchify(out, None, _grids=grids)
         ctx.save_for_backward(x.detach())
         ctx.model, ctx.st, ctx.grids = model, st, grids
@@ -1406,7 +1349,7 @@ class _HeadFn(torch.autograd.Function):
                 n = grd[0] * grd[1] * grd[2]
                 dtok[b * S:b * S + n].copy_(ops.unpatchify_bwd(gb.contiguous().float(), grd, model.patch_size))
             hh = torch.empty(R, d, dtype=torch.bfloat16, device=dev)
-            rpb, nE = getattr(st.fc, "rpb", None) or S, e.shape[0]  # rows per row of e (a frame with a per-frame t)
+            rpb, nE = st.fc.rpb or S, e.shape[0]  # rows per row of e (a frame with a per-frame t)
             ops.layernorm_modulate_raw(ptr(x), ptr(hh), R, d, head.eps, 1.0, ptr(mod, d), ptr(e), d, ptr(mod, 0),
                                        ptr(e), d, rpb)
             w, _ = head._packed.get("head", (head.head.weight, head.head.bias), lambda: (
@@ -1749,9 +1692,10 @@ def check_chunk_grad_policy(model):
 
 def forward_chunk_train(model, x, t, context, cache, frame_offset, commit, clip_fea=None, y=None):
     """WanModel.forward_chunk with autograd enabled (``grad=True``): embed node -> blocks -> head node as ``forward_train``,
-    each block's self-attention against the cache (_cached_self_attention).  Several of these graphs may await one
-    ``backward()`` (a rollout): each has its own state and kept tensors, they are registered as live forwards of the model,
-    so the weight-gradient stream joins per block and autograd sums their parameter gradients (see _BlockFn.backward)."""
+    each block's self-attention against the cache (WanSelfAttention._attend_cached with its extras).  Several of these
+    graphs may await one ``backward()`` (a rollout): each has its own state and kept tensors, they are registered as live
+    forwards of the model, so the weight-gradient stream joins per block and autograd sums their parameter gradients (see
+    _BlockFn.backward)."""
     C, lo, frame_offset = model._chunk_geometry(x, t, cache, frame_offset)
     st = _State()
     for key in [k for k in _join_pending if k[1] == id(model)]:   # a backward pass that died before its end-of-pass join
@@ -1760,13 +1704,7 @@ def forward_chunk_train(model, x, t, context, cache, frame_offset, commit, clip_
     st.packs = TrainPacks.of(model).refresh(model)
     model.__dict__.setdefault("_omh_live_states", weakref.WeakSet()).add(st)
 
-    def after_embed(fc):
-        fc.chunk = None                                    # the cache IS the causal structure: plain attention over it
-        fc.interval = None
-        fc.rope_cos, fc.rope_sin = model._rope_shifted(fc.e0.device, frame_offset)
-        fc.cache, fc.cache_lo = cache, lo
-        fc.cache_pos = fc.cache_hi = fc.cache_mask = None
-    st.after_embed = after_embed
+    st.after_embed = lambda fc: model._chunk_ctx(fc, cache, lo, frame_offset)
     named = _embed_params(model)
     (fx, nx), (fy, ny), (fctx, nc) = _flatten_input(x), _flatten_input(y), _flatten_input(context)
     st.need_ctx = any(p.requires_grad for n, p in named if n.startswith(("text_embedding.", "img_emb."))) or \

@@ -159,13 +159,14 @@ def test_sparse_entries_validate_without_gpu(omh):
 def test_python_refusals_without_gpu(omh, sparse):
     ops = importlib.import_module(PKG + ".ops")
     attn = importlib.import_module(PKG + ".wan.modules.attention")
+    cpu = torch.device("cpu")
     with pytest.raises(ValueError):
-        ops._block_mask(torch.ones(2, 2, dtype=torch.bool), 2, 256, 256, window=(16, 16))
+        ops.attn_mask((16, 16), torch.ones(2, 2, dtype=torch.bool), H=2, Lq=256, Lk=256, device=cpu)
     with pytest.raises(ValueError):
-        ops._block_mask(torch.ones(3, 2, 2, dtype=torch.bool), 2, 256, 256)
+        ops.attn_mask(block_mask=torch.ones(3, 2, 2, dtype=torch.bool), H=2, Lq=256, Lk=256, device=cpu)
     with pytest.raises(ValueError):
-        ops._block_mask(sparse.BlockMask(torch.ones(2, 2, dtype=torch.bool), 256, 256), 2, 256, 400)
-    assert ops._block_mask(None, 2, 256, 256, window=(16, 16)) is None
+        ops.attn_mask(block_mask=sparse.BlockMask(torch.ones(2, 2, dtype=torch.bool), 256, 256), H=2, Lq=256, Lk=400, device=cpu)
+    assert ops.attn_mask((16, 16), None, H=2, Lq=256, Lk=256, device=cpu).kind == "band"
     import inspect
     for fn in (attn.flash_attention, attn.attention):                            # a trailing keyword after the reference's own
         assert list(inspect.signature(fn).parameters)[-1] == "block_mask"
@@ -212,10 +213,14 @@ def test_model_mask_refusals(wan_model_mod, sparse):
     # the wrong nb is found at forward; without a GPU the layer's own check is what can be reached
     m.set_attention_block_mask(mask)
     sa = m.blocks[0].self_attn
-    assert sa._mask_for(320) is sa._block_mask and sa._mask_for(384) is sa._block_mask
+    def mask_for(S):
+        fc = wan_model_mod._FwdCtx()
+        fc.S = S
+        return sa._call_mask(fc, torch.device("cpu")).rule
+    assert mask_for(320) is sa._block_mask and mask_for(384) is sa._block_mask
     for S in (256, 385, 1560):
         with pytest.raises(ValueError):
-            sa._mask_for(S)
+            mask_for(S)
     ops = importlib.import_module(PKG + ".ops")
     if not torch.cuda.is_available():
         with pytest.raises(ops.OmhError):                                        # the existing "MI355X only" error comes first

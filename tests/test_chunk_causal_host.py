@@ -121,17 +121,18 @@ def test_chunk_entries_validate_without_gpu(omh):
 def test_python_refusals_without_gpu(omh):
     ops = importlib.import_module(PKG + ".ops")
     attn = importlib.import_module(PKG + ".wan.modules.attention")
-    assert ops._chunk_causal(None, window=(16, 16)) is None
-    cc = ops._chunk_causal((1560, -3, 8))
+    at = dict(H=2, Lq=256, Lk=256, device=torch.device("cpu"))
+    assert ops.attn_mask((16, 16), chunk_causal=None, **at).kind == "band"
+    cc = ops.attn_mask(chunk_causal=(1560, -3, 8), **at).rule
     assert (cc.chunk, cc.left_chunks, cc.q_offset, cc.reserved) == (1560, -1, 8, 0)
     with pytest.raises(ValueError):
-        ops._chunk_causal((64, -1, 0), window=(16, -1))
+        ops.attn_mask((16, -1), chunk_causal=(64, -1, 0), **at)
     with pytest.raises(ValueError):
-        ops._chunk_causal((64, -1, 0), block_mask=torch.ones(2, 2, dtype=torch.bool))
+        ops.attn_mask(chunk_causal=(64, -1, 0), block_mask=torch.ones(2, 2, dtype=torch.bool), **at)
     with pytest.raises(ValueError):
-        ops._chunk_causal((0, -1, 0))
+        ops.attn_mask(chunk_causal=(0, -1, 0), **at)
     with pytest.raises(ValueError):
-        ops._chunk_causal((64, -1, -1))
+        ops.attn_mask(chunk_causal=(64, -1, -1), **at)
     # the wrapper raises before it asks for a device
     q = torch.zeros(1, 256, 2, 128)
     mask = torch.ones(2, 2, dtype=torch.bool)

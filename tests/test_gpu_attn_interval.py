@@ -282,6 +282,6 @@ def test_interval_mask_refuses_other_masks(ops, causal, attn_mod):
         attn_mod.flash_attention(q, q, q, interval_mask=m.vis)
     host = causal.IntervalMask(causal.teacher_forcing_groups(2), 64)             # tables on the CPU: moved beside q
     assert torch.equal(ops.flash_attn(q, q, _vt(q), interval_mask=host), ops.flash_attn(q, q, _vt(q), interval_mask=m))
-    assert ops._interval_mask(host, 256, 256, device=q.device).q_iv.device == q.device
+    assert ops.attn_mask(interval_mask=host, H=q.shape[2], Lq=256, Lk=256, device=q.device).rule.q_iv.device == q.device
     with pytest.raises(ValueError):                                              # 4 x 4 groups of 64 do not cover 256 x 320
         ops.flash_attn(q, torch.cat([q, q[:, :64]], 1), _vt(torch.cat([q, q[:, :64]], 1)), interval_mask=m)

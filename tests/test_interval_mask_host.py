@@ -229,20 +229,21 @@ def test_python_refusals_without_gpu(omh, causal):
     attn = importlib.import_module(PKG + ".wan.modules.attention")
     m = causal.IntervalMask(causal.teacher_forcing_groups(2), 64)
     blocks = torch.ones(2, 2, dtype=torch.bool)
-    assert ops._interval_mask(None, 256, 256, window=(16, 16)) is None
+    at = dict(H=2, Lq=256, Lk=256, device=torch.device("cpu"))
+    assert ops.attn_mask((16, 16), interval_mask=None, **at).kind == "band"
     with pytest.raises(ValueError):
-        ops._interval_mask(m, 256, 256, window=(16, -1))
+        ops.attn_mask((16, -1), interval_mask=m, **at)
     with pytest.raises(ValueError):
-        ops._interval_mask(m, 256, 256, window=(-1, 0))
+        ops.attn_mask((-1, 0), interval_mask=m, **at)
     with pytest.raises(ValueError):
-        ops._interval_mask(m, 256, 256, block_mask=blocks)
+        ops.attn_mask(interval_mask=m, block_mask=blocks, **at)
     with pytest.raises(ValueError):
-        ops._interval_mask(m, 256, 256, chunk_causal=(64, -1, 0))
+        ops.attn_mask(interval_mask=m, chunk_causal=(64, -1, 0), **at)
     with pytest.raises(ValueError):
-        ops._interval_mask(m, 320, 256)                                          # 5 x 4 groups expected
+        ops.attn_mask(interval_mask=m, **dict(at, Lq=320))                       # 5 x 4 groups expected
     with pytest.raises(ValueError):
-        ops._interval_mask(m.vis, 256, 256)                                      # the bare matrix carries no group size
-    assert ops._interval_mask(m, 256, 256, device=torch.device("cpu")) is m       # already there: the same object
+        ops.attn_mask(interval_mask=m.vis, **at)                                 # the bare matrix carries no group size
+    assert ops.attn_mask(interval_mask=m, **at).rule is m                        # already there: the same object
     q_iv, k_iv = m.intervals()                                                   # the tables, as lists
     assert q_iv == [[0, 1, 1, 1], [0, 2, 2, 2], [2, 3, 3, 3], [0, 1, 3, 4]]
     assert k_iv == [[0, 2, 3, 4], [1, 2, 2, 2], [2, 3, 3, 3], [3, 4, 4, 4]]
