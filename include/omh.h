@@ -639,6 +639,41 @@ int omh_cfg_unipc_step(const float* cond, const float* uncond, const float* x, c
 int omh_flow_x0_step(const float* v, const float* x, const float* eps, const float* sigma, const float* sigma_next,
                      float* x0, float* x_next, int32_t B, int64_t n, int32_t backward, omh_stream_t stream);
 
+/* Additive to ABI v12 (OMH_ABI_VERSION unchanged, no existing struct or entry changed): the distribution-matching (DMD)
+ * objective a self-forcing rollout is trained with (causal.dmd_loss), DMD2 / Self-Forcing form in the flow
+ * parameterisation.  It replaces the chain of torch ops the published trainers write between the score models' calls
+ * (x0 estimates, their difference, abs().mean(), division, nan_to_num, 0.5 * mse_loss: about 12 launches with two
+ * reductions whose order the library chooses) by four launches whose reductions have a fixed order, so that a training
+ * step stays bit-repeatable under omh_set_deterministic(1).  All tensors fp32 [B, n] contiguous, any n >= 1, any 4-byte
+ * aligned pointers; sigma is a DEVICE array [B] in (0, 1) (no host synchronisation).  Per sample b:
+ *   v_real = v_uncond + guide * (v_cond - v_uncond)          (v_uncond == NULL: v_real = v_cond; guide is not read)
+ *   p_real = (x - xt) + sigma[b] * v_real                     (= x - x0_real, with xt = (1 - sigma) x + sigma eps)
+ *   n_b    = mean over the sample of |p_real|                 -> norm[b], accumulated in fp64, rounded once to fp32
+ *   grad   = nan_to_num(sigma[b] * (v_real - v_fake) / n_b)   -> grad   (NaN -> 0, +-inf -> +-FLT_MAX)
+ *   loss   = 0.5 * mean over all B * n elements of grad^2     -> loss[0], fp64: the squares of the fp32 values AS STORED,
+ *            accumulated in fp64;  d loss / d x = grad / (B n), which is what omh_dmd_grad_scale forms.
+ * Every fp32 product, sum and the division is rounded on its own.  A sample is cut into chunks of OMH_DMD_CHUNK elements
+ * that never straddle two samples; one workgroup handles one chunk and writes one fp64 partial per reduction into
+ * `workspace` (DEVICE, 8-byte aligned, omh_dmd_grad_workspace_bytes(B, n) = B * ceil(n / OMH_DMD_CHUNK) *
+ * OMH_DMD_PARTIAL_BYTES bytes, pure host arithmetic, overwritten); the partials are added in a fixed order.  Which thread
+ * adds which element depends on the element's index in its sample alone (16-byte aligned samples are read as float4,
+ * others element by element, in the same order): sample b of a batch has the bits it has alone.  No atomics, no
+ * dependence on the order in which workgroups run, four launches on `stream`, no allocation, nothing read back.
+ * Returns -1 for a NULL pointer (all but v_uncond are required), -2 for B < 1 or n < 1 and for a misaligned pointer
+ * (loss and workspace: 8 bytes), OMH_E_SHAPE for more than 2^23 chunks — before the device is touched. */
+#define OMH_DMD_CHUNK 16384
+#define OMH_DMD_PARTIAL_BYTES 16
+int omh_dmd_grad(const float* x, const float* xt, const float* v_cond, const float* v_uncond, const float* v_fake,
+                 const float* sigma, float guide, int32_t B, int64_t n, float* grad, float* norm, double* loss,
+                 void* workspace, omh_stream_t stream);
+int64_t omh_dmd_grad_workspace_bytes(int32_t B, int64_t n);
+/* The backward of that loss (replaces the autograd nodes of 0.5 * mse_loss(x, (x - grad).detach())): dx = grad * c over
+ * `total` = B * n elements, c = float(*upstream) * inv_total in fp32; upstream is the DEVICE fp64 scalar autograd hands to
+ * the loss, inv_total = float(1 / (B n)).  One fp32 multiply per element; dx may alias grad.  -1 for a NULL pointer, -2
+ * for total < 1 or a misaligned pointer (upstream: 8 bytes). */
+int omh_dmd_grad_scale(const float* grad, const double* upstream, float inv_total, int64_t total, float* dx,
+                       omh_stream_t stream);
+
 /* ----------------------------------------------------------------------
  * ABI v11.  Measurement, not product: TFLOP/s this GPU sustains on back-to-back
  * v_mfma_f32_32x32x16_bf16 with one wave per SIMD and no memory traffic

@@ -315,6 +315,9 @@ _SIGS = {
     "omh_cfg_unipc_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, i32, f32, f32, f32, f32, f32,
                                  f32, f32, vp]),
     "omh_flow_x0_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
+    "omh_dmd_grad": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i64, vp, vp, vp, vp, vp]),
+    "omh_dmd_grad_workspace_bytes": (i64, [i32, i64]),
+    "omh_dmd_grad_scale": (i32, [vp, vp, f32, i64, vp, vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

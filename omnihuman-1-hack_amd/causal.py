@@ -18,6 +18,11 @@ says which key groups a query group sees.  ``IntervalMask`` holds such a matrix 
 
 An attention sink plus a window (``WanModel.set_causal_chunks(fpc, W, S)``) rolls out on a ``RollingKVCache``: S sink slots
 and a ring of W + 1, so the cache's size does not depend on the clip's length.
+
+Self forcing trains the student on its own rollouts: ``self_forcing_rollout`` returns clips attached to a graph,
+``dmd_loss`` puts the distribution-matching objective on them (a frozen teacher and a trainable critic score the noised
+clips; include/omh.h, ``omh_dmd_grad``), ``critic_loss`` is the critic's own flow-matching loss on the same generated
+clips and ``dmd_sigmas`` draws the noise levels of both.
 """
 import ctypes
 
@@ -25,7 +30,7 @@ import torch
 
 __all__ = ["chunk_causal_visible", "KVCache", "RollingKVCache", "sample", "IntervalMask", "interval_visible",
            "teacher_forcing_groups",
-           "sink_window_groups", "forcing_loss", "self_forcing_rollout"]
+           "sink_window_groups", "forcing_loss", "self_forcing_rollout", "dmd_sigmas", "dmd_loss", "critic_loss"]
 
 
 def chunk_causal_visible(Lq, Lk, chunk, left_chunks=-1, q_offset=0, qlen=None, klen=None):
@@ -482,3 +487,134 @@ def self_forcing_rollout(model, noise, context, *, frames_per_chunk, left_chunks
         return list(clip.unbind(0))
     finally:
         model._causal_chunks = prev
+
+
+def dmd_sigmas(B, generator=None, lo=0.02, hi=0.98, shift=5.0, device=None):
+    """One noise level per clip for ``dmd_loss`` / ``critic_loss``: u uniform in [``lo``, ``hi``] (``torch.rand`` with
+    ``generator``), sigma = shift u / (1 + (shift - 1) u) — the timestep shift of the flow schedules — and timesteps =
+    1000 sigma.  Returns (sigma [B], timesteps [B]), fp32 on ``device`` (default: the generator's device, else "cuda");
+    nothing is read back to the host."""
+    B, lo, hi, shift = int(B), float(lo), float(hi), float(shift)
+    if B < 1:
+        raise ValueError(f"dmd_sigmas: B = {B} >= 1 expected")
+    if not 0.0 < lo <= hi < 1.0:
+        raise ValueError(f"dmd_sigmas: 0 < lo <= hi < 1 expected, got lo = {lo}, hi = {hi}")
+    if shift <= 0.0:
+        raise ValueError(f"dmd_sigmas: shift = {shift} > 0 expected")
+    if device is None:
+        device = generator.device if generator is not None else "cuda"
+    u = lo + (hi - lo) * torch.rand(B, dtype=torch.float32, device=device, generator=generator)
+    sigma = shift * u / (1.0 + (shift - 1.0) * u)
+    return sigma, 1000.0 * sigma
+
+
+def _score_inputs(who, clips, sigma, timesteps, eps):
+    """The shared argument rules of ``dmd_loss`` and ``critic_loss`` (shapes only: nothing touches a device).  Returns the
+    clips as a list and B."""
+    clips = list(clips)
+    if not clips or any(not isinstance(c, torch.Tensor) or c.dim() != 4 for c in clips) or \
+            len({tuple(c.shape) for c in clips}) != 1:
+        raise ValueError(f"{who}: clips is a list of tensors [C, F, H, W] of one shape")
+    B = len(clips)
+    for name, v in (("sigma", sigma), ("timesteps", timesteps)):
+        if not isinstance(v, torch.Tensor) or tuple(v.shape) != (B,):
+            raise ValueError(f"{who}: {name} of shape [{B}] expected (one level per clip), got "
+                             f"{tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+    if eps is not None and tuple(eps.shape) != (B,) + tuple(clips[0].shape):
+        raise ValueError(f"{who}: eps of shape {[B] + list(clips[0].shape)} expected, got {list(eps.shape)}")
+    return clips, B
+
+
+def _awaits_backward(model):
+    return any(not o.__dict__.get("bwd_done", False) for o in model.__dict__.get("_omh_live_states", ()))
+
+
+def _noised(clips, sigma, eps, generator):
+    """(x [B, C, F, H, W] fp32 stacked, attached as the clips are; eps; x_t = ops.flow_noise(x, eps, sigma), graph-free;
+    sigma fp32 on x's device)."""
+    from . import ops
+    x = torch.stack(clips).float().contiguous()
+    sigma = sigma.detach().to(device=x.device, dtype=torch.float32).contiguous()
+    with torch.no_grad():
+        if eps is None:
+            eps = torch.randn(x.shape, dtype=torch.float32, device=x.device, generator=generator)
+        eps = eps.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        x_t = ops.flow_noise(x, eps, sigma)
+    return x, eps, x_t, sigma
+
+
+def _seq_len(model, clip):
+    pt, ph, pw = model.patch_size
+    return (clip.shape[1] // pt) * (clip.shape[2] // ph) * (clip.shape[3] // pw)
+
+
+def dmd_loss(clips, teacher, critic, context, context_null=None, *, sigma, timesteps, guide_scale=3.0, eps=None,
+             generator=None):
+    """The distribution-matching (DMD) loss of a self-forcing generator step, DMD2 / Self-Forcing form in the flow
+    parameterisation.  ``clips``: the list ``self_forcing_rollout`` returns — B clips fp32 [C, F, H, W] of one shape,
+    attached to the student's graph; ``teacher``: a frozen bidirectional ``WanModel``; ``critic``: the trainable one that
+    tracks the student's distribution; ``context`` / ``context_null``: what ``WanModel.forward`` takes for B clips;
+    ``sigma`` / ``timesteps``: [B] (``dmd_sigmas``); ``eps``: the noise [B, C, F, H, W] (default: ``torch.randn`` with
+    ``generator``).  With x the stacked clips:
+
+        x_t    = (1 - sigma_b) x + sigma_b eps                    ``ops.flow_noise``, under ``no_grad``
+        v_real = v_u + guide_scale (v_c - v_u)                    ``teacher.forward_cfg_pair(x_t, t, context, context_null,
+                                                                  seq_len)``; without ``context_null`` v_real =
+                                                                  ``teacher.forward(x_t, t, context, seq_len)``
+        v_fake = ``critic.forward(x_t, t, context, seq_len)``
+        n_b    = mean over the clip of |(x - x_t) + sigma_b v_real|
+        grad   = nan_to_num(sigma_b (v_real - v_fake) / n_b)
+        loss   = 0.5 * mean(grad^2),   d loss / d x = grad / x.numel()        ``ops.dmd_loss``
+
+    Both score models run under ``no_grad``: nothing flows into them, the critic's training flag and the teacher's
+    ``set_causal_chunks`` setting are left alone (the teacher is the caller's object, and bidirectional as the caller
+    made it).  Returns the fp64 scalar loss, attached to ``clips``.
+
+    ValueError: clips of different shapes, a ``sigma`` or ``timesteps`` that is not [B], an ``eps`` of another shape.
+    RuntimeError: a ``teacher`` or ``critic`` with forwards that still await their ``backward()`` — the student itself:
+    its causal setting and its set of live forwards would be disturbed; pass separate models.
+
+    One training iteration, the optimisers and their alternation being the caller's:
+
+        # generator step
+        clips = causal.self_forcing_rollout(student, noise, context, frames_per_chunk=3, sigmas=..., timesteps=...,
+                                            exit_step=...)
+        sigma, t = causal.dmd_sigmas(len(clips))
+        causal.dmd_loss(clips, teacher, critic, context, context_null, sigma=sigma, timesteps=t).backward()
+        # critic step
+        with torch.no_grad():
+            clips = causal.self_forcing_rollout(student, noise, context, ...)
+        sigma, t = causal.dmd_sigmas(len(clips))
+        causal.critic_loss(critic, clips, context, sigma=sigma, timesteps=t).backward()"""
+    from . import ops
+    clips, B = _score_inputs("dmd_loss", clips, sigma, timesteps, eps)
+    for name, m in (("teacher", teacher), ("critic", critic)):
+        if _awaits_backward(m):
+            raise RuntimeError(f"dmd_loss: {name} has forwards that await their backward() — the student itself?  Its causal "
+                               f"setting and its live forwards would be disturbed: pass a separate model")
+    x, eps, x_t, sigma = _noised(clips, sigma, eps, generator)
+    seq_len = _seq_len(teacher, clips[0])
+    with torch.no_grad():
+        t = timesteps.detach().to(device=x.device, dtype=torch.float32)
+        xs = list(x_t.unbind(0))
+        if context_null is not None:
+            v_c, v_u = teacher.forward_cfg_pair(xs, t, context, context_null, seq_len)
+            v_c, v_u = torch.stack(v_c).float().contiguous(), torch.stack(v_u).float().contiguous()
+        else:
+            v_c, v_u = torch.stack(teacher.forward(xs, t, context, seq_len)).float().contiguous(), None
+        v_f = torch.stack(critic.forward(xs, t, context, seq_len)).float().contiguous()
+    return ops.dmd_loss(x, x_t, v_c, v_u, v_f, sigma, guide_scale)
+
+
+def critic_loss(critic, clips, context, *, sigma, timesteps, eps=None, generator=None):
+    """The critic's flow-matching loss on generated clips (the critic step of DMD): the clips are DETACHED (their graph,
+    if they have one, is neither read nor written), x_t = ``ops.flow_noise(x, eps, sigma)`` with ``eps`` given or drawn
+    by ``torch.randn(generator=)``, ``critic.forward(x_t, timesteps, context, seq_len)`` on the training path, and the mean
+    squared error against eps - x in plain torch on the model's outputs, as ``forcing_loss`` has it.  ``sigma`` /
+    ``timesteps``: [B] (ValueError otherwise, as for clips of different shapes).  Gradients reach the critic alone."""
+    clips, B = _score_inputs("critic_loss", clips, sigma, timesteps, eps)
+    x, eps, x_t, sigma = _noised([c.detach() for c in clips], sigma, eps, generator)
+    t = timesteps.detach().to(device=x.device, dtype=torch.float32)
+    out = critic.forward(list(x_t.unbind(0)), t, context, _seq_len(critic, clips[0]))
+    target = eps - x
+    return torch.stack([(o.float() - v.to(o.device).float()).square().mean() for o, v in zip(out, target)]).mean()

@@ -14,7 +14,7 @@ from ._lib import (ATTN_ALLOW_SPLIT, ATTN_SHORT_KERNEL, BIAS_M, BIAS_N, BIAS_NON
                    EPI_GELU_BWD_BF16, EPI_GELU_ERF_BF16, EPI_RESID, AttnArgs, GemmArgs, OmhError, check, lib)
 
 __all__ = ["gemm", "flash_attn", "flash_attn_func", "layernorm_modulate", "rmsnorm_rope", "cast_bf16", "patchify", "unpatchify",
-           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw",
+           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "flow_noise", "dmd_grad", "dmd_loss", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw",
            "softmax_rows", "OmhError",
            "EPI_BF16", "EPI_F32", "EPI_GELU_BF16", "EPI_GELU_ERF_BF16", "EPI_RESID", "EPI_F32_ACCUM", "BIAS_NONE", "BIAS_N", "BIAS_M"]
 
@@ -689,6 +689,84 @@ class _FlowX0Func(torch.autograd.Function):
     def backward(ctx, g):
         (sigma,) = ctx.saved_tensors
         return _flow_x0_raw(g.contiguous().float(), None, sigma, backward=True)[0], None, None
+
+
+def flow_noise(x, eps, sigma):
+    """x_t = (1 - sigma_b) x + sigma_b eps for fp32 ``x``, ``eps`` of one shape [B, ...] and ``sigma`` fp32 [B] on the
+    device: the forward noising of the flow parameterisation, each product and the sum rounded on its own.  No kernel of
+    its own: omh_flow_x0_step with v = x, sigma = 0 and sigma_next = ``sigma`` computes x0 = x - 0 * x, which is x for every
+    finite x, and then exactly this expression; the x0 output is discarded.  The result carries no graph."""
+    with torch.no_grad():
+        x = x.detach()
+        return _flow_x0_raw(x, x, torch.zeros_like(sigma), eps.detach(), sigma.detach())[1]
+
+
+DMD_CHUNK = 16384                                               # OMH_DMD_CHUNK (include/omh.h)
+
+
+def dmd_grad_workspace_bytes(B, n):
+    """Bytes of omh_dmd_grad's workspace for B samples of n elements (host arithmetic)."""
+    return int(lib.omh_dmd_grad_workspace_bytes(int(B), int(n)))
+
+
+def dmd_grad(x, x_t, v_cond, v_uncond, v_fake, sigma, guide):
+    """The DMD score-difference gradient (omh_dmd_grad; DMD2 / Self-Forcing form, flow parameterisation): fp32 contiguous
+    tensors of one shape [B, ...] — the generated clips ``x``, their noised version ``x_t``, the teacher's velocities
+    ``v_cond`` / ``v_uncond`` (None: no guidance, v_real = v_cond) and the critic's ``v_fake`` — and ``sigma`` fp32 [B] on
+    the device.  With v_real = v_uncond + guide (v_cond - v_uncond) and n_b = mean |(x - x_t) + sigma_b v_real| per sample:
+
+        grad = nan_to_num(sigma_b (v_real - v_fake) / n_b),    loss = 0.5 * mean(grad^2) over all elements.
+
+    Returns (grad fp32 like x, norm fp32 [B] = n_b, loss fp64 [1]) — raw tensors without a graph.  Fixed-order fp64
+    reductions: the bits repeat, and sample b of a batch has the bits it has alone.  Nothing is read back to the host."""
+    _dev(x, x_t, v_cond, v_uncond, v_fake, sigma)
+    B = sigma.numel()
+    for t in (x, x_t, v_cond, v_uncond, v_fake):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape, \
+                "dmd_grad: contiguous fp32 tensors of one shape are expected"
+    assert x.numel() > 0 and x.numel() % B == 0 and (x.dim() == 1 or x.shape[0] == B), "dmd_grad: x [B, ...], sigma [B]"
+    assert sigma.dtype == torch.float32 and sigma.is_contiguous()
+    n = x.numel() // B
+    with torch.no_grad():
+        grad = torch.empty_like(x)
+        norm = torch.empty(B, dtype=torch.float32, device=x.device)
+        loss = torch.empty(1, dtype=torch.float64, device=x.device)
+        ws = torch.empty(dmd_grad_workspace_bytes(B, n) // 8, dtype=torch.float64, device=x.device)
+        check(lib.omh_dmd_grad(_p(x), _p(x_t), _p(v_cond), _p(v_uncond), _p(v_fake), _p(sigma), float(guide), B, n, _p(grad),
+                               _p(norm), _p(loss), _p(ws), _stream()), "omh_dmd_grad")
+    return grad, norm, loss
+
+
+class _DmdLossFunc(torch.autograd.Function):
+    """loss = 0.5 mean(grad^2) with d loss / d x = grad / N and no gradient to anything else (``dmd_loss``)."""
+
+    @staticmethod
+    def forward(ctx, x, x_t, v_cond, v_uncond, v_fake, sigma, guide):
+        grad, _, loss = dmd_grad(x.detach(), x_t, v_cond, v_uncond, v_fake, sigma, guide)
+        ctx.save_for_backward(grad)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        up = g.detach().to(device=grad.device, dtype=torch.float64).reshape(1).contiguous()
+        total = grad.numel()
+        inv = float(torch.tensor(1.0 / total, dtype=torch.float32))       # float32(1 / N): rounded once, on the host
+        dx = torch.empty_like(grad)
+        check(lib.omh_dmd_grad_scale(_p(grad), _p(up), inv, total, _p(dx), _stream()), "omh_dmd_grad_scale")
+        return dx, None, None, None, None, None, None
+
+
+def dmd_loss(x, x_t, v_cond, v_uncond, v_fake, sigma, guide):
+    """``dmd_grad`` as a loss: returns the fp64 scalar loss = 0.5 * mean(grad^2) — the value of
+    0.5 * mse_loss(x, (x - grad).detach()) — attached to ``x`` alone.  Its backward is d x = grad * c, one fp32 multiply per
+    element (omh_dmd_grad_scale), c = float32(upstream) * float32(1 / N) with the upstream scalar read on the device and
+    N = x.numel().  ``x_t``, the velocities and ``sigma`` are constants: they get no gradient."""
+    args = (x_t.detach(), v_cond.detach(), None if v_uncond is None else v_uncond.detach(), v_fake.detach(), sigma.detach())
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _DmdLossFunc.apply(x, *args, float(guide))
+    return dmd_grad(x.detach(), *args, guide)[2].view(())
 
 
 def conv_pair_supported(Tin, Hin, Win, Cin2, Tout, Hout, Wout, Cout, KT, KH, KW, stride_t=1, stride_hw=1, pad_h=0, pad_w=0,
