@@ -437,6 +437,31 @@ int omh_flash_attn_bwd_interval3_d128(const omh_attn_bwd_args* args, const int32
 int omh_interval_mask_tables3(const uint8_t* vis, int32_t q_groups, int32_t k_groups, int32_t* q_iv, int32_t* k_iv);
 
 /* ------------------------------------------------------------------------
+ * Two-run interval masks with ONE GROUP SIZE PER AXIS, additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout
+ * changed; the entries above stay as they are).  Cross-attention of a video onto frame-aligned condition tokens: a query
+ * group is a latent frame (q_group >= 8 tokens, 1560 at 480 x 832), a key group a handful of tokens (k_group >= 1).  With
+ * q_groups = ceil(Lq / q_group), k_groups = ceil(Lk / k_group) and vis[q_groups][k_groups], query i of sample b sees key
+ * j iff
+ *   i < qlen  and  j < klen  and  vis[i div q_group][j div k_group].
+ * Everything else is the contract of omh_interval_mask, word for word: at most two runs per row and per column, the two
+ * tables (q_iv in key groups, k_iv in query groups; omh_interval_mask_tables builds them — it works on the matrix and
+ * knows no group size), clamped table values, blind rows (o = 0, lse = -inf, dq = 0, written), unseen keys (dk = dv = 0,
+ * written), rows past qlen never read, lse optional / o32 REQUIRED, phases 0..3, out_bf16, q_prescaled, short-sequence
+ * kernels only, no split, no workspace, no atomics, repeatable bit for bit, and the same refusals in the same order with
+ * the same codes (q_group < 8 or k_group < 1 where group < 8 stands; there is no reserved field).  With q_group ==
+ * k_group the bits of omh_flash_attn_*_interval_d128.  The dK / dV kernel reads the up to 128 table rows of its keys
+ * across the lanes of a wave, not one after another.
+ * ---------------------------------------------------------------------- */
+typedef struct omh_interval_rect_mask {
+    int32_t q_group, k_group, q_groups, k_groups;   /* q_group >= 8, k_group >= 1 */
+    const int32_t* q_iv;   /* device [q_groups][4]: key   groups [lo0,hi0) U [lo1,hi1) */
+    const int32_t* k_iv;   /* device [k_groups][4]: query groups, the same relation seen from the key */
+} omh_interval_rect_mask;
+int omh_flash_attn_fwd_interval_rect_d128(const omh_attn_args* args, const omh_interval_rect_mask* mask, omh_stream_t stream);
+int omh_flash_attn_bwd_interval_rect_d128(const omh_attn_bwd_args* args, const int32_t* q_lens,
+                                          const omh_interval_rect_mask* mask, omh_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Chunk-causal attention (a staircase over frame groups), additive to ABI v12 (OMH_ABI_VERSION unchanged, no struct layout
  * changed).  The reference has no counterpart: it denoises a clip as one bidirectional sequence.  With
  *   qlen / klen = q_lens[b] / k_lens[b] (or Lq / Lk), clamped as elsewhere,

@@ -148,6 +148,11 @@ class Interval3MaskArgs(C.Structure):
     _fields_ = [("group", i32), ("q_groups", i32), ("k_groups", i32), ("reserved", i32), ("q_iv", vp), ("k_iv", vp)]
 
 
+class IntervalRectMaskArgs(C.Structure):
+    """omh_interval_rect_mask (additive to ABI v12): the [groups, 4] tables of causal.IntervalMask(k_group=), one group size per axis."""
+    _fields_ = [("q_group", i32), ("k_group", i32), ("q_groups", i32), ("k_groups", i32), ("q_iv", vp), ("k_iv", vp)]
+
+
 class BlockPoolOperand(C.Structure):
     """omh_block_pool_operand (additive to ABI v12): one bf16 operand of omh_block_pool_d128 and its outputs."""
     _fields_ = [("x", vp), ("ld", i64), ("L", i32), ("reserved", i32), ("lens", vp), ("mean", vp), ("coh", vp)]
@@ -236,6 +241,8 @@ _SIGS = {
     "omh_flash_attn_fwd_interval3_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(Interval3MaskArgs), vp]),
     "omh_flash_attn_bwd_interval3_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(Interval3MaskArgs), vp]),
     "omh_interval_mask_tables3": (i32, [vp, i32, i32, vp, vp]),
+    "omh_flash_attn_fwd_interval_rect_d128": (i32, [C.POINTER(AttnArgs), C.POINTER(IntervalRectMaskArgs), vp]),
+    "omh_flash_attn_bwd_interval_rect_d128": (i32, [C.POINTER(AttnBwdArgs), vp, C.POINTER(IntervalRectMaskArgs), vp]),
     "omh_block_pool_d128": (i32, [C.POINTER(BlockPoolOperand), i32, i32, i32, vp]),
     "omh_block_select": (i32, [C.POINTER(BlockSelectArgs), vp]),
     "omh_block_mask_tables": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),

@@ -29,7 +29,7 @@ import ctypes
 import torch
 
 __all__ = ["chunk_causal_visible", "KVCache", "RollingKVCache", "sample", "IntervalMask", "interval_visible",
-           "teacher_forcing_groups",
+           "teacher_forcing_groups", "condition_window_visible",
            "sink_window_groups", "forcing_loss", "self_forcing_rollout", "dmd_sigmas", "dmd_loss", "critic_loss"]
 
 
@@ -60,14 +60,25 @@ class IntervalMask:
 
     ``runs=3``: the three-run form (omh_interval3_mask) — at most THREE runs per row and per column (ValueError for a
     fourth), tables [groups, 6] = lo0, hi0, lo1, hi1, lo2, hi2 from omh_interval_mask_tables3, and the three-run kernels
-    wherever the mask is passed.  Teacher forcing with an attention sink needs it."""
+    wherever the mask is passed.  Teacher forcing with an attention sink needs it.
 
-    def __init__(self, vis, group, device="cpu", runs=2):
+    ``k_group`` (an int >= 1): the rectangular form (omh_interval_rect_mask) — ``group`` >= 8 then cuts the query axis only
+    and ``k_group`` the key axis: query i sees key j iff ``vis[i // group, j // k_group]``.  Two runs (``runs=3`` beside it is
+    a ValueError), the same tables, the ..._interval_rect_d128 kernels wherever the mask is passed.  Cross-attention onto
+    frame-aligned condition tokens needs it: a query group is a latent frame, a key group a few tokens."""
+
+    def __init__(self, vis, group, device="cpu", runs=2, k_group=None):
         from . import _lib
         runs = int(runs)
         if runs not in (2, 3):
             raise ValueError(f"IntervalMask: runs = {runs}, 2 or 3 expected")
-        self.runs = runs
+        if k_group is not None:
+            k_group = int(k_group)
+            if runs != 2:
+                raise ValueError("IntervalMask: the rectangular form (k_group=) has two runs")
+            if k_group < 1:
+                raise ValueError(f"IntervalMask: k_group = {k_group}, at least 1 token expected")
+        self.runs, self.k_group = runs, k_group
         vis = torch.as_tensor(vis).detach().to("cpu")
         group = int(group)
         if vis.dim() != 2 or vis.shape[0] < 1 or vis.shape[1] < 1:
@@ -110,6 +121,9 @@ class IntervalMask:
 
     def c_struct(self):
         from . import _lib
+        if self.k_group is not None:
+            return _lib.IntervalRectMaskArgs(self.group, self.k_group, self.q_groups, self.k_groups, self.q_iv.data_ptr(),
+                                             self.k_iv.data_ptr())
         if self.runs == 3:
             return _lib.Interval3MaskArgs(self.group, self.q_groups, self.k_groups, 0, self.q_iv.data_ptr(), self.k_iv.data_ptr())
         return _lib.IntervalMaskArgs(self.group, self.q_groups, self.k_groups, 0, self.q_iv.data_ptr(), self.k_iv.data_ptr())
@@ -118,11 +132,12 @@ class IntervalMask:
         """Key tiles of ``tile`` tokens the forward's workgroups (``block`` query rows each) run on full-length samples,
         per head: what the kernel derives from the q_iv table, computed here from the same numbers."""
         q_iv, total = self.intervals()[0], 0
+        gk = self.group if self.k_group is None else self.k_group
         for q0 in range(0, Lq, block):
             rows = q_iv[q0 // self.group:(min(q0 + block, Lq) - 1) // self.group + 1]
             hull = []
             for lo, hi in ((0, 1), (2, 3), (4, 5))[:self.runs]:
-                iv = [(r[lo] * self.group, min(r[hi] * self.group, Lk)) for r in rows if r[hi] > r[lo]]
+                iv = [(r[lo] * gk, min(r[hi] * gk, Lk)) for r in rows if r[hi] > r[lo]]
                 iv = [(a, b) for a, b in iv if b > a]
                 if not iv:
                     continue
@@ -137,16 +152,17 @@ class IntervalMask:
 
 def interval_visible(mask, Lq, Lk, qlen=None, klen=None):
     """The rule of an ``IntervalMask`` as a dense bool mask [Lq, Lk] (plain torch, on the CPU): True where query i sees
-    key j.  ValueError when the mask's group counts are not ceil(Lq / group) x ceil(Lk / group)."""
-    g = mask.group
-    if (mask.q_groups, mask.k_groups) != ((Lq + g - 1) // g, (Lk + g - 1) // g):
-        raise ValueError(f"interval_visible: a mask of {mask.q_groups} x {mask.k_groups} groups of {g} does not cover "
+    key j.  ValueError when the mask's group counts are not ceil(Lq / group) x ceil(Lk / group) (ceil(Lk / k_group) for the
+    rectangular form)."""
+    g, gk = mask.group, mask.group if mask.k_group is None else mask.k_group
+    if (mask.q_groups, mask.k_groups) != ((Lq + g - 1) // g, (Lk + gk - 1) // gk):
+        raise ValueError(f"interval_visible: a mask of {mask.q_groups} x {mask.k_groups} groups of {g} x {gk} does not cover "
                          f"Lq = {Lq}, Lk = {Lk}")
     qlen = Lq if qlen is None else min(max(int(qlen), 0), Lq)
     klen = Lk if klen is None else min(max(int(klen), 0), Lk)
     i = torch.arange(Lq, dtype=torch.int64).view(Lq, 1)
     j = torch.arange(Lk, dtype=torch.int64).view(1, Lk)
-    dense = mask.vis.repeat_interleave(g, 0)[:Lq].repeat_interleave(g, 1)[:, :Lk]
+    dense = mask.vis.repeat_interleave(g, 0)[:Lq].repeat_interleave(gk, 1)[:, :Lk]
     return dense & (i < qlen) & (j < klen)
 
 
@@ -180,6 +196,45 @@ def sink_window_groups(n_chunks, sink_chunks, left_chunks):
     g = torch.arange(n).view(n, 1)
     j = torch.arange(n).view(1, n)
     return (j <= g) & ((j < S) | (j >= g - W))
+
+
+def condition_window_visible(q_frames, token_frames, n_text, back, ahead, frames_per_chunk=None, segments=1, frame_offset=0):
+    """Which context tokens the queries of a latent frame see in cross-attention, bool [segments * q_frames,
+    len(token_frames) + n_text] (plain torch, on the CPU) — the one statement of the rule of frame-aligned condition tokens.
+
+    Row r stands for the query tokens of latent frame f = ``frame_offset`` + r mod ``q_frames`` (``segments`` = 2: teacher
+    forcing, clean frame f and noisy frame f share the rule).  Column j < len(token_frames) is condition token j, of latent
+    frame g = ``token_frames[j]`` (-1: seen by every query); the last ``n_text`` columns are the text, seen by every query.
+    Frame f sees the token iff
+
+        g == -1  or  f - back <= g <= min(f + ahead, E)
+
+    where a side of (``back``, ``ahead``) below 0 is unbounded and E is the last frame of f's chunk,
+    (f // frames_per_chunk + 1) frames_per_chunk - 1, when ``frames_per_chunk`` is given (a causal student: nothing of a
+    later chunk is seen, whatever ``ahead`` says); without it there is no E.  The columns keep the order of ``token_frames``."""
+    q_frames, n_text, segments, frame_offset = int(q_frames), int(n_text), int(segments), int(frame_offset)
+    back, ahead = int(back), int(ahead)
+    g = torch.as_tensor(token_frames).detach().to("cpu")
+    if g.dim() != 1 or g.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"condition_window_visible: token_frames must be a 1-D integer tensor, got {tuple(g.shape)} {g.dtype}")
+    g = g.to(torch.int64)
+    if q_frames < 1 or n_text < 0 or segments < 1 or frame_offset < 0 or bool((g < -1).any()):
+        raise ValueError("condition_window_visible: q_frames >= 1, n_text >= 0, segments >= 1, frame_offset >= 0 and "
+                         "token_frames >= -1 expected")
+    if frames_per_chunk is not None and int(frames_per_chunk) < 1:
+        raise ValueError(f"condition_window_visible: frames_per_chunk = {frames_per_chunk}, None or >= 1 expected")
+    f = (frame_offset + torch.arange(q_frames, dtype=torch.int64)).view(q_frames, 1)
+    g = g.view(1, -1)
+    near = torch.ones(q_frames, g.shape[1], dtype=torch.bool)
+    if back >= 0:
+        near = near & (g >= f - back)
+    if ahead >= 0:
+        near = near & (g <= f + ahead)
+    if frames_per_chunk is not None:
+        fpc = int(frames_per_chunk)
+        near = near & (g <= (torch.div(f, fpc, rounding_mode="floor") + 1) * fpc - 1)
+    vis = torch.cat([near | (g == -1), torch.ones(q_frames, n_text, dtype=torch.bool)], 1)
+    return vis.repeat(segments, 1)
 
 
 class KVCache:
@@ -322,7 +377,7 @@ class RollingKVCache:
 
 @torch.no_grad()
 def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks=-1, make_scheduler, guide_scale,
-           context_t=0.0, sink_chunks=0, rolling=False, caches=None):
+           context_t=0.0, sink_chunks=0, rolling=False, caches=None, extra_conditions=None):
     """Denoise one clip chunk by chunk.  ``noise``: the initial latents [C, F, H, W] of the clip; ``context`` /
     ``context_null``: what ``WanModel.forward`` takes for a batch of one (a list with one [L, text_dim] tensor, or a
     ``ContextState``).  For every group of ``frames_per_chunk`` latent frames (the last one may be shorter):
@@ -337,6 +392,10 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
     first ``sink_chunks`` chunks of the clip as well.  ``rolling=True`` (needs ``left_chunks`` >= 0; implied by a sink):
     two ``RollingKVCache``s in place of the two ``KVCache``s — cache memory then does not depend on the clip's length.
     ``caches``: a pair (conditional, unconditional) of caches of batch 1 to use in place of fresh ones (they are reset).
+    ``extra_conditions``: condition tokens as ``WanModel.forward`` takes them, for the conditional branch only (``context``
+    is then the raw text, no ``ContextState``).  With ``"frames"`` and ``"window"`` every ``forward_chunk`` call — denoising
+    and commit passes alike — keeps only the tokens of the frames from the chunk's first frame - back to its last frame
+    (and the -1 tokens): a live stream needs nothing it does not have yet.
     The model's own
     ``set_causal_chunks`` setting is restored on the way out.  Returns the latents of the whole clip, fp32 [C, F, H, W]."""
     fpc = int(frames_per_chunk)
@@ -373,12 +432,12 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
             scheduler = make_scheduler()
             for t in scheduler.timesteps:
                 tt = torch.stack([t])
-                cond = model.forward_chunk([lat], tt, context, caches[0], commit=False)[0]
+                cond = model.forward_chunk([lat], tt, context, caches[0], commit=False, extra_conditions=extra_conditions)[0]
                 uncond = model.forward_chunk([lat], tt, context_null, caches[1], commit=False)[0]
                 lat = scheduler.step_cfg(cond, uncond, guide_scale, lat)
             done.append(lat)
             if f0 + fpc < F:
-                model.forward_chunk([lat], t_ctx, context, caches[0], commit=True)
+                model.forward_chunk([lat], t_ctx, context, caches[0], commit=True, extra_conditions=extra_conditions)
                 model.forward_chunk([lat], t_ctx, context_null, caches[1], commit=True)
         return torch.cat(done, dim=1)
     finally:
@@ -419,7 +478,7 @@ def forcing_loss(model, latents, noise, sigmas, timesteps, context, mode="teache
 
 
 def self_forcing_rollout(model, noise, context, *, frames_per_chunk, left_chunks=-1, sigmas, timesteps, exit_step,
-                         context_t=0.0, generator=None, cache=None):
+                         context_t=0.0, generator=None, cache=None, extra_conditions=None):
     """Roll a batch of clips out chunk by chunk with the few-step student sampler against a ``KVCache``, as at inference,
     and keep the graph of the LAST denoising step of every chunk (self forcing).  ``noise``: a list of B clips
     [C, F, H, W] of one shape, F a multiple of ``frames_per_chunk`` (ValueError otherwise); ``sigmas`` / ``timesteps``: the
@@ -432,6 +491,10 @@ def self_forcing_rollout(model, noise, context, *, frames_per_chunk, left_chunks
     2. step exit: ``forward_chunk(grad=True, commit=False)`` and x0_I = x - sigma v through ``ops.flow_x0_step``, attached;
     3. except behind the last chunk: ``forward_chunk(x0_I.detach(), context_t, commit=True)`` under ``no_grad`` — the later
        chunks attend to its keys and values as constants.
+
+    ``extra_conditions``: condition tokens as ``WanModel.forward`` takes them, handed to every ``forward_chunk`` call (with
+    ``"frames"`` and ``"window"`` each chunk keeps the tokens of its first frame - back to its last frame and the -1
+    tokens); tokens that require grad get it through the exit steps.
 
     Returns the list of B clips, fp32 [C, F, H, W], attached to the graph (the loss is the caller's).  The cache must
     stay as it is until ``backward()`` has run (a ``reset()`` in between makes the backward raise RuntimeError).  The
@@ -473,16 +536,19 @@ def self_forcing_rollout(model, noise, context, *, frames_per_chunk, left_chunks
             x = torch.stack([u[:, I * fpc:(I + 1) * fpc] for u in noise]).float().contiguous().detach()
             for j in range(exits[I]):
                 with torch.no_grad():
-                    v = torch.stack(model.forward_chunk(list(x.unbind(0)), t_d[j], context, cache, commit=False))
+                    v = torch.stack(model.forward_chunk(list(x.unbind(0)), t_d[j], context, cache, commit=False,
+                                                        extra_conditions=extra_conditions))
                     eps = torch.randn(x.shape, dtype=torch.float32, device=dev, generator=generator)
                     _, x = ops.flow_x0_step(v, x, sig_d[j], eps, sig_d[j + 1])
             j = exits[I]
-            v = torch.stack(model.forward_chunk(list(x.unbind(0)), t_d[j], context, cache, commit=False, grad=True))
+            v = torch.stack(model.forward_chunk(list(x.unbind(0)), t_d[j], context, cache, commit=False, grad=True,
+                                                extra_conditions=extra_conditions))
             x0 = ops.flow_x0_step(v, x, sig_d[j])
             done.append(x0)
             if I + 1 < chunks:
                 with torch.no_grad():
-                    model.forward_chunk(list(x0.detach().unbind(0)), t_ctx, context, cache, commit=True)
+                    model.forward_chunk(list(x0.detach().unbind(0)), t_ctx, context, cache, commit=True,
+                                        extra_conditions=extra_conditions)
         clip = torch.cat(done, dim=2)                                       # [B, C, F, H, W]
         return list(clip.unbind(0))
     finally:

@@ -97,7 +97,9 @@ struct AttnSplit {
 // only the tiles that are not inside the intersection of the i-th intervals of those groups, any i.  Never split.
 // The query tiles keep their natural order: last tile first, CHK's order, lost time under teacher forcing.
 // RUNS = 0: no interval mask.
-template <bool WIN, bool BLK = false, bool CHK = false, int RUNS = 0>
+// RECT (with RUNS = 2; omh_interval_rect_mask): the same path with one group size per axis — the query's group picks the
+// table row, the key group scales its values (omh_common.h IvlTab).
+template <bool WIN, bool BLK = false, bool CHK = false, int RUNS = 0, bool RECT = false>
 __global__ __launch_bounds__(256, 2)
 void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const AttnSplit wk, const BlkList bl,
                                 const ChunkRule ck) {
@@ -107,7 +109,8 @@ void flash_attn_fwd_d128_kernel(const omh_attn_args p, const int q_tiles, const 
     constexpr int NR = IVL ? RUNS : 2;                    // (the interval types need a run count where nothing uses them)
     static_assert(RUNS == 0 || RUNS == 2 || RUNS == 3, "two-run and three-run tables");
     static_assert(!IVL || (WIN && !CHK), "an interval mask runs on the band's masking, in place of the other rules");
-    const IvlTab iv = omh_ivl_tab(bl);                    // IVL: the table arrives in the BlkList argument
+    static_assert(!RECT || RUNS == 2, "the rectangular form has two runs");
+    const IvlTab iv = omh_ivl_tab<RECT>(bl);              // IVL: the table arrives in the BlkList argument
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (KT_BYTES + VT_BYTES)];
 
     const int tid = threadIdx.x;
@@ -627,7 +630,7 @@ static int attn_fwd_masked(const omh_attn_args* args, omh_stream_t stream, MaskC
     const int nwg = q_tiles * a.H * a.B;
     AttnSplit wk = {nwg, 0, 1, nullptr, nullptr};
     omh_clear_status();
-    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<M::WIN, M::BLK, M::CHK, M::RUNS>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a,
+    hipLaunchKernelGGL((flash_attn_fwd_d128_kernel<M::WIN, M::BLK, M::CHK, M::RUNS, M::RECT>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a,
                        q_tiles, wk, bl, ck);
     return omh_launch_status();
 }
@@ -663,6 +666,15 @@ extern "C" int omh_flash_attn_fwd_interval_d128(const omh_attn_args* args, const
 }
 extern "C" int omh_flash_attn_fwd_interval3_d128(const omh_attn_args* args, const omh_interval3_mask* mask, omh_stream_t stream) {
     return attn_fwd_interval<3>(args, mask, stream);
+}
+
+// the forward under a two-run interval mask with one group size per axis (include/omh.h: omh_interval_rect_mask)
+extern "C" int omh_flash_attn_fwd_interval_rect_d128(const omh_attn_args* args, const omh_interval_rect_mask* mask, omh_stream_t stream) {
+    if (!mask) return OMH_E_BADARG;
+    return attn_fwd_masked<MaskIntervalsRect>(args, stream, [&](const omh_attn_args& a, BlkList& bl, ChunkRule&) {
+        bl = omh_ivl_arg(mask->q_iv, mask->q_group, mask->q_groups, mask->k_groups, mask->k_group);
+        return omh_interval_rect_mask_check(mask, a.Lq, a.Lk);
+    });
 }
 
 // The two tables of an interval mask from its bool matrix (host functions: no device is touched).  Row g of q_iv: the at

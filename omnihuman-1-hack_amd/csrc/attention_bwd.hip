@@ -395,6 +395,7 @@ int omh_launch_attn_bwd2_sparse(const omh_attn_bwd_args& a, const int32_t* q_len
 int omh_launch_attn_bwd2_chunk(const omh_attn_bwd_args& a, const int32_t* q_lens, const ChunkRule& ck, hipStream_t s);
 int omh_launch_attn_bwd2_interval(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval_mask& m, hipStream_t s);
 int omh_launch_attn_bwd2_interval3(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval3_mask& m, hipStream_t s);
+int omh_launch_attn_bwd2_interval_rect(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval_rect_mask& m, hipStream_t s);
 
 static bool bwd_ptrs_set(const omh_attn_bwd_args& a) {
     return a.q && a.k && a.v && a.dout && a.lse && a.delta && a.dq && a.dk && a.dv;
@@ -483,6 +484,17 @@ extern "C" int omh_flash_attn_bwd_interval_d128(const omh_attn_bwd_args* args, c
 extern "C" int omh_flash_attn_bwd_interval3_d128(const omh_attn_bwd_args* args, const int32_t* q_lens, const omh_interval3_mask* mask,
                                                  omh_stream_t stream) {
     return bwd_interval_entry(args, q_lens, mask, stream, omh_launch_attn_bwd2_interval3);
+}
+// the same under the two-run mask with one group size per axis
+extern "C" int omh_flash_attn_bwd_interval_rect_d128(const omh_attn_bwd_args* args, const int32_t* q_lens,
+                                                     const omh_interval_rect_mask* mask, omh_stream_t stream) {
+    if (!mask) return OMH_E_BADARG;
+    return bwd_masked_entry(args, q_lens, [&] {
+        const int rc1 = omh_interval_rect_mask_check(mask, args->Lq, args->Lk);
+        if (rc1) return rc1;
+        omh_clear_status();
+        return omh_launch_attn_bwd2_interval_rect(*args, q_lens, *mask, (hipStream_t)stream);
+    });
 }
 
 extern "C" int omh_flash_attn_bwd_d128(const omh_attn_bwd_args* args, omh_stream_t stream) {

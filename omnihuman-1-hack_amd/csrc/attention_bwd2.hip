@@ -227,8 +227,9 @@ struct BwdSplit {
 // (omh_common.h IvlTab, the q_iv table, rows of 2 RUNS ints) — each row has the RUNS key intervals of its group; the
 // workgroup runs the key tiles inside the hulls of its groups' first, second, ... intervals: up to RUNS ranges of tiles
 // with a jump between them (omh_ivl_tiles; the forward's flash_attn_fwd_d128_kernel documents the ranges).  The table is
-// read before the loop.  RUNS = 0: no interval mask.
-template <bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, int RUNS = 0>
+// read before the loop.  RUNS = 0: no interval mask.  RECT (with RUNS = 2; omh_flash_attn_bwd_interval_rect_d128): one group
+// size per axis — the query's group picks the table row, the key group scales its values.
+template <bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, int RUNS = 0, bool RECT = false>
 __global__ __launch_bounds__(256, 2)
 void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const BwdSplit wk, const int wl, const int wr,
                          const int32_t* __restrict__ q_lens, const BlkList bl, const ChunkRule ck) {
@@ -236,6 +237,7 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     constexpr bool IVL = RUNS > 0;
     constexpr int NR = IVL ? RUNS : 2;                               // (the interval types need a run count where nothing uses them)
     static_assert(RUNS == 0 || RUNS == 2 || RUNS == 3, "two-run and three-run tables");
+    static_assert(!RECT || RUNS == 2, "the rectangular form has two runs");
     static_assert(!CHK || (WIN && VLEN), "the staircase runs on the varlen band kernels' masking");
     static_assert(!IVL || (WIN && VLEN && !CHK), "an interval mask runs on the varlen band kernels' masking");
     static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
@@ -274,7 +276,7 @@ void attn_bwd2_dq_kernel(const omh_attn_bwd_args p, const int q_blocks, const Bw
     IvlSpan<NR> span = {};                                           // IVL: this lane's intervals of keys
     IvlTiles<NR> plan = {};                                          // IVL: the tile ranges of the loop
     if constexpr (IVL) {
-        const IvlTab iv = omh_ivl_tab(bl);                           // the table arrives in the BlkList argument
+        const IvlTab iv = omh_ivl_tab<RECT>(bl);                     // the table arrives in the BlkList argument
         const int q0 = qb * 128, q1 = min(q0 + 128, qlen) - 1;      // live query rows of this workgroup
         if (q1 >= q0) plan = omh_ivl_tiles<NR>(iv, q0, q1, klen, TB, nullptr);
         t_first = plan.t_first; n_tiles = plan.n_tiles;
@@ -565,8 +567,9 @@ __device__ __forceinline__ void dkdv_store(const omh_attn_bwd_args& p, const Bwd
 // to its last live key's upper end.  One division per workgroup and one per key, none in the loop.
 // RUNS > 0 (see attn_bwd2_dq_kernel): the k_iv table — each key has the RUNS intervals of query rows of its group, cut at
 // qlen; the workgroup walks the query tiles inside the hulls of its groups' first, second, ... intervals (up to RUNS ranges
-// of tiles, omh_ivl_tiles).  A key group nobody sees runs no tile: dk = dv = 0.
-template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, int RUNS = 0>
+// of tiles, omh_ivl_tiles).  A key group nobody sees runs no tile: dk = dv = 0.  RECT: one group size per axis, the key's
+// group picks the row; the workgroup's 128 keys may span 128 rows, which it reads across its lanes (omh_ivl_tiles WIDE).
+template <int WAVES, int KPW, bool PRE, bool WIN, bool VLEN = false, bool BLK = false, bool CHK = false, int RUNS = 0, bool RECT = false>
 __global__ __launch_bounds__(64 * WAVES, 1)
 void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const BwdSplit wk, const int wl, const int wr,
                            const int32_t* __restrict__ q_lens, const BlkList bl, const ChunkRule ck) {
@@ -574,6 +577,7 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     constexpr bool IVL = RUNS > 0;
     constexpr int NR = IVL ? RUNS : 2;                               // (the interval types need a run count where nothing uses them)
     static_assert(RUNS == 0 || RUNS == 2 || RUNS == 3, "two-run and three-run tables");
+    static_assert(!RECT || RUNS == 2, "the rectangular form has two runs");
     static_assert(!CHK || (WIN && VLEN), "the staircase runs on the varlen band kernels' masking");
     static_assert(!IVL || (WIN && VLEN && !CHK), "an interval mask runs on the varlen band kernels' masking");
     static_assert(!BLK || (!WIN && !VLEN), "a block mask excludes the band");
@@ -627,9 +631,9 @@ void attn_bwd2_dkdv_kernel(const omh_attn_bwd_args p, const int k_blocks, const 
     IvlTiles<NR> plan = {};                                          // IVL: the tile ranges of the loop
     if constexpr (IVL) {
         static_assert(KPW == 1, "one key per lane");
-        const IvlTab iv = omh_ivl_tab(bl);                           // the table arrives in the BlkList argument
+        const IvlTab iv = omh_ivl_tab<RECT>(bl);                     // the table arrives in the BlkList argument
         const int k0 = kb * 128, k1 = min(k0 + 128, klen) - 1;      // live keys of this workgroup
-        if (k1 >= k0) plan = omh_ivl_tiles<NR>(iv, k0, k1, qlen, TB, nullptr);
+        if (k1 >= k0) plan = omh_ivl_tiles<NR, RECT>(iv, k0, k1, qlen, TB, nullptr);
         t_first = plan.t_first; n_tiles = plan.n_tiles;
         span = omh_ivl_row<NR>(iv, (kb * 128 + wave * 32 + li) / iv.group, qlen);
     } else if constexpr (WIN) {
@@ -1313,10 +1317,10 @@ static int launch_attn_bwd2_masked(const omh_attn_bwd_args& a, int wl, int wr, c
     wl = wl < 0 ? -1 : (wl > wmax ? wmax : wl);
     wr = wr < 0 ? -1 : (wr > wmax ? wmax : wr);
     constexpr int LDS_DQ = 4 * TILE_BYTES, LDS_KV = 4 * TILE_BYTES + 2 * 128 * 4;
-    const auto dq_gen = attn_bwd2_dq_kernel<false, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
-    const auto dq_pre = attn_bwd2_dq_kernel<true, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
-    const auto dkdv_gen = attn_bwd2_dkdv_kernel<4, 1, false, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
-    const auto dkdv_pre = attn_bwd2_dkdv_kernel<4, 1, true, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS>;
+    const auto dq_gen = attn_bwd2_dq_kernel<false, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS, M::RECT>;
+    const auto dq_pre = attn_bwd2_dq_kernel<true, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS, M::RECT>;
+    const auto dkdv_gen = attn_bwd2_dkdv_kernel<4, 1, false, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS, M::RECT>;
+    const auto dkdv_pre = attn_bwd2_dkdv_kernel<4, 1, true, M::WIN, M::VLEN, M::BLK, M::CHK, M::RUNS, M::RECT>;
     static bool attr_set = false;                                    // (one flag per instantiation of this function)
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)dq_gen, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
@@ -1360,6 +1364,10 @@ template <int RUNS, typename Mask>
 static int launch_attn_bwd2_interval(const omh_attn_bwd_args& a, const int32_t* q_lens, const Mask& m, hipStream_t s) {
     return launch_attn_bwd2_masked<MaskIntervals<RUNS>>(a, -1, -1, q_lens, omh_ivl_arg(m.q_iv, m.group, m.q_groups, m.k_groups),
                                                         omh_ivl_arg(m.k_iv, m.group, m.k_groups, m.q_groups), ChunkRule{}, s);
+}
+int omh_launch_attn_bwd2_interval_rect(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval_rect_mask& m, hipStream_t s) {
+    return launch_attn_bwd2_masked<MaskIntervalsRect>(a, -1, -1, q_lens, omh_ivl_arg(m.q_iv, m.q_group, m.q_groups, m.k_groups, m.k_group),
+                                                      omh_ivl_arg(m.k_iv, m.k_group, m.k_groups, m.q_groups, m.q_group), ChunkRule{}, s);
 }
 int omh_launch_attn_bwd2_interval(const omh_attn_bwd_args& a, const int32_t* q_lens, const omh_interval_mask& m, hipStream_t s) {
     return launch_attn_bwd2_interval<2>(a, q_lens, m, s);

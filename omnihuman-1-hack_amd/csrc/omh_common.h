@@ -146,8 +146,9 @@ static inline int omh_launch_status() {
 // ascending indices of the 128-position blocks of the other side (row lists: forward and dQ; column lists: dK / dV).
 // The IVL kernels (interval masks, below) receive their table in this same argument, since no kernel has both a block
 // mask and an interval mask: idx = the table, heads = group, lists = its rows, stride = groups of the other axis, cnt
-// unused.  omh_ivl_arg / omh_ivl_tab are the only two places that know the mapping; a change of this struct's fields
-// must keep them (and the asserts behind IvlTab) in step.
+// unused — but for the rectangular form (omh_interval_rect_mask: one group size per axis), whose kernels read the OTHER
+// axis' group size from cnt's eight bytes as an integer.  omh_ivl_arg / omh_ivl_tab are the only two places that know the
+// mapping; a change of this struct's fields must keep them (and the asserts behind IvlTab) in step.
 struct BlkList {
     const int32_t* cnt;   // [heads][lists]
     const int32_t* idx;   // [heads][lists][stride]
@@ -191,15 +192,21 @@ static inline int omh_chunk_rule(const omh_chunk_causal* c, int Lq, int Lk, Chun
 // groups of `group` positions; `n` rows, `other` groups on the other axis.  RUNS (2: omh_interval_mask, 3:
 // omh_interval3_mask) is a template argument of the kernels and of every helper below: one implementation, two
 // instantiations (a two-run mask through the three-run kernels costs 7 % forward, 15 % backward: DESIGN.md 4.2g).
+// `group` cuts the workgroup's own axis (which row of the table a position reads), `ogroup` the other axis (what a table
+// value is worth in positions).  The square masks have one size for both and their kernels one value: RECT (a template
+// argument, like RUNS) tells the instantiations of omh_interval_rect_mask, which hold the two apart.
 struct IvlTab {
     const int32_t* iv;    // [n][2 RUNS]
-    int group, n, other;
+    int group, n, other, ogroup;
 };
 // The IVL kernels take their table in the BlkList argument (no kernel has both): a further kernel argument would change
 // the kernarg segment, and with it the scalar loads of the instantiations that must keep their instruction streams.
-static inline BlkList omh_ivl_arg(const int32_t* iv, int group, int n, int other) { return BlkList{nullptr, iv, group, n, other}; }
+// (ogroup: the rectangular form only — an integer in the place of the cnt pointer, never dereferenced)
+static inline BlkList omh_ivl_arg(const int32_t* iv, int group, int n, int other, int ogroup = 0) {
+    return BlkList{(const int32_t*)(uintptr_t)(uint32_t)ogroup, iv, group, n, other};
+}
 static_assert(sizeof(BlkList) == 2 * sizeof(void*) + 4 * sizeof(int) && sizeof(IvlTab) + sizeof(void*) == sizeof(BlkList),
-              "IvlTab travels in a BlkList: one pointer and three ints beside the unused cnt");
+              "IvlTab travels in a BlkList: one pointer and three ints, and the other axis' group in the place of cnt");
 static_assert(std::is_same<decltype(BlkList::idx), decltype(IvlTab::iv)>::value && std::is_same<decltype(BlkList::heads), int>::value &&
               std::is_same<decltype(BlkList::lists), int>::value && std::is_same<decltype(BlkList::stride), int>::value,
               "omh_ivl_arg / omh_ivl_tab map idx, heads, lists, stride to iv, group, n, other");
@@ -213,8 +220,19 @@ static inline int omh_interval_mask_check(const Mask* m, int Lq, int Lk) {
     if (((uintptr_t)m->q_iv | (uintptr_t)m->k_iv) & 3) return OMH_E_ALIGN;
     return 0;
 }
+// the same for omh_interval_rect_mask (one group size per axis, no reserved field), in the same order with the same codes
+static inline int omh_interval_rect_mask_check(const omh_interval_rect_mask* m, int Lq, int Lk) {
+    if (!m || !m->q_iv || !m->k_iv || m->q_group < 8 || m->k_group < 1) return OMH_E_BADARG;
+    if ((int64_t)Lq + Lk >= (1LL << 28)) return OMH_E_SHAPE;
+    if (m->q_groups != (Lq + m->q_group - 1) / m->q_group || m->k_groups != (Lk + m->k_group - 1) / m->k_group) return OMH_E_BADARG;
+    if (((uintptr_t)m->q_iv | (uintptr_t)m->k_iv) & 3) return OMH_E_ALIGN;
+    return 0;
+}
 #if defined(__HIPCC__)
-__device__ __forceinline__ IvlTab omh_ivl_tab(const BlkList& bl) { return IvlTab{bl.idx, bl.heads, bl.lists, bl.stride}; }
+template <bool RECT = false>
+__device__ __forceinline__ IvlTab omh_ivl_tab(const BlkList& bl) {
+    return IvlTab{bl.idx, bl.heads, bl.lists, bl.stride, RECT ? (int)(uint32_t)(uintptr_t)bl.cnt : bl.heads};
+}
 // One position's (or one workgroup's) view of the other axis: RUNS intervals of positions [lo, lo + len), len <= 0: empty.
 // (Every loop over the runs is fully unrolled and indexes with constants: the arrays are registers, never scratch.)
 template <int RUNS>
@@ -238,7 +256,7 @@ __device__ __forceinline__ IvlSpan<RUNS> omh_ivl_row(const IvlTab& tb, int g, in
     for (int i = 0; i < RUNS; ++i) { a[i] = min(max(r[2 * i], 0), tb.other); b[i] = min(max(r[2 * i + 1], 0), tb.other); }
     IvlSpan<RUNS> s;
 #pragma unroll
-    for (int i = 0; i < RUNS; ++i) { s.lo[i] = a[i] * tb.group; s.len[i] = max(min(b[i] * tb.group, end) - s.lo[i], 0); }
+    for (int i = 0; i < RUNS; ++i) { s.lo[i] = a[i] * tb.ogroup; s.len[i] = max(min(b[i] * tb.ogroup, end) - s.lo[i], 0); }
     return s;
 }
 // The tiles of `tile` positions a workgroup runs: up to RUNS ranges of consecutive tiles.  tile(x), x in [0, n_tiles), is
@@ -258,7 +276,10 @@ struct IvlTiles {
 // intervals (their lower ends ascend: every row's do), empty ones dropped, neighbours that touch or overlap in tile units
 // merged.  whole (may be NULL; 2 RUNS ints): [lo, hi] of the positions EVERY one of those groups sees through its i-th
 // interval (hi < lo: none).  Scalar reads, once per workgroup.
-template <int RUNS>
+// WIDE (the rectangular dK / dV kernel, whose 128 keys span up to 128 rows of one-token groups): the rows are read across
+// the lanes of the wave instead, row g0 + lane, + 64, ..., and the hulls and intersections reduced with six butterfly
+// steps — min and max of the same integers, so the plan is the one the scalar walk gives.
+template <int RUNS, bool WIDE = false>
 __device__ __forceinline__ IvlTiles<RUNS> omh_ivl_tiles(const IvlTab& tb, int x0, int x1, int end, int tile, int* whole) {
     const int g0 = x0 / tb.group, g1 = x1 / tb.group;
     int hlo[RUNS], hhi[RUNS], wlo[RUNS], whi[RUNS];                  // hulls and intersections, [lo, hi)
@@ -270,6 +291,29 @@ __device__ __forceinline__ IvlTiles<RUNS> omh_ivl_tiles(const IvlTab& tb, int x0
     for (int i = 0; i < RUNS; ++i) wlo[i] = 0;
 #pragma unroll
     for (int i = 0; i < RUNS; ++i) whi[i] = 1 << 30;
+    if constexpr (WIDE) {
+        for (int g = g0 + (int)(threadIdx.x & 63); g <= g1; g += 64) {
+            const IvlSpan<RUNS> s = omh_ivl_row<RUNS>(tb, g, end);
+#pragma unroll
+            for (int i = 0; i < RUNS; ++i) {
+                if (s.len[i] > 0) { hlo[i] = min(hlo[i], s.lo[i]); hhi[i] = max(hhi[i], s.lo[i] + s.len[i]); }
+                wlo[i] = max(wlo[i], s.lo[i]); whi[i] = min(whi[i], s.lo[i] + s.len[i]);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+            for (int i = 0; i < RUNS; ++i) {
+                hlo[i] = min(hlo[i], __shfl_xor(hlo[i], o, 64)); hhi[i] = max(hhi[i], __shfl_xor(hhi[i], o, 64));
+                wlo[i] = max(wlo[i], __shfl_xor(wlo[i], o, 64)); whi[i] = min(whi[i], __shfl_xor(whi[i], o, 64));
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < RUNS; ++i) {
+            hlo[i] = __builtin_amdgcn_readfirstlane(hlo[i]); hhi[i] = __builtin_amdgcn_readfirstlane(hhi[i]);
+            wlo[i] = __builtin_amdgcn_readfirstlane(wlo[i]); whi[i] = __builtin_amdgcn_readfirstlane(whi[i]);
+        }
+    } else {
     for (int g = g0; g <= g1; ++g) {
         const IvlSpan<RUNS> s = omh_ivl_row<RUNS>(tb, __builtin_amdgcn_readfirstlane(g), end);
 #pragma unroll
@@ -277,6 +321,7 @@ __device__ __forceinline__ IvlTiles<RUNS> omh_ivl_tiles(const IvlTab& tb, int x0
             if (s.len[i] > 0) { hlo[i] = min(hlo[i], s.lo[i]); hhi[i] = max(hhi[i], s.lo[i] + s.len[i]); }
             wlo[i] = max(wlo[i], s.lo[i]); whi[i] = min(whi[i], s.lo[i] + s.len[i]);
         }
+    }
     }
     if (whole) {
 #pragma unroll
@@ -316,16 +361,18 @@ __device__ __forceinline__ IvlTiles<RUNS> omh_ivl_tiles(const IvlTab& tb, int x0
 
 // ---- which mask a kernel instantiation carries: the template arguments of the masked launchers, by name ----
 // (attention.hip: flash_attn_fwd_d128_kernel<WIN, BLK, CHK, RUNS>; attention_bwd2.hip: the dQ and dK / dV kernels'
-// <.., WIN, VLEN, BLK, CHK, RUNS>.  VLEN — q_lens — exists in the backward only: the forward's band kernel reads q_lens itself.)
-template <bool WIN_, bool VLEN_, bool BLK_, bool CHK_, int RUNS_>
+// <.., WIN, VLEN, BLK, CHK, RUNS, RECT>.  VLEN — q_lens — exists in the backward only: the forward's band kernel reads q_lens
+// itself.  RECT: the interval mask has one group size per axis.)
+template <bool WIN_, bool VLEN_, bool BLK_, bool CHK_, int RUNS_, bool RECT_ = false>
 struct MaskKind {
-    static constexpr bool WIN = WIN_, VLEN = VLEN_, BLK = BLK_, CHK = CHK_;
+    static constexpr bool WIN = WIN_, VLEN = VLEN_, BLK = BLK_, CHK = CHK_, RECT = RECT_;
     static constexpr int RUNS = RUNS_;
 };
 template <bool VLEN> using MaskBand = MaskKind<true, VLEN, false, false, 0>;     // the band, with or without q_lens
 using MaskBlocks = MaskKind<false, false, true, false, 0>;                       // omh_block_mask
 using MaskStairs = MaskKind<true, true, false, true, 0>;                         // omh_chunk_causal
 template <int RUNS> using MaskIntervals = MaskKind<true, true, false, false, RUNS>;   // omh_interval_mask (2), omh_interval3_mask (3)
+using MaskIntervalsRect = MaskKind<true, true, false, false, 2, true>;           // omh_interval_rect_mask
 
 // ---- split of a launch's last, partly filled round of workgroups (host side; attention.hip, attention_bwd2.hip) ----
 // A launch of `nwg` equal workgroups on `slots` resident slots takes ceil(nwg / slots) rounds; its last round holds

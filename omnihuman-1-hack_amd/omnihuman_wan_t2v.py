@@ -238,6 +238,31 @@ class _Adapters:
         cp = self.condition_projector
         return _DenseFn.apply(t, cp.weight, cp.bias, 0)
 
+    @staticmethod
+    def condition_frames(n_audio_pairs: int, n_pose: int, ref_frames: int = 0) -> torch.Tensor:
+        """The latent frame of every token ``condition_tokens`` emits for ``n_audio_pairs`` audio pairs and ``n_pose`` pose
+        tokens, int64 [2 n_audio_pairs + n_pose] in its order: the pair of video frame t is two tokens, of frames t and
+        t + 1, the pose token of video frame v follows them.  A token of video frame v sits at latent frame
+        (v + 3) // 4 + ``ref_frames`` (the causal VAE: frame 0 alone, then groups of four; ``ref_frames``: the latent frames
+        of a reference image in front of the clip) — what ``extra_conditions["frames"]`` of ``WanModel.forward`` takes."""
+        video = [t + k for t in range(int(n_audio_pairs)) for k in (0, 1)] + list(range(int(n_pose)))
+        return torch.tensor([(v + 3) // 4 + int(ref_frames) for v in video], dtype=torch.int64)
+
+    def _windowed(self, tokens, audio, pose, ref_frames=0, frames=None):
+        """``extra_conditions`` for the backbone: the tokens as they are, or — with ``config["condition_window"]`` =
+        (back, ahead) — a dict with their latent frames and the window (``frames``: given for ready tokens, else those of
+        ``condition_tokens(audio, pose)``)."""
+        window = self.config.get("condition_window")
+        if window is None or tokens is None:
+            return tokens
+        if frames is None:
+            d = tokens.shape[-1]
+            paired = audio is not None and audio.shape[-1] == 2 * d
+            frames = self.condition_frames(audio.shape[1] if paired else 0, 0 if pose is None else pose.shape[1], ref_frames)
+            if audio is not None and not paired:            # a single audio frame: one token per frame, in front
+                frames = torch.cat([self.condition_frames(0, audio.shape[1], ref_frames), frames])
+        return {"tokens": tokens, "frames": frames, "window": (int(window[0]), int(window[1]))}
+
 
 class OmniConditionsModule(_Adapters, nn.Module):
     """omnihuman_wan_t2v.py:13-92 (same constructor, parameters and methods)."""
@@ -362,6 +387,10 @@ class OmniHumanWanT2V(_Adapters, nn.Module):
         tok = self.condition_tokens(cond.get("audio"), cond.get("pose"))
         if tok is not None:
             cond["tokens"] = tok
+            if self.config.get("condition_window") is not None:      # frame-aligned tokens: their latent frames and the window
+                ref_frames = 0 if cond.get("reference") is None else cond["reference"].shape[1] // self.wan_t2v.model.patch_size[0]
+                cond.update({k: v for k, v in self._windowed(tok, cond.get("audio"), cond.get("pose"), ref_frames).items()
+                             if k != "tokens"})
         return cond
 
     def _compute_seq_len(self, shape) -> int:
@@ -403,7 +432,10 @@ class OmniHumanWanT2V(_Adapters, nn.Module):
         self.scheduler.set_begin_index(0)
         seq_len = self._compute_seq_len((1, z, T + (0 if ref is None else ref.shape[1]), h, w))
         # everything that depends on the conditions alone: once per sample
-        st_c = model.encode_context([ctx], extra_conditions=cond.get("tokens"))
+        tokens = cond.get("tokens")
+        if tokens is not None and cond.get("frames") is not None:
+            tokens = {"tokens": tokens, "frames": cond["frames"], "window": cond["window"]}
+        st_c = model.encode_context([ctx], extra_conditions=tokens)
         st_u = model.encode_context([ctx_null])
         n = len(self.scheduler.timesteps)
         for i, t in enumerate(self.scheduler.timesteps):
@@ -428,7 +460,12 @@ class OmniHumanWanT2V(_Adapters, nn.Module):
         ``tokens`` [B, Ne, dim] (ready condition tokens, e.g. from ``prepare_conditions``),
         ``audio`` / ``pose`` (adapter outputs, turned into tokens here, gradients reach the projector and the
         temporal embedding), ``audio_features`` [B, T, audio_dim] / ``pose_heatmaps`` [B, K, T, H, W] (raw inputs:
-        the adapters run here and are trained).  ``noise`` fixes the draw (tests)."""
+        the adapters run here and are trained).  ``noise`` fixes the draw (tests).
+
+        ``config["condition_window"]`` = (back, ahead): the tokens are frame-aligned — a query of latent frame f sees the
+        tokens of frames f - back .. f + ahead (``condition_frames``; ready ``tokens`` bring their ``frames`` along) —
+        through ``WanModel.forward(extra_conditions={"tokens", "frames", "window"})``.  Without the key: every query sees
+        every token, as ever."""
         frames = frames.to(self.device).float()
         t = t.to(self.device).float()
         if noise is None:
@@ -446,7 +483,9 @@ class OmniHumanWanT2V(_Adapters, nn.Module):
             pose = self.process_pose(conditions["pose_heatmaps"].to(self.device))
         tokens = conditions.get("tokens")
         if tokens is None:
-            tokens = self.condition_tokens(audio, pose)
+            tokens = self._windowed(self.condition_tokens(audio, pose), audio, pose)
+        elif conditions.get("frames") is not None:
+            tokens = self._windowed(tokens, None, None, frames=conditions["frames"])
         B = frames.shape[0]
         pred = self.wan_t2v.model(noisy, t, context=[ctx.to(self.device)] * B,
                                   seq_len=self._compute_seq_len(noisy.shape), extra_conditions=tokens)

@@ -183,11 +183,18 @@ class AttnMask:
         return self.rule if self.kind == "chunk" else self.rule.c_struct()
 
 
-# (kind, runs of an interval mask) -> the forward and the backward entry
+# (kind, runs of an interval mask; "rect": its form with one group size per axis) -> the forward and the backward entry
 _MASK_ENTRIES = {("block", 0): ("omh_flash_attn_fwd_sparse_d128", "omh_flash_attn_bwd_sparse_d128"),
                  ("chunk", 0): ("omh_flash_attn_fwd_chunk_d128", "omh_flash_attn_bwd_chunk_d128"),
                  ("interval", 2): ("omh_flash_attn_fwd_interval_d128", "omh_flash_attn_bwd_interval_d128"),
-                 ("interval", 3): ("omh_flash_attn_fwd_interval3_d128", "omh_flash_attn_bwd_interval3_d128")}
+                 ("interval", 3): ("omh_flash_attn_fwd_interval3_d128", "omh_flash_attn_bwd_interval3_d128"),
+                 ("interval", "rect"): ("omh_flash_attn_fwd_interval_rect_d128", "omh_flash_attn_bwd_interval_rect_d128")}
+
+
+def _mask_entries(mask):
+    """The (forward, backward) entry names of a resolved mask that has a rule."""
+    rect = getattr(mask.rule, "k_group", None) is not None
+    return _MASK_ENTRIES[mask.kind, "rect" if rect else getattr(mask.rule, "runs", 0)]
 
 
 # what flash_attn_bwd's "needs o32" assert calls each kind
@@ -200,7 +207,7 @@ def attn_mask(window=(-1, -1), block_mask=None, chunk_causal=None, interval_mask
     bool block tensor; ``chunk_causal`` = (chunk, left_chunks, q_offset); ``interval_mask``: a ``causal.IntervalMask``.
     ValueError for more than one of them (a mask is not combined with anything), a block mask of another head count
     than 1 or H or of other block counts, chunk < 1 or q_offset < 0, an interval mask that is no IntervalMask or has
-    group counts other than ceil(Lq / group) x ceil(Lk / group).  The tables go to ``device``; None: a mask that is on a
+    group counts other than ceil(Lq / group) x ceil(Lk / group) (``IntervalMask(k_group=)``: ceil(Lk / k_group)).  The tables go to ``device``; None: a mask that is on a
     GPU already stays there and one on the CPU goes to the current device."""
     on = (window[0] >= 0 or window[1] >= 0, block_mask is not None, chunk_causal is not None, interval_mask is not None)
     if not any(on):
@@ -227,10 +234,10 @@ def attn_mask(window=(-1, -1), block_mask=None, chunk_causal=None, interval_mask
         kind, rule = "interval", interval_mask
         if not isinstance(rule, IntervalMask):
             raise ValueError("interval_mask: a causal.IntervalMask expected (it holds the group size and the device tables)")
-        g = rule.group
-        if (rule.q_groups, rule.k_groups) != ((Lq + g - 1) // g, (Lk + g - 1) // g):
-            raise ValueError(f"interval mask of {rule.q_groups} x {rule.k_groups} groups of {g} on a call with "
-                             f"Lq = {Lq}, Lk = {Lk} ({(Lq + g - 1) // g} x {(Lk + g - 1) // g} expected)")
+        g, gk = rule.group, rule.group if rule.k_group is None else rule.k_group
+        if (rule.q_groups, rule.k_groups) != ((Lq + g - 1) // g, (Lk + gk - 1) // gk):
+            raise ValueError(f"interval mask of {rule.q_groups} x {rule.k_groups} groups of {g}{'' if gk == g else f' x {gk}'} on a call "
+                             f"with Lq = {Lq}, Lk = {Lk} ({(Lq + g - 1) // g} x {(Lk + gk - 1) // gk} expected)")
     else:
         return AttnMask("band", (int(window[0]), int(window[1])))
     if device is None:
@@ -267,14 +274,15 @@ def flash_attn_raw(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt
     ``interval_mask``: a ``causal.IntervalMask`` — up to two key intervals per group of query rows
     (omh_flash_attn_fwd_interval_d128, include/omh.h): the short-sequence kernel over the tiles inside each workgroup's
     two ranges, never split; ValueError beside a band, a block mask or ``chunk_causal``.  A mask built with ``runs=3``
-    goes to the three-run entries (omh_flash_attn_fwd_interval3_d128; ``flash_attn_bwd``: ..._bwd_interval3_d128).
+    goes to the three-run entries (omh_flash_attn_fwd_interval3_d128; ``flash_attn_bwd``: ..._bwd_interval3_d128), one
+    built with ``k_group=`` (one group size per axis) to omh_flash_attn_fwd_interval_rect_d128 / ..._bwd_interval_rect_d128.
     ``mask``: the four keywords before it as one ``AttnMask`` a caller resolved already (``attn_mask``); ValueError beside
     any of them.  Without it they are resolved here, first of all (``attn_mask`` lists what it refuses)."""
     mask = _resolved(mask, window, block_mask, chunk_causal, interval_mask, H, Lq, Lk)
     a = AttnArgs(q, k, vt, o, k_lens, B, H, Lq, Lk, q_bs, q_rs, k_bs, k_rs, vt_bs, o_bs, o_rs, ldv, scale, lse,
                  int(q_prescaled), None, 0, o32, int(flags), q_lens, mask.window[0], mask.window[1])
     if mask.rule is not None:
-        m, entry = mask.c_struct(), _MASK_ENTRIES[mask.kind, getattr(mask.rule, "runs", 0)][0]
+        m, entry = mask.c_struct(), _mask_entries(mask)[0]
         check(getattr(lib, entry)(C.byref(a), C.byref(m), _stream()), entry)
         return
     need = lib.omh_flash_attn_workspace_bytes(C.byref(a))          # split-KV tail (long-sequence kernel; short one if allowed)
@@ -414,7 +422,7 @@ def flash_attn_bwd(q, k, v, o, dout, lse, k_lens, B, H, Lq, Lk, scale=None, q_pr
                          float(scale if scale is not None else 128 ** -0.5), int(q_prescaled), bf, _p(o32), int(phase),
                          None, 0)
     if mask.rule is not None:
-        m, entry = mask.c_struct(), _MASK_ENTRIES[mask.kind, getattr(mask.rule, "runs", 0)][1]
+        m, entry = mask.c_struct(), _mask_entries(mask)[1]
         check(getattr(lib, entry)(C.byref(a), _p(q_lens), C.byref(m), _stream()), entry)
         return dq, dk, dv
     if q_lens is not None:

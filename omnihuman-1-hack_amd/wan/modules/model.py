@@ -182,11 +182,15 @@ class _FwdCtx:
                  "rpb", "interval",
                  # cache_pos, cache_hi, cache_mask: forward_chunk on a causal.RollingKVCache (the chunk's slot, the end of
                  # the filled slots, the resolved ops.AttnMask over stale keys of a short last chunk), else None
-                 "cache_pos", "cache_hi", "cache_mask")
+                 "cache_pos", "cache_hi", "cache_mask",
+                 # grids: the (f, h, w) of the samples (host); ctx_mask: the resolved ops.AttnMask every cross-attention runs
+                 # under (frame-aligned condition tokens: WanModel._condition_mask), else None
+                 "grids", "ctx_mask")
 
     def __init__(self):
         self.kv = self.chunk = self.cache = self.cache_layer = self.cache_lo = self.rpb = self.interval = None
         self.cache_pos = self.cache_hi = self.cache_mask = None
+        self.grids = self.ctx_mask = None
 
 
 class ContextState:
@@ -194,8 +198,9 @@ class ContextState:
     block's cross-attention K (normalised) and V^T — computed once by ``WanModel.encode_context`` and accepted by
     ``WanModel.forward`` in place of ``context``.  The reference recomputes these on each of the 100 forwards
     of a 50-step CFG sample (model.py:531-537,176-178,216-220); they do not depend on x or t, so reusing them
-    changes no value."""
-    __slots__ = ("ctx", "ctx_lens", "kv", "B", "model_id", "version")
+    changes no value.  ``cond``: the frames and the window of frame-aligned condition
+    tokens (the normal form of ``extra_conditions``, without the tokens), or None."""
+    __slots__ = ("ctx", "ctx_lens", "kv", "B", "model_id", "version", "cond")
 
 
 # ----------------------------------------------------------------------------
@@ -474,14 +479,18 @@ class WanT2VCrossAttention(WanSelfAttention):
         q = self._query(h, fc)
         kn, vt, L, Lp = self._context_kv(fc)
         o = torch.empty(B * S, d, dtype=torch.bfloat16, device=h.device)
+        # (fc.ctx_mask: frame-aligned condition tokens — the interval kernels with one group size per axis; None: as ever)
         ops.flash_attn_raw(ptr(q), ptr(kn), ptr(vt), ptr(o), ptr(fc.ctx_lens32), B, N, S, L, S * d, d, L * d, d,
-                           d * Lp, S * d, d, Lp, D ** -0.5)
+                           d * Lp, S * d, d, Lp, D ** -0.5, mask=fc.ctx_mask)
         return [o]
 
-    def forward(self, x, context, context_lens, _fc: Optional["_FwdCtx"] = None):
-        """Reference signature (model.py:166): returns [B, L1, C] fp32."""
+    def forward(self, x, context, context_lens, _fc: Optional["_FwdCtx"] = None, interval_mask=None):
+        """Reference signature (model.py:166): returns [B, L1, C] fp32.  ``interval_mask``: a ``causal.IntervalMask`` over
+        (queries, context rows) the attention runs under (a stand-alone call; inside a model the shared state carries it)."""
         B, S, d = x.shape
         fc = _fc or _make_ctx_for_cross(self, x, context, context_lens)
+        if interval_mask is not None:
+            fc.ctx_mask = ops.attn_mask(interval_mask=interval_mask, H=self.num_heads, Lq=S, Lk=fc.Lc, device=x.device)
         h = x.reshape(B * S, d)
         h = h if h.dtype == torch.bfloat16 else ops.cast_bf16(h.float().contiguous())
         outs = self._attend_ctx(h.contiguous(), fc)
@@ -1027,7 +1036,8 @@ class WanModel(nn.Module):
         runs under ``causal.IntervalMask(causal.teacher_forcing_groups(F / fpc, W), fpc h w)``: a clean chunk sees the
         clean chunks up to itself, noisy chunk I the clean chunks before it and itself — what ``forward_chunk`` attends
         to at chunk I (both cut to W chunks back; with ``sink_chunks`` = S > 0 the first S clean chunks stay visible:
-        ``teacher_forcing_groups(F / fpc, W, S)`` and the three-run kernels).  Cross-attention and the FFN are unchanged,
+        ``teacher_forcing_groups(F / fpc, W, S)`` and the three-run kernels).  Cross-attention and the FFN are unchanged
+        (frame-aligned ``extra_conditions``: clean frame f and noisy frame f see the same tokens),
         ``y`` goes to both halves, the head runs on the noisy rows only.  Returns the list of fp32 [C_out, F, H, W] for the
         noisy half.
         ValueError without causal chunks, for a bounded ``window_size``, a block mask or policy, clips of different
@@ -1084,7 +1094,8 @@ class WanModel(nn.Module):
         # clean half's output is cut off here: no gradient enters through it)
         return [o if o.shape[1] == F * pt else o[:, F * pt:] for o in out]
 
-    def forward_chunk(self, x, t, context, cache, frame_offset=None, commit=True, clip_fea=None, y=None, grad=False):
+    def forward_chunk(self, x, t, context, cache, frame_offset=None, commit=True, clip_fea=None, y=None, grad=False,
+                      extra_conditions=None):
         """One chunk of a clip against the keys and values kept from the chunks before it (the rollout of the
         frame-causal model).  ``x``: the latents [C_in, f, H, W] of ONE chunk per sample, all of one shape (the last chunk
         of a clip may have fewer frames); ``cache``: a ``causal.KVCache`` of this model and batch.  Each block projects
@@ -1112,7 +1123,17 @@ class WanModel(nn.Module):
         is a ValueError, as are a ``RollingKVCache`` (its slots are evicted before the backward runs: use ``KVCache``
         with ``left_chunks``), hence ``sink_chunks`` > 0, and a 2-D ``t``.  Without anything that requires grad it is the
         inference call.
+
+        ``extra_conditions``: as in ``forward``.  With ``"frames"`` the frames are clip-absolute, the chunk's queries are
+        the frames from ``frame_offset`` on and nothing behind the chunk's last frame is seen; the tokens no query of the
+        chunk sees are dropped before the embedding, so passing a stream's later tokens or leaving them out is the same
+        computation.  With ``grad=True`` the gradient reaches the tokens.
         Returns the list of fp32 [C_out, f, H, W]."""
+        if isinstance(extra_conditions, dict) and extra_conditions.get("frames") is not None:
+            x = list(x)
+            f = x[0].shape[1] // self.patch_size[0]
+            fo = self._chunk_geometry(x, t, cache, frame_offset)[2]       # (its ValueErrors; nothing touches a device)
+            extra_conditions = self._normal_conditions(extra_conditions, chunk=(fo, f))
         if grad:
             # (the refusals come before anything touches a device)
             if getattr(cache, "rolling", False):
@@ -1130,16 +1151,16 @@ class WanModel(nn.Module):
             raise ops.OmhError("WanModel.forward_chunk runs on the MI355X only (no CPU fallback): move the model "
                                "to a GPU device")
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                        or self._input_requires_grad(x, t, context, clip_fea, y, None)):
+                                        or self._input_requires_grad(x, t, context, clip_fea, y, extra_conditions)):
             if not grad:
                 raise RuntimeError("forward_chunk is an inference path (no gradient flows through the cache): call it "
                                    "under torch.no_grad() with inputs that do not require grad")
             if isinstance(context, ContextState):
                 raise ValueError("a ContextState is an inference-time cache: pass the raw context when training")
             from .model_train import forward_chunk_train
-            return forward_chunk_train(self, list(x), t, context, cache, frame_offset, commit, clip_fea, y)
+            return forward_chunk_train(self, list(x), t, context, cache, frame_offset, commit, clip_fea, y, extra_conditions)
         with torch.no_grad():
-            return self._forward_chunk(list(x), t, context, cache, frame_offset, commit, clip_fea, y)
+            return self._forward_chunk(list(x), t, context, cache, frame_offset, commit, clip_fea, y, extra_conditions)
 
     def _chunk_geometry(self, x, t, cache, frame_offset):
         """The argument rules of ``forward_chunk`` -> (C tokens of the chunk, first visible key lo, frame_offset)."""
@@ -1195,14 +1216,15 @@ class WanModel(nn.Module):
         fc.cache, fc.cache_lo = cache, lo
         fc.cache_pos = fc.cache_hi = fc.cache_mask = None
 
-    def _forward_chunk(self, x, t, context, cache, frame_offset, commit, clip_fea, y):
+    def _forward_chunk(self, x, t, context, cache, frame_offset, commit, clip_fea, y, extra_conditions=None):
         C, lo, frame_offset = self._chunk_geometry(x, t, cache, frame_offset)
         L0 = cache.length
         rolling = getattr(cache, "rolling", False)
         if rolling:
             tpf = (x[0].shape[2] // self.patch_size[1]) * (x[0].shape[3] // self.patch_size[2])
             Ct = self._causal_chunks[0] * tpf
-        xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, C, clip_fea, y)
+        xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, C, clip_fea, y, extra_conditions,
+                                                       chunk=(frame_offset, C // self._tokens_per_frame(x)))
         self._chunk_ctx(fc, cache, lo, frame_offset)
         if rolling:
             # the chunk's slot; the keys are every filled slot.  Before the ring wraps they are [0, L0 + C), KVCache's range;
@@ -1240,7 +1262,19 @@ class WanModel(nn.Module):
         ``extra_conditions`` is the keyword Omnihuman/omnihuman_wan_t2v.py:408-414 passes (the reference model does
         not accept it): a ``[B, Ne, dim]`` tensor of condition tokens in model width, or a dict holding it under
         ``"tokens"``.  They are prepended to the embedded text context (t2v, inference), so every block's
-        cross-attention attends to them — see omnihuman_wan_t2v.OmniHumanWanT2V.condition_tokens."""
+        cross-attention attends to them — see omnihuman_wan_t2v.OmniHumanWanT2V.condition_tokens.
+
+        Frame-aligned condition tokens: the dict may hold ``"frames"``, an int tensor [Ne] shared by the batch — the latent
+        frame of token j on the model's frame grid, or -1 for a token every query sees — and then must hold ``"window"`` =
+        (back, ahead) in latent frames, a side < 0 unbounded.  The queries of latent frame f see the text, the -1 tokens
+        and the tokens of frames f - back .. min(f + ahead, E), E the last frame of f's chunk under
+        ``set_causal_chunks`` (no E otherwise): ``causal.condition_window_visible`` states the rule, every block's
+        cross-attention runs under it as a ``causal.IntervalMask(k_group=1)`` over (latent frames, context rows), built once
+        per call.  The model orders the tokens itself (stable: frame tokens ascending, then the -1 tokens, then the text),
+        and their gradient comes back in the caller's order.  Every clip of the batch must have the same h, w, with
+        h w >= 8.  ValueError (before any device call) for ``"frames"`` of another length or dtype, a missing
+        ``"window"`` and an i2v model.  Without ``"frames"`` nothing changes."""
+        extra_conditions = self._normal_conditions(extra_conditions)
         device = self.patch_embedding.weight.device
         if device.type != "cuda":
             raise ops.OmhError("WanModel.forward runs on the MI355X only (no CPU fallback): move the model "
@@ -1270,7 +1304,84 @@ class WanModel(nn.Module):
             return any(isinstance(u, torch.Tensor) and u.requires_grad for u in v)
         return any(any_of(v) for v in (x, y, context, clip_fea, t, extra_conditions))
 
-    def _embed(self, x, t, context, seq_len, clip_fea, y, extra_conditions=None):
+    def _tokens_per_frame(self, x):
+        return (x[0].shape[2] // self.patch_size[1]) * (x[0].shape[3] // self.patch_size[2])
+
+    def _normal_conditions(self, extra_conditions, chunk=None):
+        """``extra_conditions`` with ``"frames"`` in its normal form: the tokens in the model's order — frame tokens
+        ascending, then the -1 tokens (a stable sort; ``index_select``, so autograd hands the gradient back in the
+        caller's order) —, ``"frames"`` as a tuple of host ints in that order and ``"window"`` = (back, ahead).  ``chunk`` =
+        (frame_offset, frames) of a ``forward_chunk`` call: the tokens no query of the chunk sees are dropped (None when
+        none is left).  Anything without ``"frames"`` is returned as it is.  Checks only: no device is touched but by the
+        ``index_select``."""
+        ec = extra_conditions
+        if not isinstance(ec, dict) or ec.get("frames") is None or ec.get("_normal"):
+            return ec
+        if self.model_type != "t2v":
+            raise ValueError("frame-aligned condition tokens ('frames') are defined for the t2v backbone")
+        tok, frames, window = ec.get("tokens"), ec["frames"], ec.get("window")
+        if not isinstance(tok, torch.Tensor) or tok.dim() != 3:
+            raise ValueError("extra_conditions: 'tokens' [B, Ne, dim] expected beside 'frames'")
+        if not isinstance(frames, torch.Tensor) or frames.is_floating_point() or frames.is_complex() or \
+                frames.dtype == torch.bool or tuple(frames.shape) != (tok.shape[1],):
+            raise ValueError(f"extra_conditions: 'frames' must be an int tensor [Ne = {tok.shape[1]}], got "
+                             f"{getattr(frames, 'dtype', type(frames))} {tuple(getattr(frames, 'shape', ()))}")
+        if window is None or len(window) != 2:
+            raise ValueError("extra_conditions: 'window' = (back, ahead) is required beside 'frames'")
+        back, ahead = int(window[0]), int(window[1])
+        fr = [int(v) for v in frames.tolist()]
+        if any(v < -1 for v in fr):
+            raise ValueError("extra_conditions: 'frames' holds latent frames >= 0, or -1 for a token every query sees")
+        order = sorted(range(len(fr)), key=lambda j: (fr[j] < 0, fr[j]))
+        if chunk is not None:
+            from ... import causal as _causal
+            fo, f = chunk
+            # (one chunk from frame 0 to the chunk's last frame: E = fo + f - 1 for every query)
+            seen = _causal.condition_window_visible(f, torch.tensor([fr[j] for j in order], dtype=torch.int64), 0, back, ahead,
+                                                    frames_per_chunk=fo + f, frame_offset=fo).any(0).tolist()
+            order = [j for j, on in zip(order, seen) if on]
+            if not order:
+                return None
+        if order != list(range(len(fr))):
+            tok = tok.index_select(1, _dev_ints(order, torch.long, tok.device))
+        return {"tokens": tok, "frames": tuple(fr[j] for j in order), "window": (back, ahead), "chunk": chunk, "_normal": True}
+
+    def _condition_mask(self, fc, cond):
+        """The resolved mask of every cross-attention of a forward whose context starts with frame-aligned condition tokens
+        (``cond``: the normal form of ``_normal_conditions``, tokens aside), or None when every query sees every token.
+        Rows: the latent frames of the sequence (both halves under teacher forcing; the chunk's frames in
+        ``forward_chunk``), columns: the rows of the context, one by one."""
+        from ... import causal as _causal
+        frames, (back, ahead), chunk = cond["frames"], cond["window"], cond.get("chunk")
+        hw = {(g[1], g[2]) for g in fc.grids}
+        if len(hw) != 1:
+            raise ValueError(f"frame-aligned condition tokens: the clips of a batch must share h, w, got {sorted(hw)}")
+        tpf = hw.pop()
+        tpf = tpf[0] * tpf[1]
+        if tpf < 8:
+            raise ValueError(f"frame-aligned condition tokens: {tpf} tokens per frame; at least 8 are needed")
+        n_text = fc.Lc - len(frames)
+        cc = getattr(self, "_causal_chunks", None)
+        if chunk is not None:                              # one chunk from frame 0 to the chunk's last frame (see above)
+            q_frames, offset, fpc, segments = chunk[1], chunk[0], chunk[0] + chunk[1], 1
+        elif getattr(self, "_tf_state", None) is not None:
+            q_frames, offset, fpc, segments = fc.S // (2 * tpf), 0, cc[0], 2
+        else:
+            q_frames, offset, fpc, segments = (fc.S + tpf - 1) // tpf, 0, None if cc is None else cc[0], 1
+        device = fc.ctx.device
+        key = (frames, back, ahead, n_text, q_frames, offset, fpc, segments, tpf, fc.S, str(device))
+        masks = self.__dict__.setdefault("_cond_masks", {})
+        if key not in masks:
+            if len(masks) > 64:
+                masks.clear()
+            vis = _causal.condition_window_visible(q_frames, torch.tensor(frames, dtype=torch.int64), n_text, back, ahead,
+                                                   fpc, segments, offset)
+            masks[key] = None if bool(vis.all()) else ops.attn_mask(
+                interval_mask=_causal.IntervalMask(vis, tpf, device, k_group=1), H=self.num_heads, Lq=fc.S, Lk=fc.Lc,
+                device=device)
+        return masks[key]
+
+    def _embed(self, x, t, context, seq_len, clip_fea, y, extra_conditions=None, chunk=None):
         device = self.patch_embedding.weight.device
         d = self.dim
         if y is not None:
@@ -1314,6 +1425,7 @@ class WanModel(nn.Module):
         fc.grid32 = _dev_ints(grids, torch.int32, device)
         fc.rope_cos, fc.rope_sin = self._rope(device)
         fc.seq_lens_host = list(lens)                                       # host copies: no device sync later
+        fc.grids = list(grids)
         fc.chunk = self._causal_rule(grids)
         if fc.chunk is not None and self._causal_sink():                    # a sink: the interval kernels, not the staircase
             fc.chunk, fc.interval = None, self._sink_mask(seq_len, fc.chunk[0], device)
@@ -1321,7 +1433,7 @@ class WanModel(nn.Module):
         if tf is not None:
             fc.chunk, fc.interval = None, tf[0]
             fc.rope_cos, fc.rope_sin = tf[1]
-        ctx_lens = self._attach_context(fc, context, clip_fea, extra_conditions)
+        ctx_lens = self._attach_context(fc, context, clip_fea, extra_conditions, chunk)
         return xs, e, fc, grids, lens, ctx_lens
 
     def _per_frame_t(self, t, grids, seq_len):
@@ -1346,8 +1458,9 @@ class WanModel(nn.Module):
             t = torch.cat([t, t[:, -1:].expand(-1, G - F)], dim=1)
         return t.reshape(-1), tpf
 
-    def _attach_context(self, fc, context, clip_fea=None, extra_conditions=None):
-        """The context-dependent fields of a forward's shared state: text (+ image) embedding, model.py:531-537."""
+    def _attach_context(self, fc, context, clip_fea=None, extra_conditions=None, chunk=None):
+        """The context-dependent fields of a forward's shared state: text (+ image) embedding, model.py:531-537.
+        ``chunk``: (frame_offset, frames) of a ``forward_chunk`` call, for the mask of frame-aligned condition tokens."""
         device = self.patch_embedding.weight.device
         state = context if isinstance(context, ContextState) else None
         if state is not None:
@@ -1357,12 +1470,18 @@ class WanModel(nn.Module):
             ctx, ctx_lens = state.ctx, list(state.ctx_lens)
             if extra_conditions is not None:
                 raise ValueError("pass extra condition tokens to encode_context(), not next to a ContextState")
+            cond = state.cond
         else:
+            extra_conditions = self._normal_conditions(extra_conditions)
             ctx, ctx_lens = self._embed_context(context, clip_fea, extra_conditions)
+            cond = extra_conditions if isinstance(extra_conditions, dict) and extra_conditions.get("_normal") else None
         fc.ctx_lens32 = _dev_ints(ctx_lens, torch.int32, device)
         fc.ctx, fc.Lc = ctx, ctx.shape[1]
         fc.kv = state.kv if state is not None else None
         fc.ctx_lens_host = list(ctx_lens)
+        fc.ctx_mask = None
+        if cond is not None:
+            fc.ctx_mask = self._condition_mask(fc, cond if chunk is None else dict(cond, chunk=chunk))
         return ctx_lens
 
     def _embed_context(self, context, clip_fea=None, extra_tokens=None):
@@ -1417,9 +1536,14 @@ class WanModel(nn.Module):
     def encode_context(self, context, clip_fea=None, extra_conditions=None) -> "ContextState":
         """Pre-compute what depends only on (context, clip_fea, extra_conditions).  Pass the result as ``context`` to
         forward() (inference only); every block adds its cross-attention K / V^T on first use and reuses them
-        afterwards."""
+        afterwards.  Frame-aligned ``extra_conditions`` (``"frames"``, ``"window"``: see ``forward``) stay with the state:
+        every forward it is passed to masks its cross-attention accordingly, ``forward_cfg_pair`` included."""
         st = ContextState()
+        extra_conditions = self._normal_conditions(extra_conditions)
         st.ctx, st.ctx_lens = self._embed_context(context, clip_fea, extra_conditions)
+        st.cond = None
+        if isinstance(extra_conditions, dict) and extra_conditions.get("_normal"):     # frames and window: the mask follows
+            st.cond = {k: v for k, v in extra_conditions.items() if k != "tokens"}     # the geometry of each forward
         st.kv, st.B, st.model_id, st.version = {}, len(context), id(self), self._context_signature()
         return st
 

@@ -821,11 +821,12 @@ def _block_forward(model, blk, idx, st, x0, P, keep, need=True, mask=None):
     kf, kc, vtc, Ltp = ctx_kv(n_img, Lt, P["wkv_c"], ca.k, ca.v, "norm_k", "ca")
     oc = bf(R, d)
     lse_ca = f32(B, N, Sq) if need else None
-    o32_ca = f32(R, d) if (_ATTN_BWD2 and need and not i2v) else None
+    # (fc.ctx_mask: frame-aligned condition tokens — the masked entries, whose backward needs the fp32 output)
+    o32_ca = f32(R, d) if ((_ATTN_BWD2 or fc.ctx_mask is not None) and need and not i2v) else None
     # the reference passes the (text + 257) lengths here (model.py:223,537); keys are clipped to the text rows
     ops.flash_attn_raw(ptr(qc), ptr(kc), ptr(vtc), ptr(oc), ptr(fc.ctx_lens32), B, N, Sq, Lt, Sq * d, d, Lt * d, d,
                        d * Ltp, Sq * d, d, Ltp, D ** -0.5, lse=ptr(lse_ca) if need else None,
-                       o32=ptr(o32_ca) if o32_ca is not None else None, flags=_ATTN_FLAGS)
+                       o32=ptr(o32_ca) if o32_ca is not None else None, flags=_ATTN_FLAGS, mask=fc.ctx_mask)
     x2, _ = resid(x1, oc, P["wo_c"], ca.o.bias.detach(), None, False)
     S.update(h3=h3, qcb=qcb, qc=qc, kf=kf, kc=kc, vtc=vtc, oc=oc, lse_ca=lse_ca, x2=x2, o32_ca=o32_ca)
     if i2v:                                                  # model.py:189-230: extra attention over the 257 image tokens
@@ -1043,7 +1044,7 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
     dkv = bf(Rc, 2 * d)                                               # dk | dv of the text keys, one buffer
     if not i2v:
         _attn_bwd(qc, kc, vc, oc, doc, S["lse_ca"], fc.ctx_lens32, B, N, Sq, Lt, D ** -0.5,
-                  (dqc, dkv[:, :d], dkv[:, d:]), S["o32_ca"], False)
+                  (dqc, dkv[:, :d], dkv[:, d:]), S["o32_ca"], False, mask=fc.ctx_mask)
     else:                                                             # the image-token branch: same q, same dO
         oi, ki = S["oi"], S["ki"]
         if train and "cross_attn.o.weight" in g:
@@ -1468,7 +1469,10 @@ class _EmbedFn(torch.autograd.Function):
             return None if n is None else list(flat[p0].unbind(0)) if n == -1 else list(flat[p0:p0 + cnt])
         x_list, y, context = unpack(0), unpack(1), unpack(2)
         with torch.no_grad():
-            xs, e, fc, grids, lens, ctx_lens = model._embed(x_list, t, context, seq_len, clip_fea, y, extra_tokens)
+            # (st.cond: the frames and the window of frame-aligned condition tokens, in the tokens' order)
+            extra = extra_tokens if extra_tokens is None or getattr(st, "cond", None) is None else dict(st.cond, tokens=extra_tokens)
+            xs, e, fc, grids, lens, ctx_lens = model._embed(x_list, t, context, seq_len, clip_fea, y, extra,
+                                                            chunk=getattr(st, "chunk", None))
             if getattr(st, "after_embed", None) is not None:          # forward_chunk_train: the cache and the shifted RoPE
                 st.after_embed(fc)
         ctx.n_extra = 0 if extra_tokens is None else int(extra_tokens.shape[1])
@@ -1649,6 +1653,8 @@ def forward_train(model, x, t, context, seq_len, clip_fea=None, y=None, extra_co
     named = _embed_params(model)
     eparams = [p for _, p in named]
     tok = extra_conditions.get("tokens") if isinstance(extra_conditions, dict) else extra_conditions
+    if isinstance(extra_conditions, dict) and extra_conditions.get("_normal"):
+        st.cond = {k: v for k, v in extra_conditions.items() if k != "tokens"}
     # the tensor inputs go to the embed node as direct arguments (inside a list autograd would not see them)
     (fx, nx), (fy, ny), (fctx, nc) = _flatten_input(x), _flatten_input(y), _flatten_input(context)
     # does anybody read the context gradient the blocks accumulate (st.d_ctx): the text / image embedding's parameters,
@@ -1690,7 +1696,7 @@ def check_chunk_grad_policy(model):
                          "checkpoint_policy='always' cannot be honoured; set it to 'auto'")
 
 
-def forward_chunk_train(model, x, t, context, cache, frame_offset, commit, clip_fea=None, y=None):
+def forward_chunk_train(model, x, t, context, cache, frame_offset, commit, clip_fea=None, y=None, extra_conditions=None):
     """WanModel.forward_chunk with autograd enabled (``grad=True``): embed node -> blocks -> head node as ``forward_train``,
     each block's self-attention against the cache (WanSelfAttention._attend_cached with its extras).  Several of these
     graphs may await one ``backward()`` (a rollout): each has its own state and kept tensors, they are registered as live
@@ -1705,11 +1711,15 @@ def forward_chunk_train(model, x, t, context, cache, frame_offset, commit, clip_
     model.__dict__.setdefault("_omh_live_states", weakref.WeakSet()).add(st)
 
     st.after_embed = lambda fc: model._chunk_ctx(fc, cache, lo, frame_offset)
+    st.chunk = (frame_offset, C // model._tokens_per_frame(x))
+    tok = extra_conditions.get("tokens") if isinstance(extra_conditions, dict) else extra_conditions
+    if isinstance(extra_conditions, dict) and extra_conditions.get("_normal"):
+        st.cond = {k: v for k, v in extra_conditions.items() if k != "tokens"}
     named = _embed_params(model)
     (fx, nx), (fy, ny), (fctx, nc) = _flatten_input(x), _flatten_input(y), _flatten_input(context)
     st.need_ctx = any(p.requires_grad for n, p in named if n.startswith(("text_embedding.", "img_emb."))) or \
-        any(isinstance(u, torch.Tensor) and u.requires_grad for u in (*fctx, clip_fea))
-    xs = _EmbedFn.apply(model, st, C, (nx, ny, nc), *fx, *fy, *fctx, clip_fea, t, None, *[p for _, p in named])
+        any(isinstance(u, torch.Tensor) and u.requires_grad for u in (*fctx, clip_fea, tok))
+    xs = _EmbedFn.apply(model, st, C, (nx, ny, nc), *fx, *fy, *fctx, clip_fea, t, tok, *[p for _, p in named])
     if not xs.requires_grad:
         xs.requires_grad_(True)
     st.keep = True                                         # always: a re-run would need the cache as it was
