@@ -154,6 +154,10 @@ def _round_up(a, b):
     return (a + b - 1) // b * b
 
 
+LOG2E = 1.4426950408889634        # log2(e): folded into q with softmax_scale, so that the attention kernels take exp2
+N_IMG = 257                       # CLIP image tokens in front of the text in an i2v context (model.py:189-230)
+
+
 _CONST_CACHE = {}
 
 
@@ -201,6 +205,91 @@ class ContextState:
     changes no value.  ``cond``: the frames and the window of frame-aligned condition
     tokens (the normal form of ``extra_conditions``, without the tokens), or None."""
     __slots__ = ("ctx", "ctx_lens", "kv", "B", "model_id", "version", "cond")
+
+
+# ----------------------------------------------------------------------------
+# the block forward, stated once: the steps below and the ``_attend`` / ``_query`` / ``_attend_rows`` methods of the
+# attention modules hold every launch of a WanAttentionBlock's forward; the inference block (WanAttentionBlock.forward)
+# and the training node (model_train._block_forward) are sequences of these calls.  What the backward wants on top
+# (branch outputs, FFN pre-activation, log-sum-exp, fp32 attention output, fp32 pre-norm K) is an optional output of the
+# producing step.
+# ----------------------------------------------------------------------------
+class BlockWeights:
+    """The operands one block's forward reads: bf16 weights [out, in] and fp32 biases — plain attributes, None where a
+    caller has nothing (``_c``: cross-attention, ``_i``: its i2v image branch).  Inference fills it from the ``_Packed``
+    copies (WanAttentionBlock._operands), training with views into its ``TrainPacks`` buffers and the fp32 master biases
+    (model_train._operands); either way it is cached with the copies it points into.  The self-attention projections come
+    as q | k and v, or as ``wqkv`` (the one-launch product of long sequences, inference only): no unused copy is built."""
+    wqk = bqk = wv = bv = wqkv = bqkv = wo = bo = wq_c = bq_c = wk_c = bk_c = wv_c = bv_c = wo_c = bo_c = None
+    wk_i = bk_i = wv_i = bv_i = w1 = b1 = w2 = b2 = n3w = n3b = None
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _vt_fresh(B, d, Lp, L, device):
+    """V^T [B, d, Lp] bf16 for a product that writes columns [0, L): only the pad columns are zeroed (0 x P = 0 needs
+    them finite)."""
+    vt = torch.empty(B, d, Lp, dtype=torch.bfloat16, device=device)
+    if Lp != L:
+        vt[:, :, L:].zero_()
+    return vt
+
+
+def _ln_mod(x, fc, mod, eps, shift_i, scale_i):
+    """bf16 [R, dim] = LN(x) (1 + e[scale_i]) + e[shift_i], e = mod + fc.e0 (mod: the block's fp32 modulation)."""
+    S, d = x.shape[1], x.shape[2]
+    R = x.shape[0] * S
+    h = torch.empty(R, d, dtype=torch.bfloat16, device=x.device)
+    # (rows per row of e0: the sequence, or a frame with a per-frame t)
+    ops.layernorm_modulate_raw(ptr(x), ptr(h), R, d, eps, 1.0, ptr(mod, scale_i * d), ptr(fc.e0, scale_i * d), 6 * d,
+                               ptr(mod, shift_i * d), ptr(fc.e0, shift_i * d), 6 * d, fc.rpb or S)
+    return h
+
+
+def _resid(x, a, w, b, fc, mod=None, gate_i=None, out=None, y=None):
+    """out = x + (a w^T + b) * gate, gate = mod[gate_i] + e0[:, gate_i] (``gate_i`` None: 1); fp32 [B, S, dim].
+    ``out`` None: x is updated in place (the inference block); else written out of place (the training node).
+    ``y``: optional bf16 [R, dim] output, the branch a w^T + b before the gate (the gate's gradient needs it)."""
+    S, d = x.shape[1], x.shape[2]
+    M, K = a.shape
+    kw = dict(c_in=ptr(x) if out is not None and out.data_ptr() != x.data_ptr() else None,
+              aux=ptr(y) if y is not None else None, ldaux=d if y is not None else 0, split_k=fc.split_k)
+    xo = ptr(x if out is None else out)
+    if gate_i is None:
+        ops.gemm_raw(ptr(a), ptr(w), xo, M, d, K, a.stride(0), w.stride(0), d, EPI_RESID,
+                     bias=ptr(b) if b is not None else None,
+                     bias_mode=BIAS_N if b is not None else BIAS_NONE, gate_const=1.0, **kw)
+    else:
+        # (split_k: at one or two [16,1,60,104] clips the FFN-down contraction, K = ffn_dim over 56 / 104 tiles,
+        # runs in slices — ABI v9; nothing is split at the sampling sizes)
+        ops.gemm_raw(ptr(a), ptr(w), xo, M, d, K, a.stride(0), w.stride(0), d, EPI_RESID, bias=ptr(b), bias_mode=BIAS_N,
+                     gate0=ptr(mod, gate_i * d), gate1=ptr(fc.e0, gate_i * d), gate1_stride=6 * d, gate_rows=fc.rpb or S,
+                     gate_const=0.0, **kw)
+    return x if out is None else out
+
+
+def _cross_input(x, W, eps):
+    """bf16 [R, dim] input of the cross-attention: norm3(x) (``W.n3w`` / ``W.n3b``, cross_attn_norm) or the plain cast."""
+    d = x.shape[2]
+    R = x.shape[0] * x.shape[1]
+    h = torch.empty(R, d, dtype=torch.bfloat16, device=x.device)
+    if W.n3w is not None:
+        ops.layernorm_modulate_raw(ptr(x), ptr(h), R, d, eps, 0.0, ptr(W.n3w), None, 0, ptr(W.n3b), None, 0, R)
+    else:
+        ops.cast_bf16(x.view(R, d), out=h)
+    return h
+
+
+def _ffn_up(h, W, pre=False):
+    """bf16 [R, ffn_dim] = gelu(h W1^T + b1).  ``pre``: also the pre-activation (GELU'), an optional output: (u, pre)."""
+    R, d = h.shape
+    f = W.w1.shape[0]
+    u = torch.empty(R, f, dtype=torch.bfloat16, device=h.device)
+    u_pre = torch.empty_like(u) if pre else None
+    ops.gemm_raw(ptr(h), ptr(W.w1), ptr(u), R, f, d, d, d, f, EPI_GELU_BF16, bias=ptr(W.b1), bias_mode=BIAS_N,
+                 aux=ptr(u_pre) if pre else None, ldaux=f if pre else 0)
+    return (u, u_pre) if pre else u
 
 
 # ----------------------------------------------------------------------------
@@ -303,52 +392,70 @@ class WanSelfAttention(nn.Module):
         m = getattr(self, name)
         return m.weight.detach() if isinstance(m, WanRMSNorm) else None
 
-    def _attend(self, h, fc: "_FwdCtx"):
-        """h bf16 [B*S, dim] -> attention output bf16 [B*S, dim] (before o-proj)."""
+    def _takes_fused(self, S):
+        """Does a sequence of S rows per clip take q | k | v as ONE product per clip over the concatenated weights
+        (ABI v10)?  h is read once and the V third leaves the kernel transposed (V^T [dim, Sp], what the attention kernel reads); the
+        same bits as the two products, which short sequences / batches keep (their rows fill the chip only together).
+        (tried at S = 1 560 in round 5: one launch instead of two is the same 19.7 ms per single-frame forward, and the
+        batched CFG pair gets slower, 14.8 -> 15.4 ms: one launch per clip against two over both clips)
+        (the library takes the one-launch form only when the q|k part is whole 384-column tiles: true at dim 1 536, not
+        at dim 5 120, where asking for it would cost B launches and a third weight copy for nothing — ADVICE round 5)"""
+        return S >= 8192 and S % 8 == 0 and (2 * self.dim) % 384 == 0
+
+    def _operands(self, fused=False, W=None):
+        """This layer's part of a ``BlockWeights``: q | k | v in one piece for the one-launch product (``fused``),
+        else q | k and v; the o projection."""
+        W = BlockWeights() if W is None else W
+        if fused:
+            W.wqkv, W.bqkv = self._w_qkv()
+        else:
+            (W.wqk, W.bqk), (W.wv, W.bv) = self._w_qk(), self._w("v")
+        W.wo, W.bo = self._w("o")
+        return W
+
+    def _attend(self, h, fc: "_FwdCtx", W, extras=False, lse=False, o32=False, flags=0, vt_alloc=_vt_fresh, mask=None):
+        """h bf16 [B*S, dim] -> attention output bf16 [B*S, dim] (before o-proj).  ``W``: a ``BlockWeights``.
+        ``lse`` (fp32 [B, heads, S]) and ``o32`` (fp32 [B*S, dim], the output before its rounding): optional outputs;
+        ``flags``: ops.flash_attn_raw's (the training node pins the short-sequence kernel); ``vt_alloc``: where V^T comes
+        from; ``mask``: the resolved mask of an earlier call on the same input (a checkpoint re-run), else resolved here.
+        The one-launch q | k | v product and the bounded long-sequence stream need ``flags == 0`` and no ``extras``.
+        Returns o; with ``extras`` (o, qk, q, k, vt, mask, lse, o32) — what the backward reads."""
         if fc.cache is not None:
-            (wqk, bqk), (wv, bv) = self._w_qk(), self._w("v")
-            return self._attend_cached(h, fc, ptr(wqk), ptr(bqk), ptr(wv), ptr(bv))
+            return self._attend_cached(h, fc, W, extras)
         B, S, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
         R = B * S
-        mask = self._call_mask(fc, h.device)               # None: a block policy, which chooses below
+        if mask is None:
+            mask = self._call_mask(fc, h.device)           # None: a block policy, which chooses below
         # q|k projection kept in bf16 (fp32 accumulate): the normalisation statistics are taken in fp32 from
         # it; measured effect on the 30-layer output < 1e-3 relative RMS, and it halves this step's traffic
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
         Sp = _round_up(S, 64)
-        vt = torch.empty(B, d, Sp, dtype=torch.bfloat16, device=h.device)
-        if Sp != S:
-            vt[:, :, S:].zero_()                       # pad columns only (0 x P = 0 needs them finite); the GEMM writes the rest
-        # long sequences: q | k | v as ONE product per clip over the concatenated weights (ABI v10) — h is read once,
-        # the V third leaves the kernel transposed (V^T [dim, Sp], what the attention kernel reads); the same bits as the
-        # two products below, which short sequences / batches keep (their rows fill the chip only together)
-        # (tried at S = 1 560 in round 5: one launch instead of two is the same 19.7 ms per single-frame forward, and the
-        # batched CFG pair gets slower, 14.8 -> 15.4 ms: one launch per clip against two over both clips)
-        # (the library takes the one-launch form only when the q|k part is whole 384-column tiles: true at dim 1 536, not
-        # at dim 5 120, where asking for it would cost B launches and a third weight copy for nothing — ADVICE round 5)
-        fused = S >= 8192 and S % 8 == 0 and (2 * d) % 384 == 0
+        fused = W.wqkv is not None and flags == 0 and not extras          # (see _takes_fused)
+        assert fused or W.wqk is not None, "a q | k | v record serves only a call without flags and extras"
         if fused:
-            wqkv, bqkv = self._w_qkv()
+            vt = vt_alloc(B, d, Sp, S, h.device)           # (pad columns zero; the GEMM writes the rest)
             for b in range(B):                         # one launch per clip: V^T is [B, dim, Sp], a clip's rows fill the chip
-                ops.gemm_raw(ptr(h, b * S * d), ptr(wqkv), ptr(qk, b * S * 2 * d), S, 3 * d, d, d, d, 2 * d,
-                             EPI_BF16_SPLIT_T, bias=ptr(bqkv), bias_mode=BIAS_N, aux=ptr(vt, b * d * Sp), ldaux=Sp,
+                ops.gemm_raw(ptr(h, b * S * d), ptr(W.wqkv), ptr(qk, b * S * 2 * d), S, 3 * d, d, d, d, 2 * d,
+                             EPI_BF16_SPLIT_T, bias=ptr(W.bqkv), bias_mode=BIAS_N, aux=ptr(vt, b * d * Sp), ldaux=Sp,
                              n_split=2 * d)
         else:
-            wqk, bqk = self._w_qk()
-            ops.gemm_raw(ptr(h), ptr(wqk), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(bqk), bias_mode=BIAS_N)
+            ops.gemm_raw(ptr(h), ptr(W.wqk), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(W.bqk),
+                         bias_mode=BIAS_N)
         q = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         k = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         # q leaves the norm kernel already multiplied by softmax_scale * log2(e) (attention.py:96-127), in fp32
         # before its one rounding to bf16: the attention kernel's exponentials then need no per-score multiply
-        q_scale = D ** -0.5 * 1.4426950408889634
+        q_scale = D ** -0.5 * LOG2E
         wq, wk = self._norm_w("norm_q"), self._norm_w("norm_k")          # q and k: one launch (two column segments)
         # where the long-sequence attention stream runs, the norm kernel also emits max |q|^2, |k|^2 per (sample, head): the
         # stream then needs no running max (a bound on this call's scores: ops.flash_attn_raw, qk_norm2_max)
         nmax = None
-        # (a block, staircase or interval mask runs the short-sequence kernel: no long-sequence stream, so no bound either)
-        if mask is not None and mask.rule is None and D == 128 and d <= 5120 and \
-                ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, mask.window):
-            nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
-        self.last_qk_norm2_max = nmax                                    # (read by tools/attn_bound_values.py)
+        if flags == 0 and not extras:
+            # (a block, staircase or interval mask runs the short-sequence kernel: no long-sequence stream, no bound)
+            if mask is not None and mask.rule is None and D == 128 and d <= 5120 and \
+                    ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, mask.window):
+                nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
+            self.last_qk_norm2_max = nmax                                # (read by tools/attn_bound_values.py)
         norm_args = (ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(wq) if wq is not None else None,
                      ptr(wk) if wk is not None else None, self.eps, int(self.qk_norm), ptr(fc.rope_cos), ptr(fc.rope_sin),
                      fc.rope_cos.shape[0], D, ptr(fc.grid32), S)
@@ -356,26 +463,30 @@ class WanSelfAttention(nn.Module):
             ops.rmsnorm_rope_bf16_pair_bound_raw(*norm_args, ptr(nmax), out_scale0=q_scale, out_scale1=1.0)
         else:
             ops.rmsnorm_rope_bf16_pair_raw(*norm_args, out_scale0=q_scale, out_scale1=1.0)
-        del qk
+        if not extras:
+            del qk
         if mask is None:                               # the mask is chosen from the q and k this call attends with
             mask = self._call_mask(fc, h.device, self._dynamic_mask(q, k, B, S, fc.seq_lens32))
         if not fused:
             # V^T[b] = Wv h_b^T + bv  ->  [B, dim, Sp]   (pad columns stay zero)
-            wv, bv = self._w("v")
-            ops.gemm_raw(ptr(wv), ptr(h), ptr(vt), d, S, d, d, d, Sp, EPI_BF16, bias=ptr(bv), bias_mode=BIAS_M, batch=B,
+            vt = vt_alloc(B, d, Sp, S, h.device)
+            ops.gemm_raw(ptr(W.wv), ptr(h), ptr(vt), d, S, d, d, d, Sp, EPI_BF16, bias=ptr(W.bv), bias_mode=BIAS_M,
+                         batch=B,
                          strideA=0, strideB=S * d, strideC=d * Sp)
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
+        lse = torch.empty(B, N, S, dtype=torch.float32, device=h.device) if lse else None
+        o32 = torch.empty(R, d, dtype=torch.float32, device=h.device) if o32 else None
         # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
         ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
-                           d * Sp, S * d, d, Sp, D ** -0.5, q_prescaled=1,
+                           d * Sp, S * d, d, Sp, D ** -0.5, lse=ptr(lse) if lse is not None else None, q_prescaled=1,
+                           o32=ptr(o32) if o32 is not None else None, flags=flags,
                            qk_norm2_max=ptr(nmax) if nmax is not None else None, mask=mask)
-        return o
+        return (o, qk, q, k, vt, mask, lse, o32) if extras else o
 
-    def _attend_cached(self, h, fc: "_FwdCtx", wqk, bqk, wv, bv, extras=False):
+    def _attend_cached(self, h, fc: "_FwdCtx", W, extras=False):
         """``_attend`` for WanModel.forward_chunk: h holds the rows of ONE chunk per sample.  q, k, v are projected for
-        these rows only (``wqk`` / ``bqk``, ``wv`` / ``bv``: pointers to the q | k and the v weights and biases the caller
-        uses); k (normalised, rotated) lands in rows [length, length + C) of this layer's cache and V^T in the
-        same columns, straight from the V^T product (ldc = the cache pitch); plain attention then runs with Lq = C over the
+        these rows only (``W``: the caller's ``BlockWeights``, its two-product form); k (normalised, rotated) lands in
+        rows [length, length + C) of this layer's cache and V^T in the same columns, straight from the V^T product (ldc = the cache pitch); plain attention then runs with Lq = C over the
         keys [lo, length + C) of the cache — a pointer offset, no copy.  The launches of ``_attend`` at seq_len = C
         otherwise, so on an empty cache the result has its bits.
         A ``causal.RollingKVCache``: the chunk's rows go to ``fc.cache_pos`` (its slot) and the keys are [0, fc.cache_hi) —
@@ -395,7 +506,7 @@ class WanSelfAttention(nn.Module):
             L0, hi = fc.cache_pos, fc.cache_hi             # (L0: where this chunk's rows go)
         R = B * C
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
-        ops.gemm_raw(ptr(h), wqk, ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=bqk, bias_mode=BIAS_N)
+        ops.gemm_raw(ptr(h), ptr(W.wqk), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(W.bqk), bias_mode=BIAS_N)
         q = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         wq, wk = self._norm_w("norm_q"), self._norm_w("norm_k")
         for b in range(B):                                 # one launch per sample: its k rows sit at their own place in the cache
@@ -403,8 +514,9 @@ class WanSelfAttention(nn.Module):
                                            ptr(wq) if wq is not None else None, ptr(wk) if wk is not None else None,
                                            self.eps, int(self.qk_norm), ptr(fc.rope_cos), ptr(fc.rope_sin),
                                            fc.rope_cos.shape[0], D, ptr(fc.grid32, 3 * b), C,
-                                           out_scale0=D ** -0.5 * 1.4426950408889634, out_scale1=1.0)
-        ops.gemm_raw(wv, ptr(h), ptr(vtc, L0), d, C, d, d, d, pitch, EPI_BF16, bias=bv, bias_mode=BIAS_M, batch=B,
+                                           out_scale0=D ** -0.5 * LOG2E, out_scale1=1.0)
+        ops.gemm_raw(ptr(W.wv), ptr(h), ptr(vtc, L0), d, C, d, d, d, pitch, EPI_BF16, bias=ptr(W.bv), bias_mode=BIAS_M,
+                     batch=B,
                      strideA=0, strideB=C * d, strideC=d * pitch)
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         lse = torch.empty(B, N, C, dtype=torch.float32, device=h.device) if extras else None
@@ -429,60 +541,86 @@ class WanSelfAttention(nn.Module):
         fc = _fc or _make_ctx_for_attention(self, x, seq_lens, grid_sizes, freqs)
         h = x.reshape(B * S, d)
         h = h if h.dtype == torch.bfloat16 else ops.cast_bf16(h.float().contiguous())
-        o = self._attend(h.contiguous(), fc)
-        wo, bo = self._w("o")
-        return ops.gemm(o, wo, bias=bo, epilogue=EPI_F32).view(B, S, d)
+        W = self._operands(fc.cache is None and self._takes_fused(S))
+        o = self._attend(h.contiguous(), fc, W)
+        return ops.gemm(o, W.wo, bias=W.bo, epilogue=EPI_F32).view(B, S, d)
 
 
 class WanT2VCrossAttention(WanSelfAttention):
     """model.py:164-186."""
 
-    def _context_kv(self, fc: "_FwdCtx", kname="k", vname="v", nname="norm_k", lo=0, hi=None):
-        """K (normalised, bf16 [B*L, dim]) and V^T ([B, dim, Lp]) of context rows [lo, hi)."""
+    n_img = 0                                          # context rows in front of the text (the i2v image tokens)
+
+    def _operands(self, W=None):
+        """This layer's part of a ``BlockWeights``."""
+        W = BlockWeights() if W is None else W
+        (W.wq_c, W.bq_c), (W.wk_c, W.bk_c), (W.wv_c, W.bv_c), (W.wo_c, W.bo_c) = (self._w(n) for n in "qkvo")
+        return W
+
+    def _context_kv(self, fc: "_FwdCtx", W, img=False, extras=False, vt_alloc=None):
+        """K (normalised, bf16 [B*L, dim]) and V^T ([B, dim, Lp]) of the text rows of the context (``img``: of its
+        N_IMG image rows): (kn, vt, L, Lp), kept in ``fc.kv`` (a ContextState's cache).  ``vt_alloc``: where V^T comes
+        from (``_vt_fresh``'s signature; None: a zeroed tensor).  With ``extras`` (kn, vt, L, Lp, kf): the fp32 K before
+        its norm on top."""
+        if img:
+            wk, bk, wv, bv, nname, key, lo, hi = W.wk_i, W.bk_i, W.wv_i, W.bv_i, "norm_k_img", "k_img", 0, N_IMG
+        else:
+            wk, bk, wv, bv, nname, key, lo, hi = W.wk_c, W.bk_c, W.wv_c, W.bv_c, "norm_k", "k", self.n_img, fc.Lc
         kv = fc.kv
-        if kv is not None and (id(self), kname) in kv:
-            return kv[(id(self), kname)]
+        if kv is not None and not extras and (id(self), key) in kv:
+            return kv[(id(self), key)]
         B, d = fc.B, self.dim
         ctx = fc.ctx                                    # bf16 [B, Lc, dim]
-        hi = fc.Lc if hi is None else hi
         L = hi - lo
         Lp = _round_up(L, 64)
-        wk, bk = self._w(kname)
-        wv, bv = self._w(vname)
         kf = torch.empty(B, L, d, dtype=torch.float32, device=ctx.device)
         ops.gemm_raw(ptr(ctx, lo * d), ptr(wk), ptr(kf), L, d, d, d, d, d, EPI_F32, bias=ptr(bk), bias_mode=BIAS_N,
                      batch=B, strideA=fc.Lc * d, strideB=0, strideC=L * d)
-        nw = self._norm_w(nname)
-        kn = ops.rmsnorm_rope(kf.view(B * L, d), nw, self.eps, do_norm=self.qk_norm)
-        vt = torch.zeros(B, d, Lp, dtype=torch.bfloat16, device=ctx.device)
+        kn = ops.rmsnorm_rope(kf.view(B * L, d), self._norm_w(nname), self.eps, do_norm=self.qk_norm)
+        if vt_alloc is None:
+            vt = torch.zeros(B, d, Lp, dtype=torch.bfloat16, device=ctx.device)
+        else:
+            vt = vt_alloc(B, d, Lp, L, ctx.device)
         ops.gemm_raw(ptr(wv), ptr(ctx, lo * d), ptr(vt), d, L, d, d, d, Lp, EPI_BF16, bias=ptr(bv), bias_mode=BIAS_M,
                      batch=B, strideA=0, strideB=fc.Lc * d, strideC=d * Lp)
         if kv is not None:
-            kv[(id(self), kname)] = (kn, vt, L, Lp)
-        return kn, vt, L, Lp
+            kv[(id(self), key)] = (kn, vt, L, Lp)
+        return (kn, vt, L, Lp, kf) if extras else (kn, vt, L, Lp)
 
-    def _query(self, h, fc):
+    def _query(self, h, fc, W, extras=False):
+        """The normalised query bf16 [R, dim]; with ``extras`` (q, its pre-norm projection)."""
         R, d = h.shape
-        wq, bq = self._w("q")
         # as the self-attention's q|k: the projection leaves the GEMM in bf16 (fp32 accumulate), the norm takes its
         # statistics in fp32 from it — half the traffic of an fp32 q between the two kernels
-        qb = ops.gemm(h, wq, bias=bq, epilogue=EPI_BF16)
+        qb = ops.gemm(h, W.wq_c, bias=W.bq_c, epilogue=EPI_BF16)
         q = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         w = self._norm_w("norm_q")
         ops.rmsnorm_rope_bf16_raw(ptr(qb), d, ptr(q), R, d, ptr(w) if w is not None else None, self.eps,
                                   int(self.qk_norm), None, None, 0, self.head_dim, None, fc.S)
-        return q
+        return (q, qb) if extras else q
 
-    def _attend_ctx(self, h, fc: "_FwdCtx"):
-        """Returns the list of attention outputs (bf16 [B*S, dim]) whose sum feeds the o-projection."""
+    def _attend_rows(self, q, fc, W, img=False, extras=False, lse=False, o32=False, flags=0, vt_alloc=None):
+        """Attention of q over the text rows of the context (``img``: over its image rows): bf16 [B*S, dim].
+        ``lse`` / ``o32`` / ``flags``: as in ``WanSelfAttention._attend``.  With ``extras`` (o, kf, kn, vt, lse, o32)."""
         B, S, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
-        q = self._query(h, fc)
-        kn, vt, L, Lp = self._context_kv(fc)
-        o = torch.empty(B * S, d, dtype=torch.bfloat16, device=h.device)
-        # (fc.ctx_mask: frame-aligned condition tokens — the interval kernels with one group size per axis; None: as ever)
-        ops.flash_attn_raw(ptr(q), ptr(kn), ptr(vt), ptr(o), ptr(fc.ctx_lens32), B, N, S, L, S * d, d, L * d, d,
-                           d * Lp, S * d, d, Lp, D ** -0.5, mask=fc.ctx_mask)
-        return [o]
+        kn, vt, L, Lp, *kf = self._context_kv(fc, W, img, extras, vt_alloc)
+        o = torch.empty(B * S, d, dtype=torch.bfloat16, device=q.device)
+        lse = torch.empty(B, N, S, dtype=torch.float32, device=q.device) if lse else None
+        o32 = torch.empty(B * S, d, dtype=torch.float32, device=q.device) if o32 else None
+        # text rows: under fc.ctx_mask (frame-aligned condition tokens — the interval kernels with one group size per
+        # axis; None: as ever) and the context lengths — for i2v the reference passes the (text + 257) lengths here
+        # (model.py:223,537); keys are clipped to the text rows.  Image rows: every one of them, no lengths, no mask
+        ops.flash_attn_raw(ptr(q), ptr(kn), ptr(vt), ptr(o), None if img else ptr(fc.ctx_lens32), B, N, S, L, S * d, d,
+                           L * d, d, d * Lp, S * d, d, Lp, D ** -0.5, lse=ptr(lse) if lse is not None else None,
+                           o32=ptr(o32) if o32 is not None else None, flags=flags,
+                           mask=None if img else fc.ctx_mask)
+        return (o, kf[0], kn, vt, lse, o32) if extras else o
+
+    def _attend_ctx(self, h, fc: "_FwdCtx", W):
+        """Returns the list of attention outputs (bf16 [B*S, dim]) whose sum feeds the o-projection: over the text,
+        and for i2v over the image tokens too."""
+        q = self._query(h, fc, W)
+        return [self._attend_rows(q, fc, W, img) for img in ((False, True) if self.n_img else (False,))]
 
     def forward(self, x, context, context_lens, _fc: Optional["_FwdCtx"] = None, interval_mask=None):
         """Reference signature (model.py:166): returns [B, L1, C] fp32.  ``interval_mask``: a ``causal.IntervalMask`` over
@@ -493,16 +631,16 @@ class WanT2VCrossAttention(WanSelfAttention):
             fc.ctx_mask = ops.attn_mask(interval_mask=interval_mask, H=self.num_heads, Lq=S, Lk=fc.Lc, device=x.device)
         h = x.reshape(B * S, d)
         h = h if h.dtype == torch.bfloat16 else ops.cast_bf16(h.float().contiguous())
-        outs = self._attend_ctx(h.contiguous(), fc)
-        wo, bo = self._w("o")
-        y = ops.gemm(outs[0], wo, bias=bo, epilogue=EPI_F32)
+        W = self._operands()
+        outs = self._attend_ctx(h.contiguous(), fc, W)
+        y = ops.gemm(outs[0], W.wo_c, bias=W.bo_c, epilogue=EPI_F32)
         for extra in outs[1:]:
-            ops.gemm(extra, wo, out=y, epilogue=ops.EPI_F32_ACCUM)
+            ops.gemm(extra, W.wo_c, out=y, epilogue=ops.EPI_F32_ACCUM)
         return y.view(B, S, d)
 
 
 class WanI2VCrossAttention(WanT2VCrossAttention):
-    """model.py:189-230 — extra attention over the first 257 (CLIP image) context tokens."""
+    """model.py:189-230 — extra attention over the first N_IMG (CLIP image) context tokens."""
 
     def __init__(self, dim, num_heads, window_size=(-1, -1), qk_norm=True, eps=1e-6):
         super().__init__(dim, num_heads, window_size, qk_norm, eps)
@@ -510,20 +648,12 @@ class WanI2VCrossAttention(WanT2VCrossAttention):
         self.v_img = nn.Linear(dim, dim)
         self.norm_k_img = WanRMSNorm(dim, eps=eps) if qk_norm else nn.Identity()
 
-    def _attend_ctx(self, h, fc):
-        B, S, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
-        n_img = 257
-        q = self._query(h, fc)
-        ki, vti, Li, Lip = self._context_kv(fc, "k_img", "v_img", "norm_k_img", 0, n_img)
-        kt, vtt, Lt, Ltp = self._context_kv(fc, "k", "v", "norm_k", n_img, fc.Lc)
-        o_img = torch.empty(B * S, d, dtype=torch.bfloat16, device=h.device)
-        ops.flash_attn_raw(ptr(q), ptr(ki), ptr(vti), ptr(o_img), None, B, N, S, Li, S * d, d, Li * d, d, d * Lip,
-                           S * d, d, Lip, D ** -0.5)
-        o = torch.empty(B * S, d, dtype=torch.bfloat16, device=h.device)
-        # the reference passes the (text + 257) lengths here (model.py:223,537); keys are clipped to the text rows
-        ops.flash_attn_raw(ptr(q), ptr(kt), ptr(vtt), ptr(o), ptr(fc.ctx_lens32), B, N, S, Lt, S * d, d, Lt * d, d,
-                           d * Ltp, S * d, d, Ltp, D ** -0.5)
-        return [o, o_img]
+    n_img = N_IMG
+
+    def _operands(self, W=None):
+        W = super()._operands(W)
+        (W.wk_i, W.bk_i), (W.wv_i, W.bv_i) = self._w("k_img"), self._w("v_img")
+        return W
 
 
 WAN_CROSSATTENTION_CLASSES = {"t2v_cross_attn": WanT2VCrossAttention, "i2v_cross_attn": WanI2VCrossAttention}
@@ -551,73 +681,57 @@ class WanAttentionBlock(nn.Module):
         return self._packed.get(f"ffn{i}", (lin.weight, lin.bias),
                                 lambda: (_weight_bf16(lin), lin.bias.detach().float().contiguous()), _lora_sig(lin))
 
+    def _operands(self, fused=False):
+        """The ``BlockWeights`` of this block from the ``_Packed`` copies (``fused``: WanSelfAttention._operands), rebuilt
+        when a parameter or an adapter behind it changed."""
+        sa, ca = self.self_attn, self.cross_attn
+        lins = [sa.q, sa.k, sa.v, sa.o, ca.q, ca.k, ca.v, ca.o, self.ffn[0], self.ffn[2]]
+        if ca.n_img:
+            lins += [ca.k_img, ca.v_img]
+        params = [p for lin in lins for p in (lin.weight, lin.bias)]
+        if self.cross_attn_norm:
+            params += [self.norm3.weight, self.norm3.bias]
+
+        def build():
+            W = ca._operands(sa._operands(fused))
+            (W.w1, W.b1), (W.w2, W.b2) = self._ffn_w(0), self._ffn_w(2)
+            if self.cross_attn_norm:
+                W.n3w, W.n3b = self.norm3.weight.detach().float(), self.norm3.bias.detach().float()
+            return W
+        return self._packed.get(("W", fused), params, build, _lora_sig(*lins))
+
     def forward(self, x, e, seq_lens, grid_sizes, freqs, context, context_lens, block_idx=0,
                 _fc: Optional["_FwdCtx"] = None, _part: str = "all"):
         """x fp32 [B, L, C] residual stream (updated and returned), e fp32 [B, 6, C].
-        ``_part`` (WanModel.forward_cfg_pair): "self" = the self-attention sub-layer only, "rest" = what follows it."""
+        ``_part`` (WanModel.forward_cfg_pair): "self" = the self-attention sub-layer only, "rest" = what follows it.
+        The launches are the steps above (the training node's too: model_train._block_forward), here in place on x."""
         assert e.dtype == torch.float32
-        B, S, d = x.shape
         fc = _fc or _make_ctx_for_block(self, x, e, seq_lens, grid_sizes, freqs, context, context_lens)
-        R = B * S
         if not (x.dtype == torch.float32 and x.is_contiguous()):
             x = x.float().contiguous()
         mod = self.modulation.detach()
         if mod.dtype != torch.float32:
             mod = mod.float()
-        e0 = fc.e0
-        xp, six_d = ptr(x), 6 * d
-        rpb = fc.rpb or S                                  # rows per row of e0: the sequence, or a frame (per-frame t)
-
-        def ln_mod(shift_i, scale_i):
-            h = torch.empty(R, d, dtype=torch.bfloat16, device=x.device)
-            ops.layernorm_modulate_raw(xp, ptr(h), R, d, self.eps, 1.0, ptr(mod, scale_i * d), ptr(e0, scale_i * d),
-                                       six_d, ptr(mod, shift_i * d), ptr(e0, shift_i * d), six_d, rpb)
-            return h
-
-        def resid(a, w, b, gate_i=None):
-            # x += (a w^T + b) * gate   (gate = modulation[gate_i] + e0[:, gate_i], or 1)
-            M, K = a.shape
-            if gate_i is None:
-                ops.gemm_raw(ptr(a), ptr(w), xp, M, d, K, K, K, d, EPI_RESID, bias=ptr(b) if b is not None else None,
-                             bias_mode=BIAS_N if b is not None else BIAS_NONE, gate_const=1.0, split_k=fc.split_k)
-            else:
-                # (split_k: at one or two [16,1,60,104] clips the FFN-down contraction, K = ffn_dim over 56 / 104 tiles,
-                # runs in slices — ABI v9; nothing is split at the sampling sizes)
-                ops.gemm_raw(ptr(a), ptr(w), xp, M, d, K, K, K, d, EPI_RESID, bias=ptr(b), bias_mode=BIAS_N,
-                             gate0=ptr(mod, gate_i * d), gate1=ptr(e0, gate_i * d), gate1_stride=six_d, gate_rows=rpb,
-                             gate_const=0.0, split_k=fc.split_k)
-
+        sa, ca = self.self_attn, self.cross_attn
+        W = self._operands(fc.cache is None and sa._takes_fused(x.shape[1]))
         # ---- self-attention: x += o(attn(LN(x)(1+e1)+e0)) * e2        model.py:292-296
         if _part != "rest":
-            h = ln_mod(0, 1)
-            o = self.self_attn._attend(h, fc)
-            wo, bo = self.self_attn._w("o")
-            resid(o, wo, bo, 2)
+            h = _ln_mod(x, fc, mod, self.eps, 0, 1)
+            o = sa._attend(h, fc, W)
+            _resid(x, o, W.wo, W.bo, fc, mod, 2)
             del h, o
             if _part == "self":
                 return x
         # ---- cross-attention: x += o(attn(norm3(x), context))          model.py:313
-        h = torch.empty(R, d, dtype=torch.bfloat16, device=x.device)
-        if self.cross_attn_norm:
-            n3 = self.norm3
-            ops.layernorm_modulate_raw(xp, ptr(h), R, d, n3.eps, 0.0, ptr(n3.weight.detach().float()), None, 0,
-                                       ptr(n3.bias.detach().float()), None, 0, R)
-        else:
-            ops.cast_bf16(x.view(R, d), out=h)
-        outs = self.cross_attn._attend_ctx(h, fc)
-        wo, bo = self.cross_attn._w("o")
-        resid(outs[0], wo, bo)
+        h = _cross_input(x, W, getattr(self.norm3, "eps", self.eps))
+        outs = ca._attend_ctx(h, fc, W)
+        _resid(x, outs[0], W.wo_c, W.bo_c, fc)
         for extra in outs[1:]:
-            resid(extra, wo, None)
+            _resid(x, extra, W.wo_c, None, fc)
         del h, outs
         # ---- FFN: x += (W2 gelu(W1 (LN(x)(1+e4)+e3) + b1) + b2) * e5    model.py:314-328
-        h = ln_mod(3, 4)
-        w1, b1 = self._ffn_w(0)
-        w2, b2 = self._ffn_w(2)
-        u = torch.empty(R, self.ffn_dim, dtype=torch.bfloat16, device=x.device)
-        ops.gemm_raw(ptr(h), ptr(w1), ptr(u), R, self.ffn_dim, d, d, d, self.ffn_dim, EPI_GELU_BF16, bias=ptr(b1),
-                     bias_mode=BIAS_N)
-        resid(u, w2, b2, 5)
+        u = _ffn_up(_ln_mod(x, fc, mod, self.eps, 3, 4), W)
+        _resid(x, u, W.w2, W.b2, fc, mod, 5)
         return x
 
     def cross_attn_ffn(self, x, context, context_lens, e, block_idx):  # pragma: no cover - API parity

@@ -9,14 +9,16 @@ parallel.BucketedGradAllReduce) still overlaps its all-reduce with the
 backward: each block's parameter gradients become ready when that block's
 node finishes.
 
-A block node's forward is ``_block_forward``: the kernels and epilogues of the
-inference block (model.py:279-330 on libomh.so; same operands, same roundings,
-bit-identical output wherever the inference path takes the same attention kernel: the training forward — kept
-activations, the forward under use_checkpoint and its re-run alike — pins the short-sequence kernel
-(OMH_ATTN_SHORT_KERNEL), the inference path switches to the long-sequence stream from 512 query tiles
-on, e.g. 16 clips x 1560 tokens), with the residual stream written out of place and the
-few extra tensors the backward needs emitted by the producing kernels' epilogues
-(the branch outputs y = o W^T + b for the gate gradients, the FFN pre-activation
+A block node's forward is ``_block_forward``: a sequence of the block-forward steps of model.py (``_ln_mod``,
+``_resid``, ``WanSelfAttention._attend`` / ``_attend_cached``, ``_cross_input``, the cross-attention's ``_query`` /
+``_context_kv`` / ``_attend_rows``, ``_ffn_up``) — the ONE statement of every launch of the block, which the inference
+block (``WanAttentionBlock.forward``) runs too; this module launches no forward kernel of the block itself.  Both read
+their operands from a ``BlockWeights`` record, so the output is bit-identical wherever the inference path takes the
+same attention kernel (the training forward — kept activations, the forward under use_checkpoint and its re-run alike —
+pins the short-sequence kernel, OMH_ATTN_SHORT_KERNEL; the inference path switches to the long-sequence
+stream from 512 query tiles on, e.g. 16 clips x 1560 tokens).  Here the residual stream is written out of place and the
+few extra tensors the backward needs are asked of the steps as optional outputs of the producing kernels (the branch
+outputs y = o W^T + b for the gate gradients, the FFN pre-activation
 for GELU').  What happens to those tensors is ``model.use_checkpoint``'s call,
 as in the reference:
 
@@ -74,13 +76,7 @@ from .._backend import ops
 
 ptr = ops.ptr
 EPI_BF16, EPI_F32, EPI_ACC = ops.EPI_BF16, ops.EPI_F32, ops.EPI_F32_ACCUM
-EPI_GELU_BF16, EPI_RESID, EPI_GELU_BWD = ops.EPI_GELU_BF16, ops.EPI_RESID, ops.EPI_GELU_BWD_BF16
-BIAS_N, BIAS_M, BIAS_NONE = ops.BIAS_N, ops.BIAS_M, ops.BIAS_NONE
-LOG2E = 1.4426950408889634
-
-
-def _ru(a, b):
-    return (a + b - 1) // b * b
+EPI_GELU_BWD = ops.EPI_GELU_BWD_BF16
 
 
 class _State:
@@ -664,10 +660,7 @@ def _vt_buffer(model, key, B, d, Lp, L, dev, keep):
     tensor (two forwards may be in flight before a backward); a transient one (use_checkpoint: produced and consumed
     inside one node) comes from a per-model cache whose pad was zeroed once."""
     if keep:
-        t = torch.empty(B, d, Lp, dtype=torch.bfloat16, device=dev)
-        if Lp != L:
-            t[:, :, L:].zero_()
-        return t
+        return _model_mod._vt_fresh(B, d, Lp, L, dev)
     cache = model.__dict__.setdefault("_vt_cache", {})
     k = (key[1:], B, d, Lp, L, str(dev))
     t = cache.get(k)
@@ -701,149 +694,101 @@ def _cached_kv(S, idx, B, Sq, d):
 
 
 # ----------------------------------------------------------------------------- block forward (training)
-def _block_forward(model, blk, idx, st, x0, P, keep, need=True, mask=None):
-    """The inference block (model.py:279-330 on libomh.so, WanAttentionBlock.forward of this package) with the
-    residual stream out of place and the backward's extra tensors emitted by the producing epilogues.  x0 fp32
-    [B, S, d] is left untouched.  Returns (x3, S) — S holds what ``_block_backward`` reads.  ``need = False`` (the
-    forward pass under use_checkpoint: the block is run again in the backward): the extras — branch outputs, FFN
-    pre-activation, log-sum-exp, fp32 attention output — are not produced; the values of x3 do not depend on it."""
+def _operands(model, packs):
+    """One ``BlockWeights`` per block for the training node: views into the TrainPacks buffers ``packs`` (q | k and v
+    out of wqkv / bqkv, k and v out of wkv_c / wkv_i) and the fp32 master biases and norm3 parameters themselves
+    (detached: an update in place is seen).  Kept on the model's TrainPacks beside the layout it points into; rebuilt
+    with the layout, and when one of the parameters TrainPacks does not track (the o, cross-attention and FFN biases,
+    norm3) sits at another address — one look per forward, nothing per block."""
+    tp = TrainPacks.of(model)
+    ent = tp.__dict__.get("operands")
+    if ent is None or ent[0] is not packs or any(p.data_ptr() != a for p, a in ent[2]):
+        out, seen = [], []
+
+        def own(p):
+            assert p.dtype == torch.float32 and p.is_contiguous(), "training reads fp32 master biases and norm3 as they are"
+            seen.append((p, p.data_ptr()))
+            return p.detach()
+        for P, blk in zip(packs, model.blocks):
+            sa, ca, d = blk.self_attn, blk.cross_attn, blk.dim
+            W = _model_mod.BlockWeights(
+                wqk=P["wqkv"][:2 * d], bqk=P["bqkv"][:2 * d], wv=P["wqkv"][2 * d:], bv=P["bqkv"][2 * d:], wo=P["wo"],
+                bo=own(sa.o.bias), wq_c=P["wq_c"], bq_c=own(ca.q.bias), wk_c=P["wkv_c"][:d], bk_c=own(ca.k.bias),
+                wv_c=P["wkv_c"][d:], bv_c=own(ca.v.bias), wo_c=P["wo_c"], bo_c=own(ca.o.bias), w1=P["w1"],
+                b1=own(blk.ffn[0].bias), w2=P["w2"], b2=own(blk.ffn[2].bias))
+            if "wkv_i" in P:
+                W.wk_i, W.bk_i, W.wv_i, W.bv_i = P["wkv_i"][:d], own(ca.k_img.bias), P["wkv_i"][d:], own(ca.v_img.bias)
+            if blk.cross_attn_norm:
+                W.n3w, W.n3b = own(blk.norm3.weight), own(blk.norm3.bias)
+            out.append(W)
+        ent = tp.operands = (packs, out, seen)
+    return ent[1]
+
+
+def _block_forward(model, blk, idx, st, x0, keep, need=True, mask=None):
+    """The inference block — the steps of model.py, the one statement of every launch (WanAttentionBlock.forward is the
+    other sequence of them) — with the residual stream out of place and the backward's extra tensors asked of the steps
+    that produce them.  x0 fp32 [B, S, d] is left untouched.  Returns (x3, S) — S holds what ``_block_backward`` reads.
+    ``need = False`` (the forward pass under use_checkpoint: the block is run again in the backward): the extras —
+    branch outputs, FFN pre-activation, log-sum-exp, fp32 attention output — are not produced; the values of x3 do not
+    depend on it."""
+    M = _model_mod
     fc = st.fc
     B, Sq, d = x0.shape
     R = B * Sq
     dev = x0.device
     sa, ca = blk.self_attn, blk.cross_attn
-    N, D = sa.num_heads, sa.head_dim
-    f = blk.ffn_dim
     mod = blk.modulation.detach()
     if mod.dtype != torch.float32:
         mod = mod.float()
     mod = mod.contiguous()
-    e0 = fc.e0
-    rpb = fc.rpb or Sq                                   # rows per row of e0: the sequence, or a frame (per-frame t)
-    six = 6 * d
     i2v = hasattr(ca, "k_img")
-    n_img = 257 if i2v else 0
     frozen_ffn = getattr(model, "reference_ffn_freeze", True) and idx > 10
-    Lc = fc.Lc
-    Lt = Lc - n_img
-    bf = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
+    W = st.operands[idx]
+    bf = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev) if need else None
+    vt_alloc = lambda key: lambda B_, d_, Lp, L, dev_: _vt_buffer(model, (idx, key), B_, d_, Lp, L, dev_, keep)
     S = {"x0": x0}
-
-    def ctx_kv(lo, L, wkv, k_lin, v_lin, norm_name, key):
-        """K (normalised bf16 [B*L, d], its fp32 pre-norm) and V ([B*L, d] for the backward, V^T for the forward)
-        of context rows [lo, lo + L) — model.py:176-178 / 216-220 as WanT2VCrossAttention._context_kv computes them."""
-        Lp = _ru(L, 64)
-        kf = torch.empty(B, L, d, dtype=torch.float32, device=dev)
-        ops.gemm_raw(ptr(fc.ctx, lo * d), ptr(wkv), ptr(kf), L, d, d, d, d, d, EPI_F32, bias=ptr(k_lin.bias.detach()),
-                     bias_mode=BIAS_N, batch=B, strideA=Lc * d, strideB=0, strideC=L * d)
-        kn = ops.rmsnorm_rope(kf.view(B * L, d), ca._norm_w(norm_name), ca.eps, do_norm=ca.qk_norm)
-        vtc = _vt_buffer(model, (idx, key), B, d, Lp, L, dev, keep)
-        ops.gemm_raw(ptr(wkv, d * d), ptr(fc.ctx, lo * d), ptr(vtc), d, L, d, d, d, Lp, EPI_BF16,
-                     bias=ptr(v_lin.bias.detach()), bias_mode=BIAS_M, batch=B, strideA=0, strideB=Lc * d, strideC=d * Lp)
-        return kf, kn, vtc, Lp
-
-    def ln_mod(xin, shift_i, scale_i):
-        h = bf(R, d)
-        ops.layernorm_modulate_raw(ptr(xin), ptr(h), R, d, blk.eps, 1.0, ptr(mod, scale_i * d), ptr(e0, scale_i * d), six,
-                                   ptr(mod, shift_i * d), ptr(e0, shift_i * d), six, rpb)
-        return h
-
-    def resid(xin, a, w, b, gate_i, want_y, xout=None):
-        """x_out = x_in + (a w^T + b) * gate  (+ y = bf16(a w^T + b) when the gate gets a gradient)."""
-        xo = torch.empty_like(xin) if xout is None else xout
-        y = bf(R, d) if (want_y and need) else None
-        M, K = a.shape
-        kw = dict(c_in=ptr(xin) if xo.data_ptr() != xin.data_ptr() else None, aux=ptr(y) if y is not None else None, ldaux=d)
-        if gate_i is None:
-            ops.gemm_raw(ptr(a), ptr(w), ptr(xo), M, d, K, a.stride(0), w.stride(0), d, EPI_RESID,
-                         bias=ptr(b) if b is not None else None, bias_mode=BIAS_N if b is not None else BIAS_NONE,
-                         gate_const=1.0, split_k=fc.split_k, **kw)
-        else:
-            ops.gemm_raw(ptr(a), ptr(w), ptr(xo), M, d, K, a.stride(0), w.stride(0), d, EPI_RESID, bias=ptr(b),
-                         bias_mode=BIAS_N, gate0=ptr(mod, gate_i * d), gate1=ptr(e0, gate_i * d), gate1_stride=six,
-                         gate_rows=rpb, gate_const=0.0, split_k=fc.split_k, **kw)      # (same slices as the inference block: model.py)
-        return xo, y
-
     # ---- self-attention: x1 = x0 + o(attn(LN(x0)(1+e1)+e0)) * e2                                    model.py:292-296
-    h1 = ln_mod(x0, 0, 1)
-    wqkv, bqkv = P["wqkv"], P["bqkv"]
-    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    h1 = M._ln_mod(x0, fc, mod, blk.eps, 0, 1)
     if fc.cache is not None:                                # WanModel.forward_chunk(grad=True): _attend_cached's launches
         if not _ATTN_BWD2:
             raise NotImplementedError("OMH_ATTN_BWD=v1 has no cached backward: forward_chunk(grad=True) needs the default kernels")
         fc.cache_layer = idx
-        o, qk, q, k, v_own, lse_sa, o32_sa = sa._attend_cached(h1, fc, ptr(wqkv), ptr(bqkv), ptr(wqkv, 2 * d * d),
-                                                                ptr(bqkv, 2 * d), extras=True)
+        o, qk, q, k, v_own, lse_sa, o32_sa = sa._attend_cached(h1, fc, W, extras=True)
         vt = None
         S.update(v_own=v_own, cached=(fc.cache, fc.cache_lo, fc.cache.length, fc.cache.mark()))
     else:
-        qk = bf(R, 2 * d)                                       # q | k projection, bf16 like the inference path
-        ops.gemm_raw(ptr(h1), ptr(wqkv), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(bqkv), bias_mode=BIAS_N)
-        q, k = bf(R, d), bf(R, d)
-        nq, nk = sa._norm_w("norm_q"), sa._norm_w("norm_k")
-        ops.rmsnorm_rope_bf16_pair_raw(ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(nq) if nq is not None else None,
-                                       ptr(nk) if nk is not None else None, sa.eps, int(sa.qk_norm), ptr(fc.rope_cos),
-                                       ptr(fc.rope_sin), fc.rope_cos.shape[0], D, ptr(fc.grid32), Sq,
-                                       out_scale0=D ** -0.5 * LOG2E, out_scale1=1.0)      # q and k: one launch, as model.py
-        Sp = _ru(Sq, 64)
-        vt = _vt_buffer(model, (idx, "sa"), B, d, Sp, Sq, dev, keep)
-        ops.gemm_raw(ptr(wqkv, 2 * d * d), ptr(h1), ptr(vt), d, Sq, d, d, d, Sp, EPI_BF16, bias=ptr(bqkv, 2 * d),
-                     bias_mode=BIAS_M, batch=B, strideA=0, strideB=Sq * d, strideC=d * Sp)
-        o = bf(R, d)
-        lse_sa = f32(B, N, Sq) if need else None
-        o32_sa = f32(R, d) if (_ATTN_BWD2 and need) else None     # the output before its rounding: delta of the backward
-        if mask is None:                                        # (else: the checkpoint re-run, handed the forward's own mask)
-            mask = sa._call_mask(fc, dev)                       # band, block mask, staircase or interval mask — or a block
-            if mask is None:                                    # policy, which chooses from this call's q and k
-                mask = sa._call_mask(fc, dev, sa._dynamic_mask(q, k, B, Sq, fc.seq_lens32))
+        # (o32, the output before its rounding: delta of the backward)
+        # (mask: the checkpoint re-run is handed the forward's own; else resolved from the band, block mask, staircase or
+        # interval mask — or by a block policy from this call's q and k)
+        o, qk, q, k, vt, mask, lse_sa, o32_sa = sa._attend(h1, fc, W, extras=True, lse=need, o32=need and _ATTN_BWD2,
+                                                           flags=_ATTN_FLAGS, vt_alloc=vt_alloc("sa"), mask=mask)
         if need and not _ATTN_BWD2 and mask.kind != "full":     # (their backwards need o32)
             raise NotImplementedError(f"OMH_ATTN_BWD=v1 has no {mask.kind} backward: the default kernels are needed")
-        ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, Sq, Sq, Sq * d, d, Sq * d, d, d * Sp,
-                           Sq * d, d, Sp, D ** -0.5, lse=ptr(lse_sa) if need else None, q_prescaled=1,
-                           o32=ptr(o32_sa) if o32_sa is not None else None, flags=_ATTN_FLAGS, mask=mask)
-    x1, y1 = resid(x0, o, P["wo"], sa.o.bias.detach(), 2, True)
+    x1, y1 = torch.empty_like(x0), bf(R, d)
+    M._resid(x0, o, W.wo, W.bo, fc, mod, 2, out=x1, y=y1)
     S.update(h1=h1, qk=qk, q=q, k=k, vt=vt, o=o, lse_sa=lse_sa, y1=y1, x1=x1, o32_sa=o32_sa, mask=mask)
     # ---- cross-attention: x2 = x1 + o(attn(norm3(x1), context))                                     model.py:313
-    h3 = bf(R, d)
+    h3 = M._cross_input(x1, W, getattr(blk.norm3, "eps", blk.eps))
     if blk.cross_attn_norm:
-        n3 = blk.norm3
-        w3, b3 = n3.weight.detach().float().contiguous(), n3.bias.detach().float().contiguous()
-        ops.layernorm_modulate_raw(ptr(x1), ptr(h3), R, d, n3.eps, 0.0, ptr(w3), None, 0, ptr(b3), None, 0, R)
-        S.update(w3=w3)
-    else:
-        ops.cast_bf16(x1.view(R, d), out=h3)
-    qcb = ops.gemm(h3, P["wq_c"], bias=ca.q.bias.detach(), epilogue=EPI_BF16)
-    qc = bf(R, d)
-    wnq = ca._norm_w("norm_q")
-    ops.rmsnorm_rope_bf16_raw(ptr(qcb), d, ptr(qc), R, d, ptr(wnq) if wnq is not None else None, ca.eps, int(ca.qk_norm),
-                              None, None, 0, D, None, Sq)
-
-    kf, kc, vtc, Ltp = ctx_kv(n_img, Lt, P["wkv_c"], ca.k, ca.v, "norm_k", "ca")
-    oc = bf(R, d)
-    lse_ca = f32(B, N, Sq) if need else None
+        S.update(w3=W.n3w)
+    qc, qcb = ca._query(h3, fc, W, extras=True)
     # (fc.ctx_mask: frame-aligned condition tokens — the masked entries, whose backward needs the fp32 output)
-    o32_ca = f32(R, d) if ((_ATTN_BWD2 or fc.ctx_mask is not None) and need and not i2v) else None
-    # the reference passes the (text + 257) lengths here (model.py:223,537); keys are clipped to the text rows
-    ops.flash_attn_raw(ptr(qc), ptr(kc), ptr(vtc), ptr(oc), ptr(fc.ctx_lens32), B, N, Sq, Lt, Sq * d, d, Lt * d, d,
-                       d * Ltp, Sq * d, d, Ltp, D ** -0.5, lse=ptr(lse_ca) if need else None,
-                       o32=ptr(o32_ca) if o32_ca is not None else None, flags=_ATTN_FLAGS, mask=fc.ctx_mask)
-    x2, _ = resid(x1, oc, P["wo_c"], ca.o.bias.detach(), None, False)
+    oc, kf, kc, vtc, lse_ca, o32_ca = ca._attend_rows(
+        qc, fc, W, extras=True, lse=need, o32=need and (_ATTN_BWD2 or fc.ctx_mask is not None) and not i2v,
+        flags=_ATTN_FLAGS, vt_alloc=vt_alloc("ca"))
+    x2 = M._resid(x1, oc, W.wo_c, W.bo_c, fc, out=torch.empty_like(x1))
     S.update(h3=h3, qcb=qcb, qc=qc, kf=kf, kc=kc, vtc=vtc, oc=oc, lse_ca=lse_ca, x2=x2, o32_ca=o32_ca)
-    if i2v:                                                  # model.py:189-230: extra attention over the 257 image tokens
-        kfi, ki, vti, Lip = ctx_kv(0, n_img, P["wkv_i"], ca.k_img, ca.v_img, "norm_k_img", "ci")
-        oi = bf(R, d)
-        lse_ci = f32(B, N, Sq) if need else None
-        ops.flash_attn_raw(ptr(qc), ptr(ki), ptr(vti), ptr(oi), None, B, N, Sq, n_img, Sq * d, d, n_img * d, d, d * Lip,
-                           Sq * d, d, Lip, D ** -0.5, lse=ptr(lse_ci) if need else None, flags=_ATTN_FLAGS)
-        resid(x2, oi, P["wo_c"], None, None, False, xout=x2)          # x2 += o_img Wo^T   (in place)
+    if i2v:                                                  # model.py:189-230: extra attention over the image tokens
+        oi, kfi, ki, vti, lse_ci, _ = ca._attend_rows(qc, fc, W, img=True, extras=True, lse=need, flags=_ATTN_FLAGS,
+                                                      vt_alloc=vt_alloc("ci"))
+        M._resid(x2, oi, W.wo_c, None, fc)                   # x2 += o_img Wo^T   (in place)
         S.update(kfi=kfi, ki=ki, vti=vti, oi=oi, lse_ci=lse_ci)
     # ---- FFN: x3 = x2 + (W2 gelu(W1 (LN(x2)(1+e4)+e3) + b1) + b2) * e5                               model.py:314-328
-    h2 = ln_mod(x2, 3, 4)
-    u = bf(R, f)
-    u_pre = None if (frozen_ffn or not need) else bf(R, f)
-    ops.gemm_raw(ptr(h2), ptr(P["w1"]), ptr(u), R, f, d, d, d, f, EPI_GELU_BF16, bias=ptr(blk.ffn[0].bias.detach()),
-                 bias_mode=BIAS_N, aux=ptr(u_pre) if u_pre is not None else None, ldaux=f)
-    x3, y3 = resid(x2, u, P["w2"], blk.ffn[2].bias.detach(), 5, True)
+    h2 = M._ln_mod(x2, fc, mod, blk.eps, 3, 4)
+    u, u_pre = M._ffn_up(h2, W, pre=True) if need and not frozen_ffn else (M._ffn_up(h2, W), None)
+    x3, y3 = torch.empty_like(x2), bf(R, d)
+    M._resid(x2, u, W.w2, W.b2, fc, mod, 5, out=x3, y=y3)                   # (same slices as the inference block)
     S.update(y3=y3)
     if not frozen_ffn:
         S.update(h2=h2, u=u, u_pre=u_pre)
@@ -1168,7 +1113,7 @@ def activation_bytes(model, rows, batch=1):
     # per token and block: fp32 [dim] x0, x1, x2, o32_sa, o32_ca (20 B) + bf16 [dim] h1, qk (2), q, k, vt, o, y1, h3, qcb,
     # qc, oc, y3, h2 (14 -> 28 B) (+ oi for i2v) + bf16 [ffn] u, u_pre + two (i2v: three) fp32 log-sum-exp values per head
     per_row = (48 + (2 if i2v else 0)) * dim + 4 * ffn + (12 if i2v else 8) * heads
-    ctx_rows = max(1, int(batch)) * (model.text_len + (257 if i2v else 0))
+    ctx_rows = max(1, int(batch)) * (model.text_len + (_model_mod.N_IMG if i2v else 0))
     per_ctx_row = 8 * dim                                     # context K fp32 + normalised K bf16 + V^T bf16
     return int(len(model.blocks) * (rows * per_row + ctx_rows * per_ctx_row) * 1.15)
 
@@ -1223,7 +1168,7 @@ class _BlockFn(torch.autograd.Function):
             x0 = x.detach()
             if not (x0.dtype == torch.float32 and x0.is_contiguous()):
                 x0 = x0.float().contiguous()
-            out, S = _block_forward(model, blk, idx, st, x0, st.packs[idx], keep, need=keep)
+            out, S = _block_forward(model, blk, idx, st, x0, keep, need=keep)
         ctx.model, ctx.st, ctx.idx = model, st, idx
         ctx.kept = S if keep else None
         ctx.mask = S["mask"]                                 # the backward (and its re-run of the block) uses this mask
@@ -1249,7 +1194,7 @@ class _BlockFn(torch.autograd.Function):
                 raise RuntimeError("forward_chunk(grad=True): the backward of a chunk runs once (its kept activations are "
                                    "released; the block cannot be re-run against the cache as it is now)")
             if S is None:                                    # use_checkpoint: re-run the forward's kernels on its input
-                _, S = _block_forward(model, blk, idx, st, x0, P, False, mask=ctx.mask)
+                _, S = _block_forward(model, blk, idx, st, x0, False, mask=ctx.mask)
             # The block backward updates the incoming gradient IN PLACE.  That is only legal when the buffer belongs to
             # this node: autograd hands a node the producer's own tensor when the block output has ONE consumer (the next
             # block / the head allocate a fresh dx), but a caller that also taps block outputs (the reference's
@@ -1517,7 +1462,7 @@ class _EmbedFn(torch.autograd.Function):
             # ---- patch embedding: x[b,:n] = tok_b Wpe^T + bpe
             pt, ph, pw = model.patch_size
             kin = model.in_dim * pt * ph * pw
-            Kp = _ru(kin, 8)
+            Kp = _model_mod._round_up(kin, 8)
             w_pe, b_pe = tr("patch_embedding.weight"), tr("patch_embedding.bias")
             dW = torch.zeros(d, Kp, dtype=torch.float32, device=dev) if w_pe else None
             db = torch.zeros(d, dtype=torch.float32, device=dev) if b_pe else None
@@ -1647,6 +1592,7 @@ def forward_train(model, x, t, context, seq_len, clip_fea=None, y=None, extra_co
         _join_pending.pop(key, None)
         _wgrad_join(key[0])
     st.packs = TrainPacks.of(model).refresh(model)           # bf16 weight copies: one launch when anything changed
+    st.operands = _operands(model, st.packs)
     # forwards of this model whose backward has not run yet: with more than one of them in a pass the
     # engine sums their contributions to a shared parameter on the main stream, so none of them may defer its join
     model.__dict__.setdefault("_omh_live_states", weakref.WeakSet()).add(st)
@@ -1708,6 +1654,7 @@ def forward_chunk_train(model, x, t, context, cache, frame_offset, commit, clip_
         _join_pending.pop(key, None)
         _wgrad_join(key[0])
     st.packs = TrainPacks.of(model).refresh(model)
+    st.operands = _operands(model, st.packs)
     model.__dict__.setdefault("_omh_live_states", weakref.WeakSet()).add(st)
 
     st.after_embed = lambda fc: model._chunk_ctx(fc, cache, lo, frame_offset)

@@ -31,8 +31,8 @@ vals = []
 def tap(sa):
     inner = sa._attend
 
-    def attend(h, fc):
-        o = inner(h, fc)
+    def attend(*args, **kw):
+        o = inner(*args, **kw)
         vals.append(None if sa.last_qk_norm2_max is None else sa.last_qk_norm2_max.clone())
         return o
     sa._attend = attend
