@@ -793,6 +793,17 @@ int omh_nchw_to_cl(const float* x, void* y_bf16, int32_t C, int32_t T, int32_t H
 int omh_cl_to_nchw(const float* x, float* y, int32_t C, int32_t T, int32_t H, int32_t W, int32_t Cp,
                    const float* mul, const float* add, float lo, float hi, int32_t t_total, int32_t t0,
                    omh_stream_t stream);
+/* Packed 8-bit frames for a consumer of a live stream (additive to ABI v12) — what the reference makes on the host when
+ * it writes a clip (wan/utils/utils.py:40-47: clamp to the value range, normalise to [0, 1], (tensor * 255).type(uint8)):
+ *   out[t0+t][h][w][c] = (uint8)( (min(max(x[t][h][w][c], lo), hi) - lo) / (hi - lo) * 255.0f ),  c < C
+ * every step in fp32 and in this order, the cast truncating; x fp32 [T, H, W, Cp] (the decoder head's output, Cp >= C),
+ * out uint8 [t_total, H, W, C].  With lo = -1, hi = 1 the bytes equal torch's
+ * ((x.clamp(-1, 1) + 1) / 2 * 255).to(torch.uint8) on the same values; +-inf clamp, NaN is outside the contract.
+ * One launch; whole-dword stores with byte stores for the 0..3 bytes at either end, so any t0 H W C is taken.
+ * OMH_E_BADARG: a null pointer, a dimension <= 0, Cp < C, frames outside [0, t_total), hi <= lo; OMH_E_SHAPE: hi - lo is
+ * no finite fp32; OMH_E_ALIGN: x not 4-byte aligned. */
+int omh_cl_to_u8(const float* x, void* out_u8, int32_t C, int32_t T, int32_t H, int32_t W, int32_t Cp, float lo, float hi,
+                 int32_t t_total, int32_t t0, omh_stream_t stream);
 
 /* ---- ABI v8: the fp32-faithful VAE mode (the reference computes its VAE in fp32: WanVAE(dtype=torch.float) ->
  * amp.autocast(dtype=self.dtype), vae.py:619-624,649-663).  Every convolution / GEMM operand is carried as a bf16

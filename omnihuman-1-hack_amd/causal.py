@@ -8,7 +8,8 @@ The rule (include/omh.h, ``omh_chunk_causal``): with ``chunk`` = C >= 1 tokens, 
 
 Positions are absolute (no bottom-right shift).  ``WanModel.set_causal_chunks`` runs every self-attention of a forward
 under it with C = a group of latent frames; ``WanModel.forward_chunk`` produces the same clip frame group by frame group
-against a ``KVCache``, and ``sample`` denoises a clip that way.
+against a ``KVCache``, and ``sample`` denoises a clip that way; ``stream`` is the same rollout as a generator that hands every
+chunk out as soon as it is denoised, with its pixel frames from a ``WanVAE.decode_stream`` when a VAE is given.
 
 Interval masks (include/omh.h, ``omh_interval_mask``) are the table-driven generalisation: both axes are cut into groups
 of ``group`` tokens and a bool matrix ``vis[q_groups, k_groups]`` with at most two runs of True per row and per column
@@ -28,7 +29,7 @@ import ctypes
 
 import torch
 
-__all__ = ["chunk_causal_visible", "KVCache", "RollingKVCache", "sample", "IntervalMask", "interval_visible",
+__all__ = ["chunk_causal_visible", "KVCache", "RollingKVCache", "sample", "stream", "StreamChunk", "IntervalMask", "interval_visible",
            "teacher_forcing_groups", "condition_window_visible",
            "sink_window_groups", "forcing_loss", "self_forcing_rollout", "dmd_sigmas", "dmd_loss", "critic_loss"]
 
@@ -397,37 +398,79 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
     and commit passes alike — keeps only the tokens of the frames from the chunk's first frame - back to its last frame
     (and the -1 tokens): a live stream needs nothing it does not have yet.
     The model's own
-    ``set_causal_chunks`` setting is restored on the way out.  Returns the latents of the whole clip, fp32 [C, F, H, W]."""
+    ``set_causal_chunks`` setting is restored on the way out.  Returns the latents of the whole clip, fp32 [C, F, H, W]
+    — the chunks of ``stream`` with the same arguments, concatenated."""
+    geom = _rollout_geometry("sample", noise, frames_per_chunk, left_chunks, sink_chunks, rolling)
+    chunks = _rollout(model, noise, context, context_null, geom, make_scheduler, guide_scale, context_t, rolling, caches,
+                      extra_conditions, who="sample")
+    return torch.cat([c.latents for c in chunks], dim=1)
+
+
+class StreamChunk:
+    """One chunk of ``stream``: ``index`` (0, 1, ...), ``frames`` = (f0, f1), the chunk's latent frame range in the clip,
+    ``latents`` fp32 [C, f1 - f0, h, w], ``video`` — the pixel frames ``DecodeStream.push`` returned for them, or None
+    without a VAE — and ``ready``, a ``torch.cuda.Event`` behind the last launch that writes either.  ``wait()`` makes the
+    current stream wait for it (and tells the caching allocator that the tensors are used there)."""
+    __slots__ = ("index", "frames", "latents", "video", "ready")
+
+    def __init__(self, index, frames, latents, video=None, ready=None):
+        self.index, self.frames, self.latents, self.video, self.ready = index, frames, latents, video, ready
+
+    def wait(self):
+        if self.ready is not None:
+            cur = torch.cuda.current_stream(self.latents.device)
+            cur.wait_event(self.ready)
+            for u in (self.latents, self.video):
+                if u is not None:
+                    u.record_stream(cur)
+        return self
+
+
+def _rollout_geometry(who, noise, frames_per_chunk, left_chunks, sink_chunks, rolling):
+    """The argument rules ``sample`` and ``stream`` share (nothing touches a device).  Returns (fpc, left_chunks,
+    sink_chunks) as the model is set up with them."""
     fpc = int(frames_per_chunk)
     if noise.dim() != 4:
-        raise ValueError(f"sample: noise [C, F, H, W] of one clip expected, got {tuple(noise.shape)}")
-    F = noise.shape[1]
-    pt, ph, pw = model.patch_size
-    tokens = (F // pt) * (noise.shape[2] // ph) * (noise.shape[3] // pw)
+        raise ValueError(f"{who}: noise [C, F, H, W] of one clip expected, got {tuple(noise.shape)}")
     left_chunks, sink_chunks = int(left_chunks), int(sink_chunks)
     if rolling and left_chunks < 0:
-        raise ValueError("sample: rolling=True needs left_chunks >= 0 (an unbounded look-back never evicts)")
+        raise ValueError(f"{who}: rolling=True needs left_chunks >= 0 (an unbounded look-back never evicts)")
     if sink_chunks < 0:
-        raise ValueError(f"sample: sink_chunks = {sink_chunks} >= 0 expected")
+        raise ValueError(f"{who}: sink_chunks = {sink_chunks} >= 0 expected")
     if left_chunks < 0:
         sink_chunks = 0
+    return fpc, left_chunks, sink_chunks
+
+
+@torch.no_grad()
+def _rollout(model, noise, context, context_null, geom, make_scheduler, guide_scale, context_t, rolling, caches,
+             extra_conditions, who, decoder=None, overlap=False, events=False):
+    """The one statement of the chunk-by-chunk rollout: a generator of ``StreamChunk``s (``sample`` concatenates their
+    latents, ``stream`` hands them out).  ``decoder``: a ``DecodeStream`` every finished chunk is pushed into; ``overlap``:
+    on a side stream of this generator's, see ``stream``; ``events``: record ``ready``."""
+    fpc, left_chunks, sink_chunks = geom
+    F = noise.shape[1]
+    dev = noise.device
+    pt, ph, pw = model.patch_size
+    tokens = (F // pt) * (noise.shape[2] // ph) * (noise.shape[3] // pw)
     prev = getattr(model, "_causal_chunks", None)
     model.set_causal_chunks(fpc, left_chunks, sink_chunks)
     try:
         if caches is not None:
             caches = tuple(caches)
             if len(caches) != 2:
-                raise ValueError("sample: caches = (conditional, unconditional) expected")
+                raise ValueError(f"{who}: caches = (conditional, unconditional) expected")
             for c in caches:
                 c.reset()
         elif rolling or sink_chunks > 0:
             Ct = fpc * (noise.shape[2] // ph) * (noise.shape[3] // pw)
-            caches = tuple(RollingKVCache(model, 1, Ct, sink_chunks, left_chunks, noise.device) for _ in range(2))
+            caches = tuple(RollingKVCache(model, 1, Ct, sink_chunks, left_chunks, dev) for _ in range(2))
         else:
-            caches = (KVCache(model, 1, tokens, noise.device), KVCache(model, 1, tokens, noise.device))
-        t_ctx = torch.full((1,), float(context_t), device=noise.device)
-        done = []
-        for f0 in range(0, F, fpc):
+            caches = (KVCache(model, 1, tokens, dev), KVCache(model, 1, tokens, dev))
+        t_ctx = torch.full((1,), float(context_t), device=dev)
+        side = torch.cuda.Stream(dev) if (overlap and decoder is not None) else None
+        held = None
+        for index, f0 in enumerate(range(0, F, fpc)):
             lat = noise[:, f0:f0 + fpc].float().contiguous()
             scheduler = make_scheduler()
             for t in scheduler.timesteps:
@@ -435,13 +478,63 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
                 cond = model.forward_chunk([lat], tt, context, caches[0], commit=False, extra_conditions=extra_conditions)[0]
                 uncond = model.forward_chunk([lat], tt, context_null, caches[1], commit=False)[0]
                 lat = scheduler.step_cfg(cond, uncond, guide_scale, lat)
-            done.append(lat)
-            if f0 + fpc < F:
+            if held is not None:                  # overlap: the chunk before goes out now that this one's launches are enqueued
+                yield held
+                held = None
+            chunk = StreamChunk(index, (f0, f0 + lat.shape[1]), lat)
+            if side is not None:
+                main = torch.cuda.current_stream(dev)
+                fence = torch.cuda.Event()
+                fence.record(main)                # behind the chunk's last sampler update
+                lat.record_stream(side)
+                with torch.cuda.stream(side):
+                    side.wait_event(fence)
+                    chunk.video = decoder.push(lat)
+                    chunk.ready = torch.cuda.Event()
+                    chunk.ready.record(side)
+            else:
+                if decoder is not None:
+                    chunk.video = decoder.push(lat)
+                if events:
+                    chunk.ready = torch.cuda.Event()
+                    chunk.ready.record(torch.cuda.current_stream(dev))
+            last = f0 + fpc >= F
+            if side is None or last:
+                yield chunk
+            else:
+                held = chunk
+            if not last:
                 model.forward_chunk([lat], t_ctx, context, caches[0], commit=True, extra_conditions=extra_conditions)
                 model.forward_chunk([lat], t_ctx, context_null, caches[1], commit=True)
-        return torch.cat(done, dim=1)
     finally:
         model._causal_chunks = prev
+
+
+def stream(model, noise, context, context_null, *, frames_per_chunk, left_chunks=-1, make_scheduler, guide_scale,
+           context_t=0.0, sink_chunks=0, rolling=False, caches=None, extra_conditions=None, vae=None, output="float",
+           overlap=False):
+    """``sample`` as a generator: one ``StreamChunk`` per chunk, as soon as the chunk is denoised — ``sample(...)`` equals
+    ``torch.cat([c.latents for c in stream(...)], 1)`` bit for bit.  ``vae``: a ``WanVAE``; every chunk is pushed into one
+    ``vae.decode_stream(output)`` and ``chunk.video`` holds the pixel frames it completes (``output`` = "float": fp32
+    [3, frames, 8h, 8w]; "uint8": packed RGB [frames, 8h, 8w, 3]), together the frames of ``vae.decode`` on the whole clip,
+    bit for bit: 4 (n - 1) + 1 frames for the first chunk of n latent frames, 4 n for every later one.
+
+    ``overlap=False`` (the default): everything runs on the current stream; chunk I is yielded behind its decode, and its
+    commit pass is enqueued when the consumer asks for the next chunk.  ``overlap=True`` (with a ``vae``): the decode of
+    chunk I runs on a side stream this generator owns, fenced by an event behind the chunk's last sampler update, and the
+    chunk is yielded only after the commit pass and the denoising launches of chunk I + 1 are enqueued on the main stream
+    (the last chunk at once) — a consumer that blocks on ``chunk.ready`` does not serialise the two.  The bits are the
+    same.  Either way call ``chunk.wait()`` (or wait for ``chunk.ready``) before reading the tensors from another stream.
+
+    While the generator is suspended the model stays under this rollout's ``set_causal_chunks`` setting; it is restored
+    when the generator finishes or is closed.  The arguments are checked here, before the first chunk is asked for
+    (ValueError, as ``sample``)."""
+    geom = _rollout_geometry("stream", noise, frames_per_chunk, left_chunks, sink_chunks, rolling)
+    if output not in ("float", "uint8"):
+        raise ValueError(f"stream: output = {output!r}, 'float' or 'uint8' expected")
+    decoder = vae.decode_stream(output) if vae is not None else None
+    return _rollout(model, noise, context, context_null, geom, make_scheduler, guide_scale, context_t, rolling, caches,
+                    extra_conditions, who="stream", decoder=decoder, overlap=bool(overlap), events=True)
 
 
 def forcing_loss(model, latents, noise, sigmas, timesteps, context, mode="teacher"):

@@ -133,6 +133,64 @@ void cl_to_nchw_kernel(const float* __restrict__ x, float* __restrict__ y, int C
     }
 }
 
+// fp32 channels-last -> packed 8-bit frames (omh_cl_to_u8; the reference's host-side rule, wan/utils/utils.py:40-47).
+// Per element, in fp32 and in this order: clamp to [lo, hi], (v - lo) / (hi - lo), * 255, truncate.  RCP: hi - lo is a
+// power of two, so the division is the exact product with its reciprocal (the same bits, a tenth of the instructions).
+template <bool RCP>
+__device__ __forceinline__ uint32_t u8_of(float x, float lo, float hi, float dm) {
+    const float v = fminf(fmaxf(x, lo), hi);
+    const float u = RCP ? (v - lo) * dm : (v - lo) / dm;
+    return (uint32_t)(u * 255.0f);
+}
+
+struct __attribute__((packed, aligned(4))) f32x4_a4 { float x, y, z, w; };       // 16 bytes at dword alignment
+
+// ``out`` points at the first byte of frame t0 and n = T H W C bytes follow.  The bytes [head, head + 4 nq) are whole
+// aligned dwords (head = the 0..3 bytes in front of the first one, when t0 H W C is odd); a lane makes one dword from four
+// consecutive elements — a wave instruction reads 1 KiB and writes 256 B, both contiguous — and has four of them in flight
+// per trip.  CONTIG (Cp == C, the decoder head's output): element e is x[e], one 16-byte load per dword (dword-aligned
+// only: the output's alignment decides where a group starts); otherwise x[(e / C) Cp + e % C], element by element.
+// The 0..3 bytes at either end are single byte stores of workgroup 0.
+template <bool CONTIG, bool RCP>
+__global__ __launch_bounds__(256)
+void cl_to_u8_kernel(const float* __restrict__ x, uint8_t* __restrict__ out, int64_t n, int head, int C, int Cp,
+                     float lo, float hi, float dm) {
+    const int64_t nq = (n - head) >> 2;
+    uint32_t* __restrict__ o32 = (uint32_t*)(out + head);
+    auto src = [&](int64_t e) -> float { return CONTIG ? x[e] : x[(e / C) * Cp + e % C]; };
+    const int64_t stride = (int64_t)gridDim.x * 1024;
+    for (int64_t q0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; q0 < nq; q0 += stride) {
+        float v[4][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t q = q0 + j * 256;
+            if (q < nq) {
+                const int64_t e = head + 4 * q;
+                if (CONTIG) {
+                    const f32x4_a4 t = *(const f32x4_a4*)(x + e);
+                    v[j][0] = t.x; v[j][1] = t.y; v[j][2] = t.z; v[j][3] = t.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[j][k] = src(e + k);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t q = q0 + j * 256;
+            if (q < nq)
+                o32[q] = u8_of<RCP>(v[j][0], lo, hi, dm) | (u8_of<RCP>(v[j][1], lo, hi, dm) << 8) |
+                         (u8_of<RCP>(v[j][2], lo, hi, dm) << 16) | (u8_of<RCP>(v[j][3], lo, hi, dm) << 24);
+        }
+    }
+    if (blockIdx.x == 0) {
+        const int64_t tail0 = head + 4 * nq;
+        const int t = threadIdx.x;
+        if (t < head) out[t] = (uint8_t)u8_of<RCP>(src(t), lo, hi, dm);
+        else if (t >= 4 && t < 8 && tail0 + (t - 4) < n) out[tail0 + (t - 4)] = (uint8_t)u8_of<RCP>(src(tail0 + (t - 4)), lo, hi, dm);
+    }
+}
+
 // one 256-thread block per row
 __global__ __launch_bounds__(256)
 void softmax_rows_kernel(const float* __restrict__ x, int64_t ldx, uint16_t* __restrict__ y, int64_t ldy, int L,
@@ -406,6 +464,34 @@ extern "C" int omh_cl_to_nchw(const float* x, float* y, int32_t C, int32_t T, in
     omh_clear_status();
     hipLaunchKernelGGL(cl_to_nchw_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, C, T,
                        H, W, Cp, mul, add, lo, hi, t_total, t0);
+    return omh_launch_status();
+}
+
+extern "C" int omh_cl_to_u8(const float* x, void* out, int32_t C, int32_t T, int32_t H, int32_t W, int32_t Cp, float lo,
+                            float hi, int32_t t_total, int32_t t0, omh_stream_t stream) {
+    if (!x || !out || C <= 0 || T <= 0 || H <= 0 || W <= 0 || Cp < C || t0 < 0 || t0 + T > t_total || !(hi > lo))
+        return OMH_E_BADARG;
+    const float d = hi - lo;
+    if (!(d <= 3.0e38f)) return OMH_E_SHAPE;                         // a range whose width is no finite fp32
+    if ((uintptr_t)x & 3) return OMH_E_ALIGN;
+    const int64_t frame = (int64_t)H * W * C, n = (int64_t)T * frame;
+    uint8_t* o = (uint8_t*)out + (int64_t)t0 * frame;
+    int64_t head = (int64_t)((4 - ((uintptr_t)o & 3)) & 3);
+    if (head > n) head = n;
+    int ex = 0;
+    const bool rcp = frexpf(d, &ex) == 0.5f && ex > -100 && ex < 100;  // a power of two: 1 / d is exact
+    const float dm = rcp ? 1.0f / d : d;
+    const int64_t blocks = ((n - head) / 4 + 1023) / 1024;
+    const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks)));
+    hipStream_t s = (hipStream_t)stream;
+    omh_clear_status();
+    if (Cp == C) {
+        if (rcp) hipLaunchKernelGGL((cl_to_u8_kernel<true, true>), grid, dim3(256), 0, s, x, o, n, (int)head, C, Cp, lo, hi, dm);
+        else hipLaunchKernelGGL((cl_to_u8_kernel<true, false>), grid, dim3(256), 0, s, x, o, n, (int)head, C, Cp, lo, hi, dm);
+    } else {
+        if (rcp) hipLaunchKernelGGL((cl_to_u8_kernel<false, true>), grid, dim3(256), 0, s, x, o, n, (int)head, C, Cp, lo, hi, dm);
+        else hipLaunchKernelGGL((cl_to_u8_kernel<false, false>), grid, dim3(256), 0, s, x, o, n, (int)head, C, Cp, lo, hi, dm);
+    }
     return omh_launch_status();
 }
 

@@ -14,7 +14,7 @@ from ._lib import (ATTN_ALLOW_SPLIT, ATTN_SHORT_KERNEL, BIAS_M, BIAS_N, BIAS_NON
                    EPI_GELU_BWD_BF16, EPI_GELU_ERF_BF16, EPI_RESID, AttnArgs, GemmArgs, OmhError, check, lib)
 
 __all__ = ["gemm", "flash_attn", "flash_attn_func", "layernorm_modulate", "rmsnorm_rope", "cast_bf16", "patchify", "unpatchify",
-           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "flow_noise", "dmd_grad", "dmd_loss", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw",
+           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "flow_noise", "dmd_grad", "dmd_loss", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw", "cl_to_u8",
            "softmax_rows", "OmhError",
            "EPI_BF16", "EPI_F32", "EPI_GELU_BF16", "EPI_GELU_ERF_BF16", "EPI_RESID", "EPI_F32_ACCUM", "BIAS_NONE", "BIAS_N", "BIAS_M"]
 
@@ -925,6 +925,19 @@ def cl_to_nchw(x, out, t0, Cc, mul=None, add=None, lo=-3.0e38, hi=3.0e38):
     assert out.shape[0] == Cc and tuple(out.shape[2:]) == (H, W)
     check(lib.omh_cl_to_nchw(_p(x), _p(out), Cc, T, H, W, Cp, _p(mul), _p(add), lo, hi, out.shape[1], t0,
                              _stream()), "omh_cl_to_nchw")
+    return out
+
+
+def cl_to_u8(x, out, t0, C, lo=-1.0, hi=1.0):
+    """x fp32 [T, H, W, Cp] -> out uint8 [Ttot, H, W, C] frames [t0, t0+T): clamp to [lo, hi], (v - lo) / (hi - lo),
+    * 255, truncate (include/omh.h, omh_cl_to_u8 — the reference's wan/utils/utils.py:40-47 with lo = -1, hi = 1)."""
+    _dev(x, out)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 4
+    T, H, W, Cp = x.shape
+    assert tuple(out.shape[1:]) == (H, W, C)
+    check(lib.omh_cl_to_u8(_p(x), _p(out), C, T, H, W, Cp, float(lo), float(hi), out.shape[0], t0, _stream()),
+          "omh_cl_to_u8")
     return out
 
 

@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from .._backend import ops
 
-__all__ = ["WanVAE"]
+__all__ = ["WanVAE", "DecodeStream", "stream_frames"]
 
 CACHE_T = 2
 
@@ -321,7 +321,7 @@ class _ConvState:
 
 
 class _Stream:
-    """All per-call state of one encode or decode (the reference's _feat_map)."""
+    """All state of one encode, or of one DecodeStream from push to push (the reference's _feat_map)."""
 
     def __init__(self, device, f32=False):
         self.device = device
@@ -671,41 +671,134 @@ class WanVAE_(nn.Module):
             raise ops.OmhError("WanVAE runs on the MI355X only (no CPU fallback)")
         assert z.dim() == 5 and z.shape[0] == 1
         lat = z[0].to(device=dev, dtype=torch.float32).contiguous()
-        _, Tl, h, w = lat.shape
-        if isinstance(scale[0], torch.Tensor):
-            mul = (1.0 / scale[1]).to(device=dev, dtype=torch.float32).contiguous()
-            add = scale[0].to(device=dev, dtype=torch.float32).contiguous()
+        # one push of the whole clip into a stream of its own: the walk is DecodeStream.push (latent-resolution front over
+        # all frames in one pass, the first latent frame alone through the Resamples, then _GROUP / _GROUP2 frames per step)
+        return DecodeStream(self, scale, clamp=clamp).push(lat).unsqueeze(0)
+
+    def clear_cache(self):
+        """The reference resets its per-call feature caches here (vae.py:582-589); this build keeps them in a stream
+        object per ``encode`` / ``decode`` call — nothing of those outlives the call, so there is nothing to clear here —
+        and, for a streamed decode, in the ``DecodeStream`` the caller holds: ``DecodeStream.reset()`` is what starts a
+        new clip there.  Kept for API parity."""
+        self._conv_num = count_conv3d(self.decoder)
+        self._enc_conv_num = count_conv3d(self.encoder)
+
+
+def stream_frames(frames_in, n):
+    """Pixel frames that ``n`` >= 1 more latent frames complete in a stream that has taken ``frames_in`` >= 0 latent frames
+    of its clip: the clip's first latent frame is one pixel frame (its chunk skips the temporal upsamples, vae.py:105-125),
+    every other one four — 4 (n - 1) + 1 for a first push, 4 n afterwards."""
+    frames_in, n = int(frames_in), int(n)
+    if frames_in < 0 or n < 1:
+        raise ValueError(f"stream_frames: frames_in = {frames_in} >= 0 and n = {n} >= 1 expected")
+    return 4 * n - 3 if frames_in == 0 else 4 * n
+
+
+class DecodeStream:
+    """A decode that outlives one call: ``push(z)`` takes the next latent frames of a clip and returns the pixel frames they
+    complete, with every convolution's temporal history (and the first-chunk bypass of the temporal upsamples) kept in one
+    persistent ``_Stream`` in between.  The frames of any partition of a clip into pushes are those of ``WanVAE.decode`` on
+    the whole clip, bit for bit: causal convolutions over [history | frames] with a kernel choice that depends on the
+    layer's geometry alone, per-frame attention whose GEMMs accumulate in ascending k whichever tile they run on.
+
+    ``output="float"``: fp32 [3, frames, 8h, 8w] clamped to ``clamp`` = [-1, 1] (omh_cl_to_nchw; None: unclamped, what a
+    bare ``WanVAE_.decode`` returns — it is one push of the whole clip into a fresh stream); ``"uint8"``: packed RGB
+    [frames, 8h, 8w, 3] written by omh_cl_to_u8 straight from the head's output.  The arithmetic class is the model's
+    (``WanVAE(dtype=)``).  All launches go to the current torch stream, nothing synchronises with the host; the buffers
+    belong to the stream that was current when they were made, so keep one ``DecodeStream`` on one stream.
+
+    ``frames_in`` / ``frames_out``: latent frames taken and pixel frames returned since the clip began; ``h`` / ``w``: the
+    latent size, fixed by the first push."""
+
+    def __init__(self, model, scale, output="float", clamp=(-1.0, 1.0)):
+        if output not in ("float", "uint8"):
+            raise ValueError(f"DecodeStream: output = {output!r}, 'float' or 'uint8' expected")
+        self.model, self.scale, self.output = model, scale, output
+        self._clamp = (-3.0e38, 3.0e38) if clamp is None else (float(clamp[0]), float(clamp[1]))    # of the float frames
+        self.frames_in = self.frames_out = 0
+        self.h = self.w = None
+        self._st = None
+        self._mul = self._add = None
+
+    def reset(self):
+        """Start a new clip: the next push is a first chunk again.  The buffers are kept (their history frames are zeroed
+        on the current stream, the causal padding in front of a clip)."""
+        self.frames_in = self.frames_out = 0
+        if self._st is not None:
+            self._st.seen.clear()
+            for cs in self._st.convs.values():
+                if isinstance(cs, _ConvState) and cs.hist and cs.buf is not None:
+                    cs.off = 0
+                    cs.buf[:cs.hist].zero_()
+
+    def _windows(self):
+        return [] if self._st is None else [cs for cs in self._st.convs.values()
+                                            if isinstance(cs, _ConvState) and cs.hist and cs.buf is not None]
+
+    def state_bytes(self):
+        """Bytes held in the convolutions' history windows (each a [history | chunks] buffer that the region slides
+        through, ``_ConvState``)."""
+        return sum(cs.buf.numel() * cs.buf.element_size() for cs in self._windows())
+
+    def history_bytes(self):
+        """... of which the history frames proper: what a stream has to carry from one push to the next."""
+        return sum(cs.hist * cs.buf[0].numel() * cs.buf.element_size() for cs in self._windows())
+
+    @torch.no_grad()
+    def push(self, z):
+        """z [z_dim, n, h, w], n >= 1 latent frames on the model's device -> the pixel frames they complete
+        (``stream_frames``): fp32 [3, frames, 8h, 8w] or uint8 [frames, 8h, 8w, 3]."""
+        m = self.model
+        dev = m._device()
+        if dev.type != "cuda":
+            raise ops.OmhError("WanVAE runs on the MI355X only (no CPU fallback)")
+        if not isinstance(z, torch.Tensor) or z.dim() != 4 or z.shape[0] != m.z_dim or z.shape[1] < 1:
+            raise ValueError(f"DecodeStream.push: latent frames [{m.z_dim}, n >= 1, h, w] expected, got "
+                             f"{tuple(z.shape) if isinstance(z, torch.Tensor) else type(z).__name__}")
+        if z.device != dev:
+            raise ValueError(f"DecodeStream.push: z is on {z.device}, the model on {dev}")
+        _, n, h, w = z.shape
+        if self._st is None:
+            self._st = _Stream(dev, f32=m._f32())
+            self.h, self.w = h, w
+            scale = self.scale
+            if isinstance(scale[0], torch.Tensor):
+                self._mul = (1.0 / scale[1]).to(device=dev, dtype=torch.float32).contiguous()
+                self._add = scale[0].to(device=dev, dtype=torch.float32).contiguous()
+            else:
+                self._mul = torch.full((m.z_dim,), 1.0 / float(scale[1]), device=dev)
+                self._add = torch.full((m.z_dim,), float(scale[0]), device=dev)
+        elif (h, w) != (self.h, self.w):
+            raise ValueError(f"DecodeStream.push: latent frames of {h} x {w}, this stream began with {self.h} x {self.w}")
+        st, dec = self._st, m.decoder
+        lat = z.to(dtype=torch.float32).contiguous()
+        zcl = (ops.nchw_to_cl_f32 if st.f32 else ops.nchw_to_cl)(lat, n, 0, _round_up(m.z_dim, 8), mul=self._mul, add=self._add)
+        x_all = _conv_on(st, "conv2", m.conv2, zcl, out_f32=st.f32)
+        frames = stream_frames(self.frames_in, n)
+        if self.output == "uint8":
+            out = torch.empty(frames, 8 * h, 8 * w, 3, dtype=torch.uint8, device=dev)
         else:
-            mul = torch.full((self.z_dim,), 1.0 / float(scale[1]), device=dev)
-            add = torch.full((self.z_dim,), float(scale[0]), device=dev)
-        st = _Stream(dev, f32=self._f32())
-        dec = self.decoder
-        zc = _round_up(self.z_dim, 8)
-        zcl = (ops.nchw_to_cl_f32 if st.f32 else ops.nchw_to_cl)(lat, Tl, 0, zc, mul=mul, add=add)   # z/scale1 + scale0
-        x_all = _conv_on(st, "conv2", self.conv2, zcl, out_f32=st.f32)                     # [T', h, w, z]
-        T_out = 4 * (Tl - 1) + 1
-        out = torch.empty(3, T_out, 8 * h, 8 * w, dtype=torch.float32, device=dev)
-        lo, hi = (-3.0e38, 3.0e38) if clamp is None else clamp
-        t_pix = 0
-        # Latent-resolution front (conv1, middle, the residual blocks before the first Resample) over ALL latent
-        # frames in one pass — same values as frame by frame (causal convolutions, per-frame attention), 21x the
-        # rows per launch; from the first Resample on, one latent frame per step as the reference (its first chunk
-        # skips the temporal upsample, vae.py:105-125).
+            out = torch.empty(3, frames, 8 * h, 8 * w, dtype=torch.float32, device=dev)
+        # Latent-resolution front (conv1, middle, the residual blocks before the first Resample) over ALL n latent frames
+        # in one pass — same values as frame by frame (causal convolutions, per-frame attention), n x the rows per launch.
         n_front = _first_resample(dec.upsamples)
         c1 = st.conv("decoder.conv1", dec.conv1)
-        _fill(c1.slot(Tl, h, w, dev), x_all)
+        _fill(c1.slot(n, h, w, dev), x_all)
         y_all = c1.run(out_f32=st.trunk_f32)
         y_all = _run_sequential(st, "decoder.middle", dec.middle, y_all)
         y_all = _run_sequential(st, "decoder.upsamples", dec.upsamples, y_all, stop=n_front)
         # From the first Resample to just past the second one (the 2h x 2w stage: 49 920 voxels per latent frame at
-        # 480x832 — 195 workgroups of 256 rows on 256 CUs) the latent frames go _GROUP at a time, the first one
-        # alone (its chunk skips the temporal upsamples); the full-resolution rest takes _GROUP2 latent frames per step
-        # (the reference: one).  Causal convolutions over [history | frames]: same values either way.
+        # 480x832 — 195 workgroups of 256 rows on 256 CUs) the latent frames go _GROUP at a time, the clip's first one
+        # alone (its chunk skips the temporal upsamples, vae.py:105-125); the full-resolution rest takes _GROUP2 latent
+        # frames per step (the reference: one).  Causal convolutions over [history | frames]: same values either way,
+        # so where a push's boundaries cut the groups does not matter, and the limits make any n legal.
         res_idx = [i for i, layer in enumerate(dec.upsamples) if isinstance(layer, Resample)]
         n_mid = res_idx[1] + 1 if len(res_idx) > 1 else len(dec.upsamples)
+        t_pix = 0
         i = 0
-        while i < Tl:
-            g = 1 if i == 0 else min(2 if (st.f32 and not (_PAIR and _F32_GROUPS[1])) else _GROUP, Tl - i)
+        while i < n:
+            first = self.frames_in == 0 and i == 0
+            g = 1 if first else min(2 if (st.f32 and not (_PAIR and _F32_GROUPS[1])) else _GROUP, n - i)
             ymid = _run_sequential(st, "decoder.upsamples", dec.upsamples, y_all[i:i + g], start=n_front, stop=n_mid)
             per = ymid.shape[0] // g
             j = 0
@@ -714,18 +807,17 @@ class WanVAE_(nn.Module):
                 y, pre = _run_sequential(st, "decoder.upsamples", dec.upsamples, ymid[j * per:(j + g2) * per], start=n_mid,
                                          head=("decoder.head", dec.head))
                 y = _head(st, "decoder.head", dec.head, y, out_f32=True, pre=pre)        # fp32 [t, 8h, 8w, 3]
-                ops.cl_to_nchw(y, out, t_pix, 3, lo=lo, hi=hi)
+                if self.output == "uint8":
+                    ops.cl_to_u8(y, out, t_pix, 3, lo=-1.0, hi=1.0)
+                else:
+                    ops.cl_to_nchw(y, out, t_pix, 3, lo=self._clamp[0], hi=self._clamp[1])
                 t_pix += y.shape[0]
                 j += g2
             i += g
-        assert t_pix == T_out
-        return out.unsqueeze(0)
-
-    def clear_cache(self):
-        """The reference resets its per-call feature caches here (vae.py:582-589); this build keeps
-        them in a per-call stream object, so there is nothing to clear.  Kept for API parity."""
-        self._conv_num = count_conv3d(self.decoder)
-        self._enc_conv_num = count_conv3d(self.encoder)
+        assert t_pix == frames
+        self.frames_in += n
+        self.frames_out += frames
+        return out
 
 
 def _video_vae(pretrained_path=None, z_dim=None, device="cpu", **kwargs):
@@ -773,6 +865,14 @@ class WanVAE:
     def decode(self, zs):
         """zs: list of [z, T', h, w] -> list of fp32 [3, 4(T'-1)+1, 8h, 8w] clamped to [-1, 1]."""
         return [self.model.decode(u.unsqueeze(0), self.scale, clamp=(-1.0, 1.0)).float().squeeze(0) for u in zs]
+
+    def decode_stream(self, output="float"):
+        """A ``DecodeStream`` over this VAE: ``push(z)`` the latent frames of a clip as they arrive ([z, n, h, w], any
+        n >= 1 per push) and get the pixel frames they complete — 4 (n - 1) + 1 from the first push, 4 n from every later
+        one — equal bit for bit to ``decode`` of the whole clip.  ``output``: "float" (fp32 [3, frames, 8h, 8w] clamped to
+        [-1, 1]) or "uint8" (packed RGB [frames, 8h, 8w, 3], the reference's wan/utils/utils.py:40-47 rule on the device).
+        Streams of one VAE are independent."""
+        return DecodeStream(self.model, self.scale, output=output)
 
 
 def bench_decode(latent, device, iters=1, telemetry=None, dtype=torch.bfloat16):
