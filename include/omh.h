@@ -878,7 +878,8 @@ int omh_layernorm_modulate_bwd(const float* x, const float* dy, float* dx_accum,
                                float eps, float mul_const, const float* mul0, const float* mul1, int64_t mul1_stride,
                                float* dmul, float* dadd, int64_t dstride, int64_t rows_per_batch, omh_stream_t stream);
 /* Backward of omh_rmsnorm_rope: dy fp32 [rows, dim] (grad of the rotated, normalised output) ->
- * dx bf16 [rows, lddx]; dweight[c] += ... (may be NULL). */
+ * dx bf16 [rows, lddx]; dweight[c] += ... (may be NULL).  With a rotary table, head_dim % 4 == 0 and
+ * dim % head_dim == 0 as in the forward (OMH_E_BADARG otherwise; omh_rmsnorm_rope_bwd_t alike). */
 int omh_rmsnorm_rope_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, void* dx_bf16, int64_t lddx,
                          float* dweight, int64_t rows, int32_t dim, const float* weight, float eps, int32_t do_norm,
                          const float* rope_cos, const float* rope_sin, int32_t rope_len, int32_t head_dim,

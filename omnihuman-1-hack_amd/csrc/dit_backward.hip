@@ -862,7 +862,8 @@ static int rmsnorm_rope_bwd_launch(const void* x, int64_t ldx, const void* dy, i
                                    int32_t head_dim, const int32_t* grid, int32_t seq_len, omh_stream_t stream) {
     if (!x || !dy || !dx_bf16 || rows <= 0 || dim <= 0) return OMH_E_BADARG;
     if ((dim & 3) || dim > MAXV * 256 || (ldx & 3) || (lddy & 3) || (lddx & 3)) return OMH_E_SHAPE;
-    if (rope_cos && (!rope_sin || !grid || seq_len <= 0 || head_dim <= 0)) return OMH_E_BADARG;
+    if (rope_cos && (!rope_sin || !grid || seq_len <= 0 || head_dim <= 0 || (head_dim & 3) || dim % head_dim))
+        return OMH_E_BADARG;                                        // as the forward: a float4 never straddles two heads
     omh_clear_status();
     auto kern = dim <= 6 * 256 ? rmsnorm_rope_bwd_kernel<6, XT, GT>
                                : (dim <= 20 * 256 ? rmsnorm_rope_bwd_kernel<20, XT, GT> : rmsnorm_rope_bwd_kernel<MAXV, XT, GT>);

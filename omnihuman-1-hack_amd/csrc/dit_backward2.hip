@@ -66,6 +66,9 @@ __global__ __launch_bounds__(256)
 void ln_bwd2_kernel(const omh_ln_bwd_args a, const int nj) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NP = 2 + (GATE ? 1 : 0);
+    // the old dx of a row is requested with its other operands up to 20 chunks per lane; the 32-chunk instantiations hold
+    // 256 registers of sums alone and spill 1 - 3 KB per lane: they fetch it where it is used
+    constexpr bool DX_UP_FRONT = NV <= 20;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = blockIdx.x, b = blockIdx.y;
     const int dim = a.dim, nv = dim >> 2;
@@ -96,7 +99,7 @@ void ln_bwd2_kernel(const omh_ln_bwd_args a, const int nj) {
             if (c < nv) {
                 v[i] = ((const float4*)xr)[c];
                 g[i] = ld4t<GT>(gr, c);
-                o[i] = ((const float4*)dxr)[c];
+                if (DX_UP_FRONT) o[i] = ((const float4*)dxr)[c];
                 if (GATE) yn[i] = ld4t<uint16_t>((const uint16_t*)a.y_next + row * dim, c);
             }
         }
@@ -134,7 +137,7 @@ void ln_bwd2_kernel(const omh_ln_bwd_args a, const int nj) {
         for (int i = 0; i < NV; ++i) {
             const int c = lane + 64 * i;
             if (c < nv) {
-                float4 r = o[i];
+                float4 r = DX_UP_FRONT ? o[i] : ((const float4*)dxr)[c];
                 r.x += rstd * (g[i].x - mg - v[i].x * mgx);
                 r.y += rstd * (g[i].y - mg - v[i].y * mgx);
                 r.z += rstd * (g[i].z - mg - v[i].z * mgx);
@@ -155,6 +158,110 @@ void ln_bwd2_kernel(const omh_ln_bwd_args a, const int nj) {
         }
     }
     combine_and_store<NV, NP>(acc, lds, a.workspace + ((int64_t)b * nj + j) * NP * dim, dim, nv, lane, wave);
+}
+
+// The same for widths above 5120 (21 - 32 float4 chunks per lane; no Wan model has one).  ln_bwd2_kernel<32, ...> kept
+// 256 registers of sums beside the row's 256 of x and dy and spilled 1.1 - 2.9 KB per lane, and two of its twelve
+// instantiations (plain, 2 rows per wave, fp32 and bf16 dy) returned a wrong component of one float4 of dmul in all
+// lanes (tests/test_gpu_norm_exact.py; no index in the source explains it).  This kernel holds nothing per column: a
+// wave walks its row chunk by chunk in each pass (the row stays in L2 between them) and the per-column sums live in
+// the LDS buffer [NP][dim], to which the four waves add their rows one after the other (wave 3, 2, 1, 0 with a barrier
+// between: a fixed order, bit-repeatable like the register form).  Same geometry: 4 * rpw rows of one batch element per
+// workgroup, one partial per workgroup in the workspace.
+template <typename GT, bool NEXT, bool GATE>
+__global__ __launch_bounds__(256)
+void ln_bwd2_wide_kernel(const omh_ln_bwd_args a, const int nj, const int rpw) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int NP = 2 + (GATE ? 1 : 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = blockIdx.x, b = blockIdx.y;
+    const int dim = a.dim, nv = dim >> 2;
+    const int64_t rpb = a.rows_per_batch;
+    const int64_t base = (int64_t)b * rpb + (int64_t)j * (4 * rpw);
+    const int64_t end = min((int64_t)(b + 1) * rpb, a.rows);
+    const float4* m0 = (const float4*)a.mul0;
+    const float4* m1 = a.mul1 ? (const float4*)(a.mul1 + (int64_t)b * a.mul1_stride) : nullptr;
+    const float4* g0 = (const float4*)a.gate0;
+    const float4* g1 = a.gate1 ? (const float4*)(a.gate1 + (int64_t)b * a.gate1_stride) : nullptr;
+    float4* sums = (float4*)lds;
+    for (int i = threadIdx.x; i < NP * nv; i += 256) sums[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    auto mul_of = [&](int c) {
+        float4 mu = make_float4(a.mul_const, a.mul_const, a.mul_const, a.mul_const);
+        if (m0) acc4(mu, m0[c]);
+        if (m1) acc4(mu, m1[c]);
+        return mu;
+    };
+    for (int rr = 0; rr < rpw; ++rr) {
+        const int64_t row = base + wave + 4 * rr;
+        const bool active = row < end;                                  // wave-uniform
+        const float4* xr = (const float4*)(a.x + row * dim);
+        const GT* gr = (const GT*)a.dy + row * dim;
+        float4* dxr = (float4*)(a.dx + row * dim);
+        float mean = 0.f, rstd = 0.f, mg = 0.f, mgx = 0.f;
+        if (active) {
+            float s = 0.f;
+            for (int c = lane; c < nv; c += 64) { const float4 v = xr[c]; s += v.x + v.y + v.z + v.w; }
+            mean = wave_sum(s) / dim;
+            float q = 0.f;
+            for (int c = lane; c < nv; c += 64) {
+                float4 v = xr[c];
+                v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
+                q += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            }
+            rstd = rsqrtf(wave_sum(q) / dim + a.eps);
+            float sg = 0.f, sgx = 0.f;
+            for (int c = lane; c < nv; c += 64) {
+                float4 v = xr[c];
+                const float4 d = ld4t<GT>(gr, c), mu = mul_of(c);
+                v.x = (v.x - mean) * rstd; v.y = (v.y - mean) * rstd; v.z = (v.z - mean) * rstd; v.w = (v.w - mean) * rstd;
+                const float4 g = make_float4(d.x * mu.x, d.y * mu.y, d.z * mu.z, d.w * mu.w);
+                sg += g.x + g.y + g.z + g.w;
+                sgx += g.x * v.x + g.y * v.y + g.z * v.z + g.w * v.w;
+            }
+            mg = wave_sum(sg) / dim;
+            mgx = wave_sum(sgx) / dim;
+        }
+#pragma unroll 1
+        for (int w = 3; w >= 0; --w) {
+            if (wave == w && active) {
+                for (int c = lane; c < nv; c += 64) {
+                    float4 v = xr[c];
+                    const float4 d = ld4t<GT>(gr, c), mu = mul_of(c);
+                    v.x = (v.x - mean) * rstd; v.y = (v.y - mean) * rstd; v.z = (v.z - mean) * rstd; v.w = (v.w - mean) * rstd;
+                    const float4 g = make_float4(d.x * mu.x, d.y * mu.y, d.z * mu.z, d.w * mu.w);
+                    float4 t = sums[c];
+                    t.x += d.x * v.x; t.y += d.y * v.y; t.z += d.z * v.z; t.w += d.w * v.w;
+                    sums[c] = t;
+                    t = sums[nv + c];
+                    acc4(t, d);
+                    sums[nv + c] = t;
+                    float4 r = dxr[c];
+                    r.x += rstd * (g.x - mg - v.x * mgx);
+                    r.y += rstd * (g.y - mg - v.y * mgx);
+                    r.z += rstd * (g.z - mg - v.z * mgx);
+                    r.w += rstd * (g.w - mg - v.w * mgx);
+                    dxr[c] = r;
+                    if (NEXT) {
+                        float4 gt = make_float4(a.gate_const, a.gate_const, a.gate_const, a.gate_const);
+                        if (g0) acc4(gt, g0[c]);
+                        if (g1) acc4(gt, g1[c]);
+                        ((uint2*)((uint16_t*)a.dy_next + row * dim))[c] =
+                            make_uint2(pack_bf2(r.x * gt.x, r.y * gt.y), pack_bf2(r.z * gt.z, r.w * gt.w));
+                        if (GATE) {
+                            const float4 yn = ld4t<uint16_t>((const uint16_t*)a.y_next + row * dim, c);
+                            t = sums[2 * nv + c];
+                            t.x += r.x * yn.x; t.y += r.y * yn.y; t.z += r.z * yn.z; t.w += r.w * yn.w;
+                            sums[2 * nv + c] = t;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    float4* part = (float4*)(a.workspace + ((int64_t)b * nj + j) * NP * dim);
+    for (int i = threadIdx.x; i < NP * nv; i += 256) part[i] = sums[i];
 }
 
 // out_k[b * stride_k + c] += sum_j part[((b * nj + j) * NP + k) * dim + c]   in a FIXED order: a workgroup takes 64
@@ -338,6 +445,21 @@ int launch_ln(const omh_ln_bwd_args& a, int nj, int nb, hipStream_t s) {
     return gate ? 3 : 2;
 }
 
+int launch_ln_wide(const omh_ln_bwd_args& a, int nj, int nb, hipStream_t s) {
+    const bool next = a.dy_next != nullptr, gate = next && a.y_next && a.dgate;
+    const dim3 grid((unsigned)nj, (unsigned)nb), blk(256);
+    const size_t lds = (size_t)(gate ? 3 : 2) * a.dim * sizeof(float);
+    const int rpw = ln_rows_per_wg(a.rows) / 4;
+#define OMH_LN2W(GT, NEXT, GATE) hipLaunchKernelGGL((ln_bwd2_wide_kernel<GT, NEXT, GATE>), grid, blk, lds, s, a, nj, rpw)
+    if (a.dy_bf16) {
+        if (gate) OMH_LN2W(uint16_t, true, true); else if (next) OMH_LN2W(uint16_t, true, false); else OMH_LN2W(uint16_t, false, false);
+    } else {
+        if (gate) OMH_LN2W(float, true, true); else if (next) OMH_LN2W(float, true, false); else OMH_LN2W(float, false, false);
+    }
+#undef OMH_LN2W
+    return gate ? 3 : 2;
+}
+
 template <int NV>
 void launch_rms(const omh_rms_bwd_args& a, int nj, hipStream_t s) {
     const dim3 grid((unsigned)nj, (unsigned)a.n_seg), blk(256);
@@ -374,7 +496,7 @@ extern "C" int omh_layernorm_modulate_bwd2(const omh_ln_bwd_args* args, omh_stre
     hipStream_t s = (hipStream_t)stream;
     omh_clear_status();
     const int np = a.dim <= 6 * 256 ? launch_ln<6>(a, (int)nj, (int)nb, s)
-                                    : (a.dim <= 20 * 256 ? launch_ln<20>(a, (int)nj, (int)nb, s) : launch_ln<MAXV2>(a, (int)nj, (int)nb, s));
+                                    : (a.dim <= 20 * 256 ? launch_ln<20>(a, (int)nj, (int)nb, s) : launch_ln_wide(a, (int)nj, (int)nb, s));
     if (a.deferred) {
         omh_partial_reduce& d = *a.deferred;
         d.part = a.workspace; d.nj = (int)nj; d.np = np; d.nb = (int)nb; d.dim = a.dim; d.grid_y = (int)(nb * np);
