@@ -59,6 +59,8 @@ int omh_set_deterministic(int on);
  *   GEMM_KERNEL ("w64" / "8w")   GEMM_TILE ("big" / "small" / "tiny")   GEMM_RULE   GEMM_GROUP_M   GEMM_SPLITK ("0")
  *   GEMM_QKV ("0" / "1")   GEMM_W64_R192 / N192 / BF16M / GBWD / GAUX ("0" / "1")   GEMM_W64_P256 (experiment builds only)
  *   RMS_PAIR_ROW ("0" / "1": omh_rmsnorm_rope_bf16_pair's two-workgroup / one-wave-per-row form)
+ *   RMS_PAIR_BOUND ("0": omh_rmsnorm_rope_bf16_pair_bound's one-wave-per-row form; "2": its persistent form without the
+ *                   next-row prefetch; unset: the persistent form at dim <= 1536; the same bits, A/B timing)
  *   GEMM_TN_W64 ("0" / "1")   GEMM_TN_TILE   GEMM_TN_GROUP_TILE ("big" / "small")   GEMM_TN_SPLIT (count)
  *   CONV_TILE ("w64" / "wide" / "small")   CONV_W64   CONV_WIDE_MIN   CONV_FUSE_NORM   CONV_KW3   CONV_PERSIST
  *   CONV_W64_UP2   LN_RPW ("1" / "2" / "4")   DETERMINISTIC ("0" / "1")
@@ -592,11 +594,14 @@ int omh_rmsnorm_rope_bf16_pair(const void* x_bf16, int64_t ldx, int64_t seg_x, v
                                int32_t dim, const float* weight0, const float* weight1, float eps, int32_t do_norm,
                                const float* rope_cos, const float* rope_sin, int32_t rope_len, int32_t head_dim,
                                const int32_t* grid, int32_t seq_len, float out_scale0, float out_scale1, omh_stream_t stream);
-/* Additive to ABI v12: the same q and k, bit for bit (always in the one-wave-per-row form; rotary table required, head_dim
- * 128, dim <= 5120), plus norm2_max float [rows / seq_len][dim / 128][2]: per (sample, head) the maximum over the sample's
- * rows of the squared norm of that head's slice of y0 (index 0) and of y1 (index 1), taken on the values as stored (after
- * gain, RoPE, out_scale and the rounding to bf16).  The CALLER zeroes the buffer before the launch; the kernel
- * folds into it with an order-independent maximum (bitwise repeatable).  Feeds omh_flash_attn_fwd_d128_bounded. */
+/* Additive to ABI v12: the same q and k, bit for bit (one wave per row whatever the row count; rotary table required,
+ * head_dim 128, dim <= 5120), plus norm2_max float [rows / seq_len][dim / 128][2]: per (sample, head) the maximum over the
+ * sample's rows of the squared norm of that head's slice of y0 (index 0) and of y1 (index 1), taken on the values as stored
+ * (after gain, RoPE, out_scale and the rounding to bf16).  The CALLER zeroes the buffer before the launch (still: the kernel
+ * never stores, it only raises); the kernel folds into it with an UNSIGNED maximum on the bit pattern, which for these
+ * non-negative floats is the exact maximum whatever the order (bitwise repeatable).  At dim <= 1536 the launch is a
+ * persistent grid whose waves keep their maxima in registers and combine them once per sample they walk through; wider
+ * rows combine once per row (option RMS_PAIR_BOUND).  Feeds omh_flash_attn_fwd_d128_bounded. */
 int omh_rmsnorm_rope_bf16_pair_bound(const void* x_bf16, int64_t ldx, int64_t seg_x, void* y0_bf16, void* y1_bf16,
                                      int64_t rows, int32_t dim, const float* weight0, const float* weight1, float eps,
                                      int32_t do_norm, const float* rope_cos, const float* rope_sin, int32_t rope_len,

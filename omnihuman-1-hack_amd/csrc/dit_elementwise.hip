@@ -481,6 +481,231 @@ void rmsnorm_rope_pair_row_bound_kernel(const uint16_t* __restrict__ x, int64_t 
     finish(hb, y1, w1, scale1, 1);
 }
 
+// The bound kernel for dim <= 1 536 in its PERSISTENT form (the default; option RMS_PAIR_BOUND = "0" runs the kernel above).
+// What the kernel above pays for the bound: on a freshly zeroed buffer every wave of the first rounds beats
+// the slot it reads and issues its atomics (94 us on a buffer that holds the maxima, 148 us on zeros), and its exchange
+// selects between array ELEMENTS, which indexes the register array at run time (1 300 VALU instructions per row against
+// the plain kernel's 820).  Here the grid is what the chip holds (PAIR_BOUND_WG_PER_CU workgroups per CU, whatever `rows`),
+// wave w of the launch walks rows w, w + waves, ..., and the lane that holds a (head, segment) sum after the 32-lane
+// exchange folds it into a running maximum in a REGISTER — no memory operation per row.  The maxima are per sample: when the
+// walk enters another sample (b = row / seq_len changes) the wave flushes them — the kernel above's
+// read-then-atomic-if-larger on the bit pattern — and starts again from zero; one more flush, per workgroup, ends the walk.
+// A wave without rows never touches the buffer.  The maximum is taken on the unsigned bit pattern in the register too: the
+// buffer holds what the kernel above leaves, bit for bit, whatever the order.
+// PREFETCH: the 12 loads of the next row and its four rotary-table entries are issued before the current row's arithmetic,
+// and the body itself issues no vector-memory load (the gains come from LDS): a load in the body would be waited for in
+// issue order, behind the prefetch.  Measured at 32 760 x 2 x 1 536: 81 us with, 88 us without it.
+// The q and k bits do not depend on what the compiler contracts here (the build's -ffp-contract=fast lets the backend fuse any
+// multiply with any add, and a loop around a body has changed such decisions before).  In rmsnorm_rope_pair_row_kernel's ISA
+// the sums of squares and the products with rinv and the gain are plain multiplies and adds, and the rotation is
+// fma(re, cs, -(im sn)), fma(im, cs, re sn).  The rotation is WRITTEN as those two fused operations here, which leaves the
+// compiler nothing to decide: a product that is an fma's addend cannot be fused again.  Every other multiply that feeds
+// an add is the square of a bf16 value, exact in fp32, so fma(a, a, c) and a a + c are the same bits; the rest are chains
+// of multiplies, and a division before the add of eps.  (Packed or not does not change a bit either.)  The sums for the
+// bound are such squares too, added in the order of the kernel above.
+constexpr int PAIR_BOUND_WG_PER_CU = 4;        // two rows of 24 registers in flight per wave: 128 registers, four waves per SIMD
+template <bool PREFETCH>
+__global__ __launch_bounds__(256, PAIR_BOUND_WG_PER_CU)
+void rmsnorm_rope_pair_bound_persistent_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t seg_x,
+                                               uint16_t* __restrict__ y0, uint16_t* __restrict__ y1, int64_t rows, int dim,
+                                               const float* __restrict__ w0, const float* __restrict__ w1, float eps,
+                                               int do_norm, const float* __restrict__ rope_cos,
+                                               const float* __restrict__ rope_sin, int rope_len, int head_dim,
+                                               const int* __restrict__ grid, int seq_len, float scale0, float scale1,
+                                               float* __restrict__ norm2_max) {
+    constexpr int MAXV = 6, P = 8;
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * 4;
+    int64_t row = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nv = dim >> 2, heads = dim >> 7;
+    // the two gain vectors, once per workgroup instead of once per row (12 KB: as many bytes as the row itself reads and
+    // writes), and out of the vector-memory queue: a load in the body would make the wave wait for the prefetch issued before it
+    __shared__ float4 gains[2][MAXV * 64];
+    if ((int64_t)blockIdx.x * 4 >= rows) return;                     // (workgroup-uniform) no rows: nothing is touched
+    for (int c = threadIdx.x; c < nv; c += 256) {
+        if (w0) gains[0][c] = ((const float4*)w0)[c];
+        if (w1) gains[1][c] = ((const float4*)w1)[c];
+    }
+    __syncthreads();
+    const bool has_rows = row < rows;                                // (wave-uniform; the others only meet the barriers)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int hc = head_dim >> 1, c3 = hc / 3, cf = hc - 2 * c3;
+    uint2 ha[MAXV], hb[MAXV], na[MAXV], nb[MAXV];
+    auto fetch = [&](int64_t r, uint2 (&a)[MAXV], uint2 (&b)[MAXV]) {
+        const uint2* xa = (const uint2*)(x + r * ldx);
+        const uint2* xb = (const uint2*)(x + seg_x + r * ldx);
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            a[i] = c < nv ? xa[c] : make_uint2(0u, 0u);
+        }
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            b[i] = c < nv ? xb[c] : make_uint2(0u, 0u);
+        }
+    };
+    // token position and the lane's two complex pairs (the same for every vector of the lane and for both segments): fetched
+    // with the row, so that the body issues no vector-memory load — and fetched whether the token is rotated or not (the
+    // index is clamped into the table either way), so that nothing has to wait for the entries before the body uses them
+    struct Rope { bool rot; float cs[2], sn[2]; int b; };
+    auto entries = [&](int64_t r) {
+        Rope t;
+        t.b = (int)(r / seq_len);
+        const int sidx = (int)(r % seq_len);
+        const int gf = grid[3 * t.b], gh = grid[3 * t.b + 1], gw = grid[3 * t.b + 2];
+        t.rot = sidx < gf * gh * gw;
+        const int ghw = max(gh * gw, 1), gw1 = max(gw, 1), gh1 = max(gh, 1);   // (rot: the values themselves)
+        const int pf = sidx / ghw, ph = (sidx / gw1) % gh1, pw = sidx % gw1;
+        const int p0 = ((4 * lane) % head_dim) >> 1;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int pc = p0 + e;
+            const int pos = pc < cf ? pf : (pc < cf + c3 ? ph : pw);
+            const int idx = min(pos, rope_len - 1) * hc + pc;
+            t.cs[e] = rope_cos[idx]; t.sn[e] = rope_sin[idx];
+        }
+        return t;
+    };
+    // where the exchange below leaves this lane: the sum of vector vi over its half-wave, i.e. of head 2 vi + lane / 32
+    // (the same in all four lanes of a group: the first of them keeps the maximum)
+    const int vi = ((lane & 16) ? 4 : 0) + ((lane & 8) ? 2 : 0) + ((lane & 4) ? 1 : 0);
+    const int head = 2 * vi + (lane >> 5);
+    const bool holder = (lane & (32 / P - 1)) == 0 && vi < MAXV && head < heads;
+    unsigned int mx[2] = {0u, 0u};                                   // running maxima of sample `cur`, bit patterns
+    auto flush = [&](int sample) {
+        if (holder) {
+#pragma unroll
+            for (int seg = 0; seg < 2; ++seg) {
+                unsigned int* slot = (unsigned int*)norm2_max + ((int64_t)sample * heads + head) * 2 + seg;
+                if (mx[seg] > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, mx[seg]);
+            }
+        }
+    };
+    int cur = -1;
+    if (has_rows) {
+        Rope rp = entries(row), nrp = rp;
+        fetch(row, ha, hb);
+        cur = rp.b;
+        for (;;) {
+            const int64_t next = row + stride;
+            if (PREFETCH && next < rows) {
+                nrp = entries(next);
+                fetch(next, na, nb);
+            }
+            if (rp.b != cur) {                                       // (wave-uniform) the walk enters another sample
+                flush(cur);
+                mx[0] = 0u; mx[1] = 0u;
+                cur = rp.b;
+            }
+            const bool rot = rp.rot;
+            const float cs2[2] = {rp.cs[0], rp.cs[1]}, sn2[2] = {rp.sn[0], rp.sn[1]};
+            auto finish = [&](uint2 (&h)[MAXV], uint16_t* __restrict__ y, const float* __restrict__ weight, float out_scale,
+                              int seg) {
+                float4 v[MAXV];
+                float q = 0.f;
+#pragma unroll
+                for (int i = 0; i < MAXV; ++i) {
+                    const int c = lane + 64 * i;
+                    if (c < nv) {
+                        v[i] = make_float4(bf2f((uint16_t)(h[i].x & 0xffff)), bf2f((uint16_t)(h[i].x >> 16)),
+                                           bf2f((uint16_t)(h[i].y & 0xffff)), bf2f((uint16_t)(h[i].y >> 16)));
+                        q += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
+                    }
+                }
+                const float rinv = (do_norm ? rsqrtf(wave_sum(q) / dim + eps) : 1.0f) * out_scale;
+                const float4* wv = weight ? gains[seg] : nullptr;
+                uint2* yr = (uint2*)(y + row * dim);
+                float r[P];                                          // per-vector sums of squares of the stored values
+#pragma unroll
+                for (int i = 0; i < P; ++i) r[i] = 0.f;
+#pragma unroll
+                for (int i = 0; i < MAXV; ++i) {
+                    const int c = lane + 64 * i;
+                    if (c < nv) {
+                        float4 t = v[i];
+                        t.x *= rinv; t.y *= rinv; t.z *= rinv; t.w *= rinv;
+                        if (wv) { const float4 g = wv[c]; t.x *= g.x; t.y *= g.y; t.z *= g.z; t.w *= g.w; }
+                        if (rot) {
+#pragma unroll
+                            for (int e = 0; e < 2; ++e) {
+                                const float cs = cs2[e], sn = sn2[e];
+                                float& re = e == 0 ? t.x : t.z;
+                                float& im = e == 0 ? t.y : t.w;
+                                const float nr = __builtin_fmaf(re, cs, -(im * sn));
+                                const float ni = __builtin_fmaf(im, cs, re * sn);
+                                re = nr; im = ni;
+                            }
+                        }
+                        uint2 o;
+                        o.x = pack_bf2(t.x, t.y);
+                        o.y = pack_bf2(t.z, t.w);
+                        yr[c] = o;
+                        {
+                            // from the STORED bf16 values, behind the compiler barrier of the kernel above
+                            uint32_t px = o.x, py = o.y;
+                            asm volatile("" : "+v"(px), "+v"(py));
+                            const float a0 = __uint_as_float(px << 16), a1 = __uint_as_float(px & 0xffff0000u);
+                            const float a2 = __uint_as_float(py << 16), a3 = __uint_as_float(py & 0xffff0000u);
+                            r[i] = a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
+                        }
+                    }
+                }
+                // the exchange of the kernel above (P = 8): halves at lane distance 16, 8, 4, then plain adds at 2 and 1
+                int n = P;
+#pragma unroll
+                for (int o = 16; o > 0; o >>= 1) {
+                    if (n > 1) {
+                        n >>= 1;
+                        const bool up = (lane & o) != 0;
+#pragma unroll
+                        for (int j = 0; j < n; ++j) {
+                            // (VALUES first: `up ? r[j + n] : r[j]` selects between two lvalues, i.e. an address, and the array
+                            // then is indexed at run time — eight compares and selects per read in the kernel above)
+                            const float lo = r[j], hi = r[j + n];
+                            const float keep = up ? hi : lo, send = up ? lo : hi;
+                            r[j] = keep + __shfl_xor(send, o, 64);
+                        }
+                    } else {
+                        r[0] += __shfl_xor(r[0], o, 64);
+                    }
+                }
+                mx[seg] = max(mx[seg], __float_as_uint(r[0]));
+            };
+            finish(ha, y0, w0, scale0, 0);
+            finish(hb, y1, w1, scale1, 1);
+            if (next >= rows) break;
+            row = next;
+            if (PREFETCH) {
+                rp = nrp;
+#pragma unroll
+                for (int i = 0; i < MAXV; ++i) { ha[i] = na[i]; hb[i] = nb[i]; }
+            } else {
+                rp = entries(row);
+                fetch(row, ha, hb);
+            }
+        }
+    }
+    // the end of the walk: ONE combine per workgroup and sample instead of one per wave (the waves of a launch end together,
+    // and a slot that still holds the caller's zero is beaten by every one of them).  The four waves' last rows are
+    // neighbours, so as a rule they end in the same sample: the first wave of a sample takes the others' maxima and flushes.
+    __shared__ unsigned int end_mx[4][2][64];
+    __shared__ int end_cur[4];
+    end_mx[wave][0][lane] = mx[0];
+    end_mx[wave][1][lane] = mx[1];
+    if (lane == 0) end_cur[wave] = cur;
+    __syncthreads();
+    if (!has_rows) return;
+    for (int u = 0; u < wave; ++u)
+        if (end_cur[u] == cur) return;                               // (wave-uniform) an earlier wave speaks for this sample
+    for (int u = wave + 1; u < 4; ++u)
+        if (end_cur[u] == cur) {
+            mx[0] = max(mx[0], end_mx[u][0][lane]);
+            mx[1] = max(mx[1], end_mx[u][1][lane]);
+        }
+    flush(cur);
+}
+
 // ------------------------------------------------------------------ cast
 __global__ __launch_bounds__(256)
 void cast_f32_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int64_t n) {
@@ -764,6 +989,21 @@ extern "C" int omh_rmsnorm_rope_bf16_pair_bound(const void* x_bf16, int64_t ldx,
     if ((dim & 3) || (ldx & 3) || (seg_x & 3) || head_dim != 128 || dim % 128 || dim > 20 * 256) return OMH_E_SHAPE;
     if (((uintptr_t)x_bf16 & 7) || ((uintptr_t)y0 & 7) || ((uintptr_t)y1 & 7) || ((uintptr_t)norm2_max & 3)) return OMH_E_ALIGN;
     omh_clear_status();
+    // dim <= 1 536: the persistent form, a grid of what the chip holds whatever `rows` (RMS_PAIR_BOUND = "0": the
+    // one-wave-per-row form, "2": the persistent form without its prefetch — the same bits, for A/B timing)
+    {
+        const char* pb = omh_opt(OMH_OPT_RMS_PAIR_BOUND);
+        if (dim <= 6 * 256 && !(pb && pb[0] == '0')) {
+            const bool pf = !(pb && pb[0] == '2');
+            auto kp = pf ? rmsnorm_rope_pair_bound_persistent_kernel<true> : rmsnorm_rope_pair_bound_persistent_kernel<false>;
+            const int wgs = omh_cu_count() * PAIR_BOUND_WG_PER_CU;
+            hipLaunchKernelGGL(kp, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x_bf16, ldx, seg_x,
+                               (uint16_t*)y0, (uint16_t*)y1, rows, dim, weight0, weight1, eps, do_norm, rope_cos, rope_sin,
+                               rope_len, head_dim, grid, seq_len, out_scale0, out_scale1, norm2_max);
+            return omh_launch_status();
+        }
+    }
+    // (dim 5 120 keeps the one-wave-per-row form: 40 row registers per segment leave no room for a second row in flight)
     auto k2 = dim <= 6 * 256 ? rmsnorm_rope_pair_row_bound_kernel<6> : rmsnorm_rope_pair_row_bound_kernel<20>;
     hipLaunchKernelGGL(k2, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x_bf16, ldx,
                        seg_x, (uint16_t*)y0, (uint16_t*)y1, rows, dim, weight0, weight1, eps, do_norm, rope_cos, rope_sin,

@@ -189,12 +189,31 @@ class _FwdCtx:
                  "cache_pos", "cache_hi", "cache_mask",
                  # grids: the (f, h, w) of the samples (host); ctx_mask: the resolved ops.AttnMask every cross-attention runs
                  # under (frame-aligned condition tokens: WanModel._condition_mask), else None
-                 "grids", "ctx_mask")
+                 "grids", "ctx_mask",
+                 # bounds: where the self-attention calls of this forward take their zeroed score-bound buffers from
+                 "bounds")
 
     def __init__(self):
         self.kv = self.chunk = self.cache = self.cache_layer = self.cache_lo = self.rpb = self.interval = None
         self.cache_pos = self.cache_hi = self.cache_mask = None
         self.grids = self.ctx_mask = None
+        self.bounds = _BoundPool()
+
+
+class _BoundPool:
+    """Zeroed float [B, heads, 2] buffers for ops.rmsnorm_rope_bf16_pair_bound_raw, cut from one [SLICES, B, heads, 2] tensor:
+    one fill launch per forward instead of one per block (59 in a CFG step).  Every slice is handed out once; the two branches
+    of a CFG pair share the pool by reference, so neither sees the other's maxima."""
+    SLICES = 64
+
+    def __init__(self):
+        self.buf, self.used = None, 0
+
+    def take(self, B, heads, device):
+        if self.buf is None or self.used == self.buf.shape[0] or self.buf.shape[1:] != (B, heads, 2) or self.buf.device != device:
+            self.buf, self.used = torch.zeros(self.SLICES, B, heads, 2, dtype=torch.float32, device=device), 0
+        self.used += 1
+        return self.buf[self.used - 1]
 
 
 class ContextState:
@@ -454,7 +473,7 @@ class WanSelfAttention(nn.Module):
             # (a block, staircase or interval mask runs the short-sequence kernel: no long-sequence stream, no bound)
             if mask is not None and mask.rule is None and D == 128 and d <= 5120 and \
                     ops.flash_attn_takes_bounded(B, N, S, S, d, d, d, Sp, mask.window):
-                nmax = torch.zeros(B, N, 2, dtype=torch.float32, device=h.device)
+                nmax = fc.bounds.take(B, N, h.device)                    # zeroed float [B, N, 2]
             self.last_qk_norm2_max = nmax                                # (read by tools/attn_bound_values.py)
         norm_args = (ptr(qk), 2 * d, d, ptr(q), ptr(k), R, d, ptr(wq) if wq is not None else None,
                      ptr(wk) if wk is not None else None, self.eps, int(self.qk_norm), ptr(fc.rope_cos), ptr(fc.rope_sin),
