@@ -53,11 +53,11 @@ int omh_set_deterministic(int on);
 
 /* Process options (ABI v10).  Every dispatch switch of the library — kernel-family overrides used by the parity tests
  * (one product on every kernel that can take it) and by A/B timing — is an entry of one table:
- *   ATTN_KERNEL ("w64" / "base")   ATTN_SPLIT ("0" / "tail")   W64_SPLIT ("0")   W64_VARIANT (ablation builds only)
+ *   ATTN_KERNEL ("w64" / "base")   ATTN_SPLIT ("0" / "tail")   W64_SPLIT ("0")
  *   ATTN_BOUNDED ("0": omh_flash_attn_fwd_d128_bounded runs exactly omh_flash_attn_fwd_d128)
  *   W64_SCHED ("0": the long-sequence attention streams in their original instruction order; same bits, A/B timing)
  *   GEMM_KERNEL ("w64" / "8w")   GEMM_TILE ("big" / "small" / "tiny")   GEMM_RULE   GEMM_GROUP_M   GEMM_SPLITK ("0")
- *   GEMM_QKV ("0" / "1")   GEMM_W64_R192 / N192 / BF16M / GBWD / GAUX ("0" / "1")   GEMM_W64_P256 (experiment builds only)
+ *   GEMM_QKV ("0" / "1")   GEMM_W64_R192 / N192 / BF16M / GBWD / GAUX ("0" / "1")
  *   RMS_PAIR_ROW ("0" / "1": omh_rmsnorm_rope_bf16_pair's two-workgroup / one-wave-per-row form)
  *   RMS_PAIR_BOUND ("0": omh_rmsnorm_rope_bf16_pair_bound's one-wave-per-row form; "2": its persistent form without the
  *                   next-row prefetch; unset: the persistent form at dim <= 1536; the same bits, A/B timing)

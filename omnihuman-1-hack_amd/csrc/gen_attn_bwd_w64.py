@@ -38,7 +38,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_attn_w64 import Emit, spread, vr, ar             # noqa: E402
+from gen_w64_common import Emit, spread, vr, ar           # noqa: E402
 
 SLOT = 32768                      # one ring slot: Q tile 16 KiB | dO tile 16 KiB
 NSLOT = 4
@@ -47,7 +47,6 @@ STAT_FIN = STAT_RAW + NSLOT * 512 # fixed-up statistics, same shape
 LDS_BYTES = STAT_FIN + NSLOT * 512
 PARK_BLOCK = 1040                 # the epilogue parks 4 accumulator registers x 64 lanes per block; 16 bytes of padding: the
 PARK_WAVE = 32 * PARK_BLOCK       # row-major read-back (16 lanes = 16 blocks of one row) then hits 64 different banks
-ABL = os.environ.get("OMH_BWD_ABL", "").split(",")     # timing-only ablations (wrong numerics by construction; never shipped)
 LEAD_A, LEAD_C = 12, 6            # a fragment is requested this many MFMAs ahead (stage A: one read each; C: two) — the
                                   # LDS counter holds 15 outstanding operations
 
@@ -112,23 +111,21 @@ def mfma_of(i):
         hb, kk = i // 16, (i % 16) // 2
         acc = vr((S(hb) if w == 0 else DP(hb)), 16)
         b = ar((KF(kk) if w == 0 else VF(kk)), 4)
-        needs = [] if "norow" in ABL else [f"F{i}"]
-        if kk == 0 and "nostat" not in ABL:
+        needs = [f"F{i}"]
+        if kk == 0:
             needs += [f"ST{hb}.{w}.{g}" for g in range(4)]
         return f"v_mfma_f32_32x32x16_bf16 {acc}, {frag}, {b}, {acc}", needs
     j = i - 32
     hb, a, db = j // 16, (j % 16) // 8, (j % 8) // 2
     acc = ar((DV(db) if w == 0 else DK(db)), 16)
     b = vr(PK(hb, w, a), 4)
-    return f"v_mfma_f32_32x32x16_bf16 {acc}, {frag}, {b}, {acc}", ([] if "notr" in ABL else [f"F{i}a", f"F{i}b"])
+    return f"v_mfma_f32_32x32x16_bf16 {acc}, {frag}, {b}, {acc}", [f"F{i}a", f"F{i}b"]
 
 
 def frag_reads(i, prep):
     """The LDS reads that feed MFMA i (issued LEAD_A / LEAD_C MFMAs earlier)."""
     pr, w = i // 2, i % 2
     st = pr % 8
-    if ("norow" in ABL and i < 32) or ("notr" in ABL and i >= 32):
-        return []
     if i < 32:
         hb, kk = i // 16, (i % 16) // 2
         off = hb * 8192 + (16384 if w == 1 else 0)              # S: Q rows;  dP: dO rows
@@ -218,8 +215,6 @@ def tile_ops(pre):
     # stage B, half of it at a time: pairs 0..3 make the a = 0 operands (first read by the 1st MFMA of stage C), pairs 4..7
     # the a = 1 operands (first read by the 9th) — spread as widely as those deadlines allow: ~2 VALU per gap
     b0, b1 = stage_b(0, pre), stage_b(1, pre)
-    if "nob" in ABL:
-        b0, b1 = [], []
     for lst, lo, hi in ((b0[:len(b0) // 2], 17, 30), (b0[len(b0) // 2:], 30, 38), (b1[:len(b1) // 2], 34, 46), (b1[len(b1) // 2:], 46, 54)):
         for g, ops_ in enumerate(spread(lst, 64, lo, hi)):
             gaps[g] += ops_
@@ -239,26 +234,21 @@ def tile_ops(pre):
     # done with tile t-1, whose slot the loads of tile t+3 now overwrite
     gaps[47] += [op("x", "s_waitcnt vmcnt(10)"), op("x", "s_barrier")]
     gaps[48] += [op("x", ln) for ln in advance(S_DMA, S_OFF, C_STEP, C_WRAP, NSLOT * SLOT)[:2] + [f"s_cselect_b32 {S_DMA}, 0, {S_DMA}"]]
-    for g, lst in enumerate(spread([op("x", ln) for ln in dma_group(S_DMA) if not ("nodma" in ABL and ln.startswith("buffer_load"))], 64, 48, 60)):
+    for g, lst in enumerate(spread([op("x", ln) for ln in dma_group(S_DMA)], 64, 48, 60)):
         gaps[g] += lst
-    if "nodma" in ABL:
-        gaps[47][-2] = op("x", "s_nop 0")
-    if "nobar" in ABL:
-        gaps[47][-1] = op("x", "s_nop 0")
     # statistics of tile t+1
-    if "nostat" not in ABL:
-        fix = stat_fixup()
-        gaps[48] += fix[:2]
-        gaps[50] += fix[2:]
-        gaps[52] += stat_reads(0)[:4]
-        gaps[53] += stat_reads(0)[4:]
-        gaps[56] += stat_reads(1)[:4]
-        gaps[57] += stat_reads(1)[4:]
+    fix = stat_fixup()
+    gaps[48] += fix[:2]
+    gaps[50] += fix[2:]
+    gaps[52] += stat_reads(0)[:4]
+    gaps[53] += stat_reads(0)[4:]
+    gaps[56] += stat_reads(1)[:4]
+    gaps[57] += stat_reads(1)[4:]
     return gaps
 
 
 def generate(pre):
-    e = Emit("bk%d" % (0 if pre else 1))
+    e = Emit("w64v", "bk%d" % (0 if pre else 1))
     # ---------------- prologue
     for kk in range(8):                                              # K / V fragments of this lane's key (rows past Lk: out of range -> 0)
         e(f"buffer_load_dwordx4 {vr(S(0) + 4 * kk, 4)}, %[vokv], %[rk], 0 offen offset:{kk * 32}")
@@ -304,7 +294,7 @@ def generate(pre):
         ops.append(op("m", text, needs))
         ops += gaps[i]
     # what is still outstanding where the loop closes (the last MFMAs' waits retired everything older): enter the same way
-    loop_pending = linearize(Emit("dry"), ops, full)
+    loop_pending = linearize(Emit("w64v", "dry"), ops, full)
     assert full[len(full) - len(loop_pending):] == loop_pending, (full, loop_pending)
     e(f"s_waitcnt lgkmcnt({min(len(loop_pending), 15)})")
     # ---------------- the loop: one tile per iteration
@@ -354,16 +344,14 @@ def dq_mfma_of(i):
         acc = vr((S(hb) if w == 0 else DP(hb)), 16)
         c = vr((NEGL if w == 0 else NEGD), 16) if kk == 0 else acc
         b = ar((QF(kk) if w == 0 else DOF(kk)), 4)
-        return f"v_mfma_f32_32x32x16_bf16 {acc}, {frag}, {b}, {c}", ([] if "norow" in ABL else [f"F{i}"])
+        return f"v_mfma_f32_32x32x16_bf16 {acc}, {frag}, {b}, {c}", [f"F{i}"]
     j = i - 32
     hb, a, db = j // 8, (j % 8) // 4, j % 4
     acc = ar(DQA(db), 16)
-    return f"v_mfma_f32_32x32x16_bf16 {acc}, {frag}, {vr(PKD(hb, a), 4)}, {acc}", ([] if "notr" in ABL else [f"F{i}a", f"F{i}b"])
+    return f"v_mfma_f32_32x32x16_bf16 {acc}, {frag}, {vr(PKD(hb, a), 4)}, {acc}", [f"F{i}a", f"F{i}b"]
 
 
 def dq_frag_reads(i, prep):
-    if ("norow" in ABL and i < 32) or ("notr" in ABL and i >= 32):
-        return []
     if i < 32:
         hb, kk, w = i // 16, (i % 16) // 2, i % 2
         off = hb * 8192 + (16384 if w == 1 else 0)              # S: K rows;  dP: V rows
@@ -425,16 +413,13 @@ def dq_tile_ops(pre, e):
         gaps[g % 48] += dq_frag_reads(tgt % 48, prep=g < 48)
         assert (tgt % 48) - 16 <= (tgt % 48) - lead
     b0, b1 = dq_stage_b(0, pre), dq_stage_b(1, pre)
-    if "nob" in ABL:
-        b0, b1 = [], []
     h0, h1 = len(b0) // 2, len(b1) // 2
     for lst, lo, hi in ((b0[:h0], 17, 28), (b0[h0:], 28, 35), (b1[:h1], 33, 39), (b1[h1:], 39, 43)):
         for g, ops_ in enumerate(spread(lst, 48, lo, hi)):
             gaps[g] += ops_
     # the edge masks sit right in front of each half's stage B (multi-line ops keep the labels with their branches)
-    if "nomask" not in ABL:
-        gaps[16] += [op("x", "\\n\\t\"\n    \"".join(dq_mask_block(e, 0, "h0")))]
-        gaps[32] += [op("x", "\\n\\t\"\n    \"".join(dq_mask_block(e, 1, "h1")))]
+    gaps[16] += [op("x", "\\n\\t\"\n    \"".join(dq_mask_block(e, 0, "h0")))]
+    gaps[32] += [op("x", "\\n\\t\"\n    \"".join(dq_mask_block(e, 1, "h1")))]
     gaps[20] += [op("x", ln) for ln in advance(S_ROW, D_ROW, C_STEP, C_WRAP, NSLOT * SLOT)]
     for g, lst in enumerate(spread([op("x", f"v_add_u32 {vr(r)}, {D_ROW}, {vr(r)}") for r in ROW], 48, 21, 33)):
         gaps[g] += lst
@@ -444,15 +429,13 @@ def dq_tile_ops(pre, e):
     # barrier where the next tile's first fragments are requested (gap 36 = 48 - 12); the 8 loads of tile t+2 may still fly
     gaps[35] += [op("x", "s_waitcnt vmcnt(8)"), op("x", "s_barrier"), op("x", f"s_sub_u32 {S_REM}, {S_REM}, 64")]
     gaps[36] += [op("x", ln) for ln in advance(S_DMA, S_OFF, C_STEP, C_WRAP, NSLOT * SLOT)[:2] + [f"s_cselect_b32 {S_DMA}, 0, {S_DMA}"]]
-    for g, lst in enumerate(spread([op("x", ln) for ln in dq_dma_group(S_DMA) if not ("nodma" in ABL and ln.startswith("buffer_load"))], 48, 36, 46)):
+    for g, lst in enumerate(spread([op("x", ln) for ln in dq_dma_group(S_DMA)], 48, 36, 46)):
         gaps[g] += lst
-    if "nodma" in ABL:
-        gaps[35][0] = op("x", "s_nop 0")
     return gaps
 
 
 def generate_dq(pre):
-    e = Emit("bq%d" % (0 if pre else 1))
+    e = Emit("w64v", "bq%d" % (0 if pre else 1))
     for kk in range(8):                                              # Q / dO fragments of this lane's query (rows past Lq: out of range -> 0)
         e(f"buffer_load_dwordx4 {vr(S(0) + 4 * kk, 4)}, %[voq], %[rq], 0 offen offset:{kk * 32}")
     for kk in range(8):
@@ -495,7 +478,7 @@ def generate_dq(pre):
         text, needs = dq_mfma_of(i)
         ops.append(op("m", text, needs))
         ops += gaps[i]
-    loop_pending = linearize(Emit("dry"), ops, full)
+    loop_pending = linearize(Emit("w64v", "dry"), ops, full)
     assert full[len(full) - len(loop_pending):] == loop_pending, (full, loop_pending)
     e(f"s_waitcnt lgkmcnt({min(len(loop_pending), 15)})")
     LOOP = e.lab("loop")

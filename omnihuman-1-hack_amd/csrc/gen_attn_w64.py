@@ -25,13 +25,10 @@ between lanes; K [64][128] / V^T [128][64] bf16 tiles, 16-byte-slot XOR swizzle,
     phase 2 = V^T(t).P^T(t) (32 MFMA) || row sums of tile t + row max of tile t+1 (~100 VALU) || V^T fragment reads;
     <= 4.2 non-MFMA issues per MFMA (the budget is 5: MI355X_MICROARCH.md, one wave per SIMD).
 
-Variants (selected at launch, OMH_W64_VARIANT; kept side by side for A/B timing on one box):
-  V0  K / V^T rings of two 16 KiB slots each, all LDS-DMA issued at the head of phase 1, every phase starts by
-      reading its own first fragments;
-  V1  = V0 with the eight DMA pieces spread over phase 1 and the first three V^T fragments of phase 2 read under
-      the last MFMAs of phase 1;
-  V2  = V1 with a K ring of THREE slots filled three tiles ahead, so that the first K fragments of the next tile are
-      read under the last MFMAs of phase 2 (no phase starts by waiting for the LDS);
+Variants (the numbers are history: V0 / V1, the steps that led to V2, are no longer generated):
+  V2  a V^T ring of two 16 KiB slots and a K ring of THREE, filled three tiles ahead; the eight DMA pieces of a tile are
+      spread over phase 1, the first three V^T fragments of phase 2 are read under the last MFMAs of phase 1 and the
+      first K fragments of the next tile under the last MFMAs of phase 2 (no phase starts by waiting for the LDS);
   V3  = V2 storing its normalised result in fp32: the split-KV workers of the tail (attention_w64.hip).
   V4  = V2 WITHOUT a running max: the caller supplies m >= every score of the workgroup's (sample, head) as an SGPR operand
       (%[sm], from the norms of q and k: attention_w64.hip); MI holds -m from the prologue on and is never touched, so
@@ -68,8 +65,12 @@ Register map (asm-owned; the thirteen per-lane inputs stay in the compiler's ope
   s92 s93 DMA source offsets, s94 tile counter, s95 K tile stride, s[96:97] exec save, s98 K read-slot offset,
   s99 K DMA-slot offset, s91 address step of the K ring
 """
+import os
 import re
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gen_w64_common import Emit, ar, linearize, spread, vr        # noqa: E402
 
 THR = "4.0"                      # inline constant: rescale when a row max exceeds the running max by > 4 (log2 units)
 KSLOT = 16384
@@ -99,61 +100,7 @@ INV = [240, 241]
 E0 = 242                          # 242..249 scratch (8)
 
 
-def vr(lo, n=1):   return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
-def ar(lo, n=1):   return f"a{lo}" if n == 1 else f"a[{lo}:{lo + n - 1}]"
-
-
-class Emit:
-    def __init__(self, tag):
-        self.lines, self.tag, self.cuts = [], tag, []
-
-    def __call__(self, s):
-        self.lines.append(s)
-
-    def lab(self, name):
-        return f".Lw64v{self.tag}_{name}_%="
-
-    def label(self, name):
-        self.lines.append(f"{name}:")
-
-    def cut(self):
-        """A piece of the text ends here (pieces(): what the schedules share is written into the .inc once)."""
-        self.cuts.append(len(self.lines))
-
-    def pieces(self):
-        b = [0] + self.cuts + [len(self.lines)]
-        return [self.lines[i:j] for i, j in zip(b, b[1:])]
-
-    def text(self):
-        return "\n".join('    "%s\\n\\t"' % ln for ln in self.lines)
-
-
-# ---------------------------------------------------------------- op lists and the LDS wait tracker
-# op = ("m", text, [tags needed])  MFMA   |  ("r", tag, text)  ds_read   |  ("x", text)  anything else
-def linearize(e, ops, pending):
-    """Emit `ops` in order; before an MFMA that needs ds_read results, emit the s_waitcnt lgkmcnt that makes exactly
-    those reads complete (LDS returns in order).  `pending` = tags of reads issued earlier and not yet waited for,
-    oldest first.  Returns the pending list at the end."""
-    pending = list(pending)
-    for op in ops:
-        if op[0] == "r":
-            e(op[2])
-            pending.append(op[1])
-        elif op[0] == "m":
-            need = [t for t in op[2] if t in pending]
-            if need:
-                last = max(pending.index(t) for t in need)
-                allowed = len(pending) - last - 1
-                assert allowed <= 15
-                e(f"s_waitcnt lgkmcnt({allowed})")
-                pending = pending[last + 1:]
-            for ln in (op[1] if isinstance(op[1], tuple) else (op[1],)):      # (M16 ablation: two instructions per op)
-                e(ln)
-        else:
-            e(op[1])
-    return pending
-
-
+# ---------------------------------------------------------------- op lists (gen_w64_common.py: their three kinds, linearize)
 def weave(mfmas, plans, pre=()):
     """mfmas: list of ("m", ...) ops; plans: lists (one entry per gap) of lists of ops issued after that MFMA."""
     ops = list(pre)
@@ -162,16 +109,6 @@ def weave(mfmas, plans, pre=()):
         for pl in plans:
             ops.extend(pl[g])
     return ops
-
-
-def spread(items, gaps, start=0, end=None):
-    """Distribute `items` (ordered) over gaps[start:end] as evenly as possible; returns a per-gap list of lists."""
-    end = gaps if end is None else end
-    n = end - start
-    out = [[] for _ in range(gaps)]
-    for i, it in enumerate(items):
-        out[start + min(n - 1, (i * n) // len(items))].append(it)
-    return out
 
 
 def X(lines):
@@ -255,25 +192,12 @@ def vread_op(i, vbase):
     return ("r", f"V{i}", f"ds_read_b128 {ar(VR(i % 4), 4)}, {vr(VA[2 * kb + a])} offset:{vbase + db * 4096}")
 
 
-M16 = False     # OMH_ATTN_ABL=4, variant 0 (timing only, round 6): every 32x32x16 MFMA as TWO v_mfma_f32_16x16x32_bf16 on the
-#                 same operand registers — the same flops and traffic, garbage results: what would the MFMA shape that sustains
-#                 2.16 instead of 1.88 PFLOP/s on data-like operands (tools/mfma_shape_probe.py) buy this stream?
-
-
 def qk_mfmas(nxt, c_zero=False):
     """32 MFMAs of K.Q^T into score set nxt (C = MI = -m_run on the first k step), + the fragment reads that ride
     behind them (steps kk+2, after the 2nd MFMA of step kk)."""
     mf = []
     for kk in range(8):
         for kb, qb in ((0, 0), (0, 1), (1, 0), (1, 1)):
-            if M16:
-                two = []
-                for half in range(2):
-                    d = vr(S(nxt, qb, kb) + 4 * half, 4)
-                    c = ("0" if c_zero else vr(MI(qb) + 4 * half, 4)) if kk == 0 else d
-                    two.append(f"v_mfma_f32_16x16x32_bf16 {d}, {ar(KR(kk % 3, kb), 4)}, {ar(Q(qb, kk), 4)}, {c}")
-                mf.append(("m", tuple(two), [f"K{kk}.{kb}"]))
-                continue
             c = ("0" if c_zero else vr(MI(qb), 16)) if kk == 0 else vr(S(nxt, qb, kb), 16)
             mf.append(("m", f"v_mfma_f32_32x32x16_bf16 {vr(S(nxt, qb, kb), 16)}, {ar(KR(kk % 3, kb), 4)}, "
                             f"{ar(Q(qb, kk), 4)}, {c}", [f"K{kk}.{kb}"]))
@@ -288,30 +212,14 @@ def qk_read_plan(kbase, first=2):
     return plan
 
 
-# Timing-only ablation builds (tools/attn_abl.sh; wrong numerics by construction, never shipped — the default output of
-# this generator is unchanged).  OMH_ATTN_ABL=1: variant 0 = V2 with every 4th exponential replaced by the 5 FMA-pipe
-# instructions a degree-3 exp2 polynomial costs (floor, subtract, 3 fma; the exponent insertion not even counted),
-# variant 1 = V2 without the per-piece SALU address arithmetic of the LDS-DMA (all four pieces of a tile then fetch the
-# same rows into the same 1 KiB).  OMH_ATTN_ABL=2: variant 1 = V2 with that arithmetic kept but adding zero (same
-# instruction count, same-rows traffic).  Round-3 results (profiles/r03_attention_ablations.json): polynomial share
-# -3.5 % (slower); no-SALU +7.7 %, same-count same-rows +10.3 % — i.e. NOT the SALU slots: with three quarters of every
-# K / V^T tile left stale the operands toggle less and the power-limited chip clocks higher (see the telemetry there).
-ABL = __import__("os").environ.get("OMH_ATTN_ABL", "")
-
-
-def softmax_lines(cur, poly=False):
+def softmax_lines(cur):
     """exp2 in place + bf16 packing of score set cur: 64 + 32 VALU; a block's packing trails its exponentials."""
     out = []
     for qb in range(2):
         for kb in range(2):
             base = S(cur, qb, kb)
             for r in range(16):
-                if poly and r % 4 == 3:
-                    x = vr(base + r)
-                    out += [f"v_floor_f32 {vr(T3)}, {x}", f"v_sub_f32 {x}, {x}, {vr(T3)}", f"v_fma_f32 {vr(T3)}, {x}, 0.5, 1.0",
-                            f"v_fma_f32 {vr(T3)}, {x}, {vr(T3)}, 0.5", f"v_fma_f32 {x}, {x}, {vr(T3)}, 1.0"]
-                else:
-                    out.append(f"v_exp_f32 {vr(base + r)}, {vr(base + r)}")
+                out.append(f"v_exp_f32 {vr(base + r)}, {vr(base + r)}")
             for a in range(2):
                 for eidx in range(4):
                     r0 = base + 8 * a + 2 * eidx
@@ -378,13 +286,6 @@ def pv_mfmas(cur):
     for i in range(16):
         kb, a, db = i >> 3, (i >> 2) & 1, i & 3
         for qb in range(2):
-            if M16:
-                two = []
-                for half in range(2):
-                    d = ar(O(qb, db) + 4 * half, 4)
-                    two.append(f"v_mfma_f32_16x16x32_bf16 {d}, {ar(VR(i % 4), 4)}, {vr(P(qb, kb, a), 4)}, {d}")
-                mf.append(("m", tuple(two), [f"V{i}"]))
-                continue
             mf.append(("m", f"v_mfma_f32_32x32x16_bf16 {ar(O(qb, db), 16)}, {ar(VR(i % 4), 4)}, "
                             f"{vr(P(qb, kb, a), 4)}, {ar(O(qb, db), 16)}", [f"V{i}"]))
     return mf
@@ -478,49 +379,32 @@ def rotate(sreg, nslots):
 # ---------------------------------------------------------------- whole stream
 def generate(variant, sched=0):
     defer = DEFER[variant] if sched else 0
-    assert not (sched and ABL)
-    abl_poly = ABL == "1" and variant == 0
-    abl_salu = ABL == "1" and variant == 1
-    abl_traffic = ABL == "2" and variant == 1
-    # OMH_ATTN_ABL=3 (round 5): variant 0 = V2 without the row maxima and the rescale check, variant 1 = without the row sums
-    # as well.  Measured: 4.707 -> 4.555 -> 4.411 ms per launch (-3.2 %, -6.3 %).  The first of the two is built as V4.  A
-    # stream without the running max needs a bound on the scores; the a-priori one is useless (the model's RMS norm runs over
-    # all 1 536 channels, not per head: 196 log2 units, p would underflow), but the stream does not need the worst case, it
-    # needs a bound for THIS launch's q and k: s_ij <= |q_i| |k_j| per head (Cauchy-Schwarz), and the norm kernel that writes
-    # q and k emits max |q|^2 and max |k|^2 per (sample, head) on the way (dit_elementwise.hip).  The kernel takes V4 only
-    # where that bound is <= 48, so that p >= 2^-96 stays a normal number; above it the workgroup runs V2.
-    abl_nomax = ABL == "3" and variant in (0, 1)
-    abl_nosum = ABL == "3" and variant == 1
-    global M16
-    M16 = ABL == "4" and variant == 0
+    # V4 (round 5: V2 without the row maxima and the rescale check measured 4.707 -> 4.555 ms per launch).  A stream without
+    # the running max needs a bound on the scores; the a-priori one is useless (the model's RMS norm runs over all 1 536
+    # channels, not per head: 196 log2 units, p would underflow), but the stream does not need the worst case, it needs a
+    # bound for THIS launch's q and k: s_ij <= |q_i| |k_j| per head (Cauchy-Schwarz), and the norm kernel that writes q and k
+    # emits max |q|^2 and max |k|^2 per (sample, head) on the way (dit_elementwise.hip).  The kernel takes V4 only where
+    # that bound is <= 48, so that p >= 2^-96 stays a normal number; above it the workgroup runs V2.
     bounded = variant == 4
-    base = 2 if (abl_poly or abl_salu or abl_traffic or abl_nomax or M16) else min(variant, 2)
-    dma_spread = base >= 1
-    vpre = base >= 1
-    k3 = base >= 2
     # (timing-only ablations of V2 measured in round 2, profiles/r02_attention_w64_ablations.json: no LDS-DMA in the
     # loop -5.9 %, v_exp -> v_mov -3.4 %, no barrier -0.2 %, no ds_reads -8.1 %: nothing dominates)
-    abl = 0
     # variant 3 = variant 2 with the "partial" epilogue of the split-KV tail workers: the normalised output is stored
     # in fp32 (one [256, 128] slab per worker) instead of bf16; with the log-sum-exp stored next to it a combine
     # pass weights the workers' results (attention_w64.hip)
     partial = variant == 3
-    # LDS map: two-slot rings: K [0, 32K) | V^T [32K, 64K).  Three-slot K ring: V^T [0, 32K) | K [32K, 80K) — the K
-    # addresses carry the ring base and slot in the address registers, so every ds_read offset stays below 64 KiB
-    VBASE = 0 if k3 else 2 * KSLOT
-    KBASE = 2 * KSLOT if k3 else 0
-    e = Emit(variant)                    # (both schedules: the labels end in %=, unique per asm statement)
+    # LDS map: V^T ring of two slots [0, 32K) | K ring of three slots [32K, 80K) — the K addresses carry the ring base
+    # and slot in the address registers, so every ds_read offset stays below 64 KiB
+    VBASE = 0
+    KBASE = 2 * KSLOT
+    e = Emit("w64v", variant)                 # (both schedules: the labels end in %=, unique per asm statement)
 
     def k_dma(slot_expr, advance=True):
         """4 pieces of K(next) -> K ring slot; slot_expr: literal byte offset or an SGPR name."""
-        out = [f"s_add_u32 m0, %[ldsw], {slot_expr}"]
-        if KBASE:
-            out.append(f"s_add_u32 m0, m0, {KBASE}")
+        out = [f"s_add_u32 m0, %[ldsw], {slot_expr}", f"s_add_u32 m0, m0, {KBASE}"]
         for j in range(4):
-            if j and not abl_salu:
-                out.append("s_add_u32 m0, m0, 0" if abl_traffic else "s_add_u32 m0, m0, 4096")
-            if not (abl_salu and j):
-                out.append("s_mov_b32 s92, %[skn]" if j == 0 else ("s_add_u32 s92, s92, 0" if abl_traffic else "s_add_u32 s92, s92, %[skp]"))
+            if j:
+                out.append("s_add_u32 m0, m0, 4096")
+            out.append("s_mov_b32 s92, %[skn]" if j == 0 else "s_add_u32 s92, s92, %[skp]")
             out.append("buffer_load_dwordx4 %[vok], %[rk], s92 offen lds")
         if advance:
             out.append("s_add_u32 %[skn], %[skn], s95")
@@ -529,10 +413,9 @@ def generate(variant, sched=0):
     def v_dma(slot):
         out = [f"s_add_u32 m0, %[ldsw], {VBASE + slot * KSLOT}"]
         for j in range(4):
-            if j and not abl_salu:
-                out.append("s_add_u32 m0, m0, 0" if abl_traffic else "s_add_u32 m0, m0, 4096")
-            if not (abl_salu and j):
-                out.append("s_mov_b32 s93, %[svn]" if j == 0 else ("s_add_u32 s93, s93, 0" if abl_traffic else "s_add_u32 s93, s93, %[svp]"))
+            if j:
+                out.append("s_add_u32 m0, m0, 4096")
+            out.append("s_mov_b32 s93, %[svn]" if j == 0 else "s_add_u32 s93, s93, %[svp]")
             out.append("buffer_load_dwordx4 %[vov], %[rv], s93 offen lds")
         out.append("s_add_u32 %[svn], %[svn], 128")
         return out
@@ -546,8 +429,7 @@ def generate(variant, sched=0):
     for kk in range(8):
         e(f"v_xor_b32 {vr(T0)}, {kk}, %[xh]")
         e(f"v_lshl_add_u32 {vr(KA[kk])}, {vr(T0)}, 5, %[kab]")
-        if KBASE:
-            e(f"v_add_u32 {vr(KA[kk])}, {KBASE}, {vr(KA[kk])}")
+        e(f"v_add_u32 {vr(KA[kk])}, {KBASE}, {vr(KA[kk])}")
     for j in range(4):
         e(f"v_xor_b32 {vr(T0)}, {j}, %[yh]")
         e(f"v_lshl_add_u32 {vr(VA[j])}, {vr(T0)}, 5, %[vab]")
@@ -563,9 +445,9 @@ def generate(variant, sched=0):
                 e(f"v_mov_b32 {vr(MI(qb) + r)}, 0")
     for i in range(128):
         e(f"v_accvgpr_write_b32 {ar(i)}, 0")
-    # first tiles: K(0), V(0), K(1) (and K(2) with the three-slot ring)
+    # first tiles: K(0), V(0), K(1), K(2)
     n_dma = 0
-    for ln in k_dma(0) + v_dma(0) + k_dma(KSLOT) + (k_dma(2 * KSLOT) if k3 else []):
+    for ln in k_dma(0) + v_dma(0) + k_dma(KSLOT) + k_dma(2 * KSLOT):
         e(ln)
         n_dma += ln.startswith("buffer_load")
     e(f"s_waitcnt vmcnt({n_dma})")                              # the 16 Q loads (issued first) have landed
@@ -584,15 +466,14 @@ def generate(variant, sched=0):
     ops = weave(qk_mfmas(0, c_zero=not bounded), [qk_read_plan(0)], pre=kread_ops(0, 0) + kread_ops(1, 0))
     pending = linearize(e, ops, [])
     assert not pending
-    if k3:
-        # K ring bookkeeping: tile t reads slot (t+1) % 3 and refills slot t % 3; the address registers now move to slot 1
-        e(f"s_mov_b32 s98, {KSLOT}")                            # slot offset the K addresses point at
-        e("s_mov_b32 s99, 0")                                   # slot offset the next K DMA fills
-        for kk in range(8):
-            e(f"v_add_u32 {vr(KA[kk])}, {KSLOT}, {vr(KA[kk])}")
-        for op in kread_ops(0, 0) + kread_ops(1, 0):
-            e(op[2])
-        pending = ["K0.0", "K0.1", "K1.0", "K1.1"]
+    # K ring bookkeeping: tile t reads slot (t+1) % 3 and refills slot t % 3; the address registers now move to slot 1
+    e(f"s_mov_b32 s98, {KSLOT}")                                # slot offset the K addresses point at
+    e("s_mov_b32 s99, 0")                                       # slot offset the next K DMA fills
+    for kk in range(8):
+        e(f"v_add_u32 {vr(KA[kk])}, {KSLOT}, {vr(KA[kk])}")
+    for op in kread_ops(0, 0) + kread_ops(1, 0):
+        e(op[2])
+    pending = ["K0.0", "K0.1", "K1.0", "K1.1"]
     e("s_nop 7")
     e("s_nop 7")                                               # MFMA write of the scores -> VALU
     nomask0 = e.lab("nomask_first")
@@ -613,27 +494,19 @@ def generate(variant, sched=0):
         cur, nxt = p, p ^ 1
         e("s_waitcnt vmcnt(0)")
         e("s_barrier")
-        if k3:
-            dma = k_dma("s99") + v_dma(nxt)
-            kbase = 0                                          # the address registers carry the slot
-        else:
-            dma = k_dma(p * KSLOT) + v_dma(nxt)
-            kbase = nxt * KSLOT
+        dma = k_dma("s99") + v_dma(nxt)
         vbase = VBASE + p * KSLOT
-        # ---- phase 1
+        # ---- phase 1: the eight DMA pieces spread over it, the first three V^T fragments of phase 2 read under its last MFMAs
         mf1 = qk_mfmas(nxt)
-        plans = [qk_read_plan(kbase)]
-        plans.append(spread(X(dma), 32, 0, 30) if dma_spread else spread(X(dma), 32, 0, 6))
-        pre = [] if k3 else kread_ops(0, kbase) + kread_ops(1, kbase)
+        plans = [qk_read_plan(0)]                              # (offset 0: the address registers carry the K slot)
+        plans.append(spread(X(dma), 32, 0, 30))
         vp = [[] for _ in range(32)]
-        if vpre:
-            vp[29], vp[30], vp[31] = [vread_op(0, vbase)], [vread_op(1, vbase)], [vread_op(2, vbase)]
+        vp[29], vp[30], vp[31] = [vread_op(0, vbase)], [vread_op(1, vbase)], [vread_op(2, vbase)]
         groups = DEFER_ORDER[:defer // 8]
-        sm_now, sm_later = softmax_split(cur, groups) if sched else (softmax_lines(cur, abl_poly), {})
+        sm_now, sm_later = softmax_split(cur, groups) if sched else (softmax_lines(cur), {})
         plans.append(spread_cost(X(sm_now), 32, 2, 32, base=plans + [vp]) if sched else spread(X(sm_now), 32, 2, 32))
-        if vpre:
-            plans.append(vp)
-        ops1 = weave(mf1, plans, pre=pre)
+        plans.append(vp)
+        ops1 = weave(mf1, plans)
         e.cut()
         pend = linearize(e, ops1, LOOP_PENDING)
         e.cut()
@@ -649,16 +522,15 @@ def generate(variant, sched=0):
         # ---- phase 2
         mf2 = pv_mfmas(cur)
         plans = [pv_read_plan(vbase)]
-        tail = ([] if abl_nosum else rowsum_lines(cur)) + ([] if abl_nomax or bounded else rowmax_lines(nxt))
-        if k3:
-            # the K addresses step to the next slot once the reads of phase 1 are all issued; the first fragments of
-            # the next tile's K are read under the last MFMAs
-            step = ["s_mov_b32 s91, s98"] + rotate("s98", 3) + ["s_sub_u32 s91, s98, s91"] + rotate("s99", 3)
-            step += [f"v_add_u32 {vr(KA[kk])}, s91, {vr(KA[kk])}" for kk in range(8)]
-            plans.append(spread(X(step), 32, 0, 12))
-            kp = [[] for _ in range(32)]
-            kp[27], kp[29] = kread_ops(0, 0), kread_ops(1, 0)
-            plans.append(kp)
+        tail = rowsum_lines(cur) + ([] if bounded else rowmax_lines(nxt))
+        # the K addresses step to the next slot once the reads of phase 1 are all issued; the first fragments of
+        # the next tile's K are read under the last MFMAs
+        step = ["s_mov_b32 s91, s98"] + rotate("s98", 3) + ["s_sub_u32 s91, s98, s91"] + rotate("s99", 3)
+        step += [f"v_add_u32 {vr(KA[kk])}, s91, {vr(KA[kk])}" for kk in range(8)]
+        plans.append(spread(X(step), 32, 0, 12))
+        kp = [[] for _ in range(32)]
+        kp[27], kp[29] = kread_ops(0, 0), kread_ops(1, 0)
+        plans.append(kp)
         floor = None
         if groups:
             # the deferred groups, first reader first, under MFMAs [0, 16); every pack at least two MFMAs before the first
@@ -683,12 +555,11 @@ def generate(variant, sched=0):
             plans.append(by_cost)
         else:
             plans.append(by_count)
-        pre = [] if vpre else [vread_op(0, vbase), vread_op(1, vbase), vread_op(2, vbase)]
         e.cut()
-        pend = linearize(e, weave(mf2, plans, pre=pre), pend)
+        pend = linearize(e, weave(mf2, plans), pend)
         e.cut()
         assert pend == LOOP_PENDING, (pend, LOOP_PENDING)
-        if not (abl_nomax or bounded):
+        if not bounded:
             check_and_rescale(e, nxt, f"b{p}")
         e("s_add_u32 s94, s94, 1")
 
@@ -770,7 +641,7 @@ def generate(variant, sched=0):
 
 
 N_VARIANTS = 4
-LDS_BYTES = {0: 5 * KSLOT if ABL else 4 * KSLOT, 1: 5 * KSLOT if ABL else 4 * KSLOT, 2: 5 * KSLOT, 3: 5 * KSLOT, 4: 5 * KSLOT}
+LDS_BYTES = 5 * KSLOT                                            # V^T ring of two slots, K ring of three
 CLOBBER_V = range(12, 256)
 CLOBBER_A = range(0, 256)
 CLOBBER_S = range(91, 100)
@@ -797,21 +668,18 @@ def put_whole(name, parts):
 
 def main():
     print("// GENERATED by gen_attn_w64.py — do not edit; edit the generator.")
-    # Round 5: the shipped library carries the default stream (V2) and the split-KV workers' stream (V3) only; V0 / V1
-    # (the steps that led to V2, kept side by side for A/B timing in rounds 2-4) are emitted for the timing-only ablation
-    # builds (OMH_ATTN_ABL), which re-use their slots.  V4 (the bounded stream) is not a launch variant: V2's kernel holds it.
-    for v in ((0, 1, 2, 3, 4) if ABL else (2, 3, 4)):
+    # V2 (the default stream), V3 (the split-KV workers') and V4 (the bounded stream: not a launch variant, V2's kernel
+    # holds it).  The numbering is history: V0 / V1 were the steps that led to V2.
+    for v in (2, 3, 4):
         e = generate(v)
         p0 = e.pieces()
         assert len(p0) == len(PIECES)
         for name, lines in zip(PIECES, p0):
             put(f"OMH_ATTN_W64_V{v}_{name}", lines)
         put_whole(f"OMH_ATTN_W64_ASM_V{v}", [f"OMH_ATTN_W64_V{v}_{name}" for name in PIECES])
-        print(f"#define OMH_ATTN_W64_LDS_V{v} {LDS_BYTES[v]}")
+        print(f"#define OMH_ATTN_W64_LDS_V{v} {LDS_BYTES}")
         n_mfma = sum("v_mfma" in ln for ln in e.lines)
         print(f"// variant {v}: {len(e.lines)} lines, {n_mfma} MFMA")
-        if ABL:                                                  # ablation builds carry schedule 0 only
-            continue
         # schedule 1 (option W64_SCHED picks per launch): its four phases, everything else is schedule 0's text
         parts, p1 = [], generate(v, 1).pieces()
         for i in (2, 6):                                         # a loop body: the same lines in both schedules

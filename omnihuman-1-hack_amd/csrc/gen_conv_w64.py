@@ -31,8 +31,10 @@ v[168:215] ring of three residual tiles.  s[60:73] scalar arguments, s[80:99] st
 import os
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gen_w64_common import Emit, linearize, vr           # noqa: E402
+
 NI, NJ = 3, 4
-ABL = os.environ.get("OMH_CW64_ABL", "")     # timing-only ablations (wrong results): "dma", "and", "bar", "reads"
 STAGE = 53312
 NSTAGES = 3
 KINDS = ("bf16", "f32")
@@ -89,10 +91,6 @@ def res_request(n, kind):
     return out
 
 
-def vr(lo, n=1):
-    return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
-
-
 def acc(i, j):
     t = i * NJ + j
     return f"a[{t * 16}:{t * 16 + 15}]"
@@ -104,44 +102,6 @@ def wfrag(buf, i):
 
 def xfrag(buf, j):
     return FRAG[buf] + 12 + 4 * j
-
-
-class Emit:
-    def __init__(self, tag):
-        self.lines, self.tag = [], tag
-
-    def __call__(self, s):
-        self.lines.append(s)
-
-    def lab(self, name):
-        return f".Lcw64{self.tag}_{name}_%="
-
-    def label(self, name):
-        self.lines.append(f"{name}:")
-
-    def text(self):
-        return "\n".join('    "%s\\n\\t"' % ln for ln in self.lines)
-
-
-def linearize(e, ops, pending):
-    """ops: ("r", tag, text) LDS read; ("m", text, [tags]) instruction that needs those reads landed; ("x", text)."""
-    pending = list(pending)
-    for op in ops:
-        if op[0] == "r":
-            e(op[2])
-            pending.append(op[1])
-        elif op[0] == "m":
-            need = [t for t in op[2] if t in pending]
-            if need:
-                last = max(pending.index(t) for t in need)
-                allowed = len(pending) - last - 1
-                assert allowed <= 15, allowed
-                e(f"s_waitcnt lgkmcnt({allowed})")
-                pending = pending[last + 1:]
-            e(op[1])
-        else:
-            e(op[1])
-    return pending
 
 
 def frag_reads(G, buf):
@@ -162,7 +122,7 @@ def group_ops(G, buf, first=False):
     kw = G >> 1
     out = []
     for j in range(NJ):
-        if kw != 1 and ABL != "and":
+        if kw != 1:
             m = (EDGE0 if kw == 0 else EDGE2) + j
             for r_ in range(4):
                 out.append(("m", f"v_and_b32 v{xfrag(buf, j) + r_}, v{m}, v{xfrag(buf, j) + r_}", [f"X{buf}.{j}"]))
@@ -177,7 +137,7 @@ def group_ops(G, buf, first=False):
 def and_ops(G, buf, j):
     """The four ANDs of voxel fragment j of group G with the lane's edge word ([] for the centre tap)."""
     kw = G >> 1
-    if kw == 1 or ABL == "and":
+    if kw == 1:
         return []
     m = (EDGE0 if kw == 0 else EDGE2) + j
     return [("m", f"v_and_b32 v{xfrag(buf, j) + r_}, v{m}, v{xfrag(buf, j) + r_}", [f"X{buf}.{j}"]) for r_ in range(4)]
@@ -302,20 +262,19 @@ def main_loop(e, NA, NB, kind):
         barrier (every wave has read this stage), addresses advance, group 5 || reads of the next stage's group 0 ||
         the requests of residual tile res_tile.  mode "last": the final stage, nothing to wait for or read ahead."""
         pend = LOOP_PENDING
-        dm = pieces if (mode == "full" and ABL != "dma") else []
+        dm = pieces if mode == "full" else []
         per = [dm[0:4], dm[4:7], dm[7:10], dm[10:13], dm[13:]] if dm else [[]] * 5
         for G in range(5):
-            reads = frag_reads(G + 1, (G + 1) & 1) if ABL != "reads" else []
+            reads = frag_reads(G + 1, (G + 1) & 1)
             flat = [op for piece in per[G] for op in piece]
             ops = group_sched(G, G & 1, first and G == 0, reads, flat, and_ops(G + 1, (G + 1) & 1, 0))
             pend = linearize(e, ops, pend)
         if mode == "last":
             linearize(e, group_sched(5, 1, False, [], [], []), pend)
             return
-        e(f"s_waitcnt vmcnt({(NP if (mode == 'full' and ABL != 'dma') else 0) + r_prev})")
+        e(f"s_waitcnt vmcnt({(NP if mode == 'full' else 0) + r_prev})")
         e("s_waitcnt lgkmcnt(0)")
-        if ABL != "bar":
-            e("s_barrier")
+        e("s_barrier")
         advance(e)
         req = [("x", ln) for ln in res_request(res_tile, kind)] if res_tile is not None else []
         pend = linearize(e, group_sched(5, 1, False, frag_reads(0, 0), req, and_ops(0, 0, 0)), [])
@@ -751,7 +710,7 @@ def epilogue_norm(e, kind, pair_out=False):
 
 
 def generate(cfg, kind, norm=False, pair=False):
-    e = Emit(cfg + kind + ("n" if norm else "") + ("p" if pair else ""))
+    e = Emit("cw64", cfg + kind + ("n" if norm else "") + ("p" if pair else ""))
     NA, NB = CONFIGS[cfg]
     (main_loop_pair if pair else main_loop)(e, NA, NB, kind)
     if norm:

@@ -28,15 +28,20 @@ k loop: v[32:71] / v[72:111] fragment buffers, v[12:17] / v[22:27] B-fragment ad
 v[28:31] A-fragment addresses; epilogue: v[32:47] tile values, v[48:79] two slots of old C values, v[112:116] lane constants / temporaries; s[60:73] scalar
 arguments, s[80:95] scratch.
 """
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gen_w64_common import Emit, linearize, spread_after, vr, with_dma_tail    # noqa: E402
+
 NI, NJ = 6, 4                   # n tiles (B) x m tiles (A) per wave
 STAGE = 81920
 BOFF = 32768                    # B tile behind the A tile inside a stage
 PA, PB = 512, 768               # row pitches
 FB = 4 * NI + 4 * NJ
 NTILES = NI * NJ
-import os
-READ_END = int(os.environ.get("OMH_GTW64_READ_END", "20"))       # the next group's 20 reads go behind the first READ_END MFMAs
-DMA_START = int(os.environ.get("OMH_GTW64_DMA_START", "4"))      # a group's 6 B pieces: every other MFMA from this one on
+READ_END = 20                   # the next group's 20 reads go behind the first READ_END MFMAs
+DMA_START = 4                   # a group's 6 B pieces: every other MFMA from this one on
 # (measured on a block's group, one launch: start 12 -> 203 us, 8 -> 201, 4 -> 197, 2 -> 196, 0 -> 196.5; reads behind the first
 # 16 / 20 / 24 MFMAs: 208 / 203 / 204)
 
@@ -54,45 +59,6 @@ def nfrag(buf, i):   return 32 + buf * FB + 4 * i
 def mfrag(buf, j):   return 32 + buf * FB + 4 * NI + 4 * j
 def NA(s, i):        return 12 + s * 10 + i
 def MA(s, j):        return 12 + s * 10 + NI + j
-def vr(lo, n=1):     return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
-
-
-class Emit:
-    def __init__(self, tag):
-        self.lines, self.tag = [], tag
-
-    def __call__(self, s):
-        self.lines.append(s)
-
-    def lab(self, name):
-        return f".Lgtw64{self.tag}_{name}_%="
-
-    def label(self, name):
-        self.lines.append(f"{name}:")
-
-    def text(self):
-        return "\n".join('    "%s\\n\\t"' % ln for ln in self.lines)
-
-
-def linearize(e, ops, pending):
-    """Emit `ops` in order; before an MFMA whose fragments are still in flight, the exact lgkmcnt (LDS reads return in
-    order; the counter has 4 bits, so more than 15 younger reads wait for a few of them too)."""
-    pending = list(pending)
-    for op in ops:
-        if op[0] == "r":
-            e(op[2])
-            pending.append(op[1])
-        elif op[0] == "m":
-            need = [t for t in op[2] if t in pending]
-            if need:
-                last = max(len(pending) - 1 - pending[::-1].index(t) for t in need)
-                allowed = min(15, len(pending) - last - 1)
-                e(f"s_waitcnt lgkmcnt({allowed})")
-                pending = pending[len(pending) - allowed:]
-            e(op[1])
-        else:
-            e(op[1])
-    return pending
 
 
 def frag_reads(stage, kk, buf):
@@ -155,33 +121,6 @@ def tile_prologue(e):
     for ops in all_pieces(1)[:8]:
         for op in ops:
             e(op[1])
-
-
-def spread_after(mfmas, extras, start=0, end=None):
-    end = len(mfmas) if end is None else end
-    n = end - start
-    slots = [[] for _ in mfmas]
-    for k, ex in enumerate(extras):
-        slots[start + min(n - 1, (k * n) // max(1, len(extras)))].extend(ex)
-    ops = []
-    for m, s in zip(mfmas, slots):
-        ops.append(m)
-        ops.extend(s)
-    return ops
-
-
-def with_dma_tail(ops, dm, start=12):
-    """Insert the DMA op lists `dm` after every other MFMA from the (start+1)-th on."""
-    out, idx, cnt = [], 0, 0
-    for op in ops:
-        out.append(op)
-        if op[0] == "m":
-            cnt += 1
-            if cnt > start and idx < len(dm) and (cnt - start) % 2 == 1:
-                out.extend(dm[idx]); idx += 1
-    while idx < len(dm):
-        out.extend(dm[idx]); idx += 1
-    return out
 
 
 def main_loop(e):
@@ -333,7 +272,7 @@ def epilogue(e, accumulate):
 
 
 def generate(accumulate):
-    e = Emit("acc" if accumulate else "st")
+    e = Emit("gtw64", "acc" if accumulate else "st")
     main_loop(e)
     epilogue(e, accumulate)
     return e

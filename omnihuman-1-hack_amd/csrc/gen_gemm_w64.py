@@ -30,6 +30,9 @@ s[60:75] unpacked scalar arguments, s[80:91] scratch.
 import os
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gen_w64_common import Emit, linearize, spread_after, vr, with_dma_tail    # noqa: E402
+
 NI, NJ = 6, 4                   # n tiles (weights) x m tiles (activations) per wave
 STAGE = 81920
 WOFF = 32768                    # W tile behind the X tile inside a stage
@@ -38,18 +41,11 @@ NW = 12                         # W pieces (1 KiB) per wave and k tile: 2 NI
 KINDS = ("f32", "bf16", "gelu", "resid")
 
 
-PGR = False                     # configure(4, pgr=True): the "p256" streams (main_loop_pgr)
-SET = (96, 160)                 # p256: v[96:159] / v[160:223] = the 16 pieces (4 registers each) of a k tile in flight
-VDW = (224, 225)                # p256: LDS write address of the lane in stage 0 / 1 (X region; W: + WOFF)
-
-
-def configure(ni, pgr=False):
+def configure(ni):
     """Tile configuration of the streams generated next: ni = 6 -> 256 x 384 (the default), ni = 3 -> 256 x 192 (the
     "resid192" stream: 12 accumulator tiles per wave, all in AGPRs; v[96:255] + a[192:223] hold the tile's OLD C values,
-    requested during the k loop), ni = 4 with ``pgr`` -> 256 x 256, all 16 accumulator tiles in AGPRs and the 128 free
-    registers holding two k tiles of operands IN FLIGHT (main_loop_pgr)."""
-    global NI, STAGE, FB, NW, NTILES, PGR
-    PGR = pgr
+    requested during the k loop)."""
+    global NI, STAGE, FB, NW, NTILES
     NI = ni
     STAGE = 32768 + ni * 8192
     FB = 4 * ni + 4 * NJ
@@ -61,7 +57,6 @@ S_LDX, S_LDW, S_SXB, S_SWB, S_SXS, S_SWS, S_NK, S_SCB = "s60", "s61", "s62", "s6
 S_SCJ, S_N, S_MB, S_G1LO, S_G1ST, S_GC, S_COL0, S_REG = "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75"
 S_NXB, S_NWB, S_NEXT = "s76", "s77", "s78"      # next tile of this workgroup: X / W source offsets, != 0 if there is one
 S_COLN = "s89"                  # first column of the wave (elements) = S_COL0 / 4
-NPAIRS = 10                     # p0..p9 -> s[60:79]
 
 
 def acc(i, j):
@@ -73,44 +68,6 @@ def wfrag(buf, i):   return 32 + buf * FB + 4 * i
 def xfrag(buf, j):   return 32 + buf * FB + 4 * NI + 4 * j
 def XA(s, kk):       return 12 + s * 4 + kk
 def WA(s, kk):       return 20 + s * 4 + kk
-def vr(lo, n=1):     return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
-
-
-class Emit:
-    def __init__(self, tag):
-        self.lines, self.tag = [], tag
-
-    def __call__(self, s):
-        self.lines.append(s)
-
-    def lab(self, name):
-        return f".Lgw64{self.tag}_{name}_%="
-
-    def label(self, name):
-        self.lines.append(f"{name}:")
-
-    def text(self):
-        return "\n".join('    "%s\\n\\t"' % ln for ln in self.lines)
-
-
-def linearize(e, ops, pending):
-    pending = list(pending)
-    for op in ops:
-        if op[0] == "r":
-            e(op[2])
-            pending.append(op[1])
-        elif op[0] == "m":
-            need = [t for t in op[2] if t in pending]
-            if need:
-                last = max(pending.index(t) for t in need)
-                allowed = len(pending) - last - 1
-                assert allowed <= 15, allowed
-                e(f"s_waitcnt lgkmcnt({allowed})")
-                pending = pending[last + 1:]
-            e(op[1])
-        else:
-            e(op[1])
-    return pending
 
 
 def frag_reads(stage, kk, buf):
@@ -125,26 +82,12 @@ def frag_reads(stage, kk, buf):
 SWAP = False                    # "bf16vt": activations in the MFMA A slot, weights in the B slot -> a lane holds 4 consecutive m
 
 
-M16 = False                     # timing-only ablation: every 32x32x16 MFMA as TWO v_mfma_f32_16x16x32_bf16 on the same operand
-#                                 registers (the same flops, LDS and global traffic; the results are garbage) — does the shape
-#                                 that sustains 2.16 instead of 1.88 PFLOP/s on data-like operands (tools/mfma_shape_probe.py) pay
-#                                 inside a real k loop?
-
-
 def group_mfmas(buf, first=False):
     out = []
     for i in range(NI):
         for j in range(NJ):
             c = "0" if first else acc(i, j)
             a_, b_ = (xfrag(buf, j), wfrag(buf, i)) if SWAP else (wfrag(buf, i), xfrag(buf, j))
-            if M16:
-                t = i * NJ + j
-                base, f = (t * 16, "a") if t < 16 else (128 + (t - 16) * 16, "v")
-                for half in range(2):
-                    d = f"{f}[{base + 4 * half}:{base + 4 * half + 3}]"
-                    out.append(("m", f"v_mfma_f32_16x16x32_bf16 {d}, {vr(a_, 4)}, {vr(b_, 4)}, {d}",
-                                [f"W{buf}.{i}", f"X{buf}.{j}"] if half == 0 else []))
-                continue
             out.append(("m", f"v_mfma_f32_32x32x16_bf16 {acc(i, j)}, {vr(a_, 4)}, {vr(b_, 4)}, {c}",
                         [f"W{buf}.{i}", f"X{buf}.{j}"]))
     return out
@@ -171,10 +114,6 @@ def all_pieces(stage, xb=S_SXB, wb=S_SWB):
     return [dma_piece(stage, "x", q, xb, wb) for q in range(8)] + [dma_piece(stage, "w", q, xb, wb) for q in range(NW)]
 
 
-def unpack(e, pairs=range(NPAIRS)):
-    """Nothing to emit: gemm_w64.hip binds the packed scalar operands to s[60:79] directly ("{s[60:61]}" ...)."""
-
-
 def tile_prologue(e, xb, wb):
     """k tile 0 -> stage 0 (all 8 + NW pieces per wave), k tile 1 -> stage 1 (the 8 X pieces; the k loop issues the NW
     W pieces): 16 + NW LDS-DMA instructions."""
@@ -183,44 +122,12 @@ def tile_prologue(e, xb, wb):
         for op in ops:
             e(op[1])
     e("s_mov_b32 s80, 128")
-    for ops in (all_pieces(1, xb, wb) if PGR else all_pieces(1, xb, wb)[:8]):   # p256: k tile 1 whole (its k loop fetches to registers)
+    for ops in all_pieces(1, xb, wb)[:8]:
         for op in ops:
             e(op[1])
 
 
-def pro_pieces():
-    """LDS-DMA pieces of a tile's prologue that are younger than k tile 0's."""
-    return 8 + NW if PGR else 8
-
-
-def spread_after(mfmas, extras, start=0, end=None):
-    end = len(mfmas) if end is None else end
-    n = end - start
-    slots = [[] for _ in mfmas]
-    for k, ex in enumerate(extras):
-        slots[start + min(n - 1, (k * n) // max(1, len(extras)))].extend(ex)
-    ops = []
-    for m, s in zip(mfmas, slots):
-        ops.append(m)
-        ops.extend(s)
-    return ops
-
-
-SCHED = os.environ.get("OMH_GW64_SCHED", "0")     # experiment knob: where the W pieces of a k step are issued
-
-
-def with_dma_tail(ops, dm, start=12):
-    """Insert the DMA op lists `dm` after every other MFMA from the (start+1)-th on."""
-    out, idx, cnt = [], 0, 0
-    for op in ops:
-        out.append(op)
-        if op[0] == "m":
-            cnt += 1
-            if cnt > start and idx < len(dm) and (cnt - start) % 2 == 1:
-                out.extend(dm[idx]); idx += 1
-    while idx < len(dm):
-        out.extend(dm[idx]); idx += 1
-    return out
+PRO_PIECES = 8                  # LDS-DMA pieces of a tile's prologue that are younger than k tile 0's
 
 
 CPRE = 96                      # resid192: v[96:255] = old C of tiles 0..9, a[192:223] = tiles 10, 11
@@ -251,7 +158,6 @@ def main_loop(e, epi_vmem, cpre=False):
     order by `epi_vmem` stores / loads of the previous tile's epilogue (none for the workgroup's first tile, whose
     prologue stream ended with its own wait).  ``cpre``: k steps 0 .. NTILES-1 are peeled and each requests one
     accumulator tile's old C values (c_prefetch); K >= (NTILES + 2) k tiles."""
-    unpack(e)
     for kk in range(4):
         e(f"v_xor_b32 v112, {kk}, %[xh]")
         e(f"v_lshl_add_u32 {vr(XA(0, kk))}, v112, 5, %[xab]")
@@ -281,15 +187,7 @@ def main_loop(e, epi_vmem, cpre=False):
             mf = group_mfmas(kk & 1, first=(first and kk == 0))
             reads = [[r] for r in frag_reads(s, kk + 1, (kk + 1) & 1)]
             ops = spread_after(mf, reads, 0, min(14, NM))
-            if SCHED == "1":                                    # all W pieces in group 0
-                if kk == 0:
-                    ops = with_dma_tail(ops, rest, 0)
-            elif SCHED == "2":                                  # 8 in group 0 from the first MFMA, 4 in group 1
-                if kk == 0:
-                    ops = with_dma_tail(ops, rest[:8], 4)
-                elif kk == 1:
-                    ops = with_dma_tail(ops, rest[8:], 0)
-            elif kk < 2:
+            if kk < 2:
                 ops = with_dma_tail(ops, rest[kk * half:(kk + 1) * half], 12 if NM >= 24 else 2)
             elif ctile is not None:
                 ops = with_dma_tail(ops, [c_prefetch(ctile)], 2)
@@ -352,196 +250,6 @@ def main_loop(e, epi_vmem, cpre=False):
         e("s_nop 7")                                            # last MFMA results readable by VALU
 
 
-VOX, VOW = 226, 234             # p256: v[226:233] / v[234:241] = the lane's source offset of X / W piece q (swizzle + q row blocks)
-
-
-def load_piece(vset, operand, q):
-    """p256: one 1 KiB piece of a k tile as an ordinary buffer load into registers (piece index: X 0..7, W 8..15); the
-    same source addresses as dma_piece (swizzle on the lane's offset), the piece's row block in a per-piece offset
-    register, the tile's k offset in s81 (X) / s82 (W)."""
-    dst = SET[vset] + 4 * (q if operand == "x" else 8 + q)
-    vo = (VOW if operand == "w" else VOX) + q
-    rs, sreg = ("%[rb]", "s82") if operand == "w" else ("%[ra]", "s81")
-    return ("v", f"buffer_load_dwordx4 {vr(dst, 4)}, v{vo}, {rs}, {sreg} offen{LDMOD}")
-
-
-def write_piece(vset, stage, idx):
-    """p256: piece idx of the k tile held in register set vset -> LDS stage `stage`, where the LDS-DMA would have put it
-    (lane-linear inside the wave's 1 KiB piece)."""
-    off = idx * 1024 if idx < 8 else WOFF + (idx - 8) * 1024
-    return ("w", f"P{idx}", f"ds_write_b128 v{VDW[stage]}, {vr(SET[vset] + 4 * idx, 4)} offset:{off}", idx)
-
-
-LDMOD = ""                      # cache-policy bits of the p256 loads (experiment: " nt", " sc1", ...)
-PABL = ""                       # timing-only ablation of main_loop_pgr (OMH_GEMM_W64_P256 = a..e, tools/gemm_p256_abl.py):
-#   "noload" no global loads, "nowrite" no LDS writes, "nomem" neither, "nobar" no barrier, "noread" no fragment reads
-
-
-def linearize_pgr(e, ops, pending, vm):
-    """linearize + the in-order VMEM counter.  ``vm`` = [loads outstanding that are OLDER than piece 0 of the k tile
-    being written — none — then: loads of that tile and younger ones issued before this op list, loads issued in it]:
-    a ds_write of piece i waits until at most (vm[0] - 1 - i) + vm[1] loads are outstanding."""
-    pending = list(pending)
-    for op in ops:
-        if op[0] == "r":
-            if PABL == "noread":
-                continue
-            e(op[2])
-            pending.append(op[1])
-        elif op[0] == "w":
-            if PABL in ("nowrite", "nomem"):
-                continue
-            if PABL != "noload":
-                e(f"s_waitcnt vmcnt({vm[0] - 1 - op[3] + vm[1]})")
-            e(op[2])
-            pending.append(op[1])
-        elif op[0] == "v":
-            if PABL in ("noload", "nomem"):
-                continue
-            e(op[1])
-            vm[1] += 1
-        elif op[0] == "m":
-            need = [t for t in op[2] if t in pending]
-            if need:
-                last = max(pending.index(t) for t in need)
-                allowed = len(pending) - last - 1
-                e(f"s_waitcnt lgkmcnt({min(allowed, 15)})")
-                pending = pending[last + 1:]
-            e(op[1])
-        else:
-            e(op[1])
-    return pending
-
-
-def slots(mfmas, first_half, second_half):
-    """One extra per MFMA gap: ``first_half`` after MFMAs 0.., ``second_half`` after MFMAs 8.. of the group of 16 (a
-    single wave per SIMD issues in order: a gap with two or three memory instructions is a gap in which the matrix pipe
-    runs dry — measured, tools/gemm_p256_abl.py)."""
-    assert len(mfmas) == 16 and len(first_half) <= 8 and len(second_half) <= 8
-    ops = []
-    for k, m in enumerate(mfmas):
-        ops.append(m)
-        if k < 8 and k < len(first_half):
-            ops.append(first_half[k])
-        if k >= 8 and k - 8 < len(second_half):
-            ops.append(second_half[k - 8])
-    return ops
-
-
-def main_loop_pgr(e, epi_vmem):
-    """The k loop of one 256 x 256 output tile with the operands of two k tiles in flight in REGISTERS.
-
-    The LDS-DMA loop above can only request a k tile when an LDS stage is free for it: 80 of the 160 KiB hold the tile
-    being multiplied, so at most one k tile (less, on average) is on its way, and the W pieces of tile kt+1 have half a
-    k step to arrive.  Here a k tile is 16 ordinary 1 KiB loads per wave into v[96:159] / v[160:223] (the accumulators
-    are all AGPRs), issued TWO steps before the tile is multiplied, and written to the LDS stage one step later, when
-    the stage has been read for the last time: every load has a whole k step (>= 2 048 MFMA cycles) to land.  Every gap
-    between two MFMAs carries exactly ONE memory instruction (64 MFMAs, 32 fragment reads, 16 loads, 16 LDS writes per
-    step).  Step tau on stage s = tau & 1, register set of k tile t = t & 1:
-        groups 0..2  MFMAs kk = 0..2 || gaps 0-7: fragment reads of kk + 1 || gaps 8-15: ds_write of k tile tau+1
-                     (set s^1 -> stage s^1; 16 in 24 gaps) and the 8 W pieces of k tile tau+2 (-> set s)
-        lgkmcnt(0), barrier                      (stage s^1 complete, stage s read for the last time, set s^1 free)
-        group 3      MFMAs kk = 3 || gaps 0-7: fragment reads kk = 0 of stage s^1 || gaps 8-15: the 8 X pieces of k tile
-                     tau+3 (-> set s^1)
-    Same MFMA, same order over k as every other GEMM kernel of the library: identical bits.  The prologue (k tiles 0
-    and 1, LDS-DMA, issued from the previous tile's epilogue) and the epilogues are the LDS-DMA streams'."""
-    unpack(e)
-    for kk in range(4):
-        e(f"v_xor_b32 v112, {kk}, %[xh]")
-        e(f"v_lshl_add_u32 {vr(XA(0, kk))}, v112, 5, %[xab]")
-        e(f"v_lshl_add_u32 {vr(WA(0, kk))}, v112, 5, %[wab]")
-        e(f"v_add_u32 {vr(XA(1, kk))}, {STAGE}, {vr(XA(0, kk))}")
-        e(f"v_add_u32 {vr(WA(1, kk))}, {STAGE}, {vr(WA(0, kk))}")
-    e(f"v_lshl_add_u32 v{VDW[0]}, %[vlane], 4, {S_LDX}")          # the wave's X piece 0 + 16 lane
-    e(f"v_add_u32 v{VDW[1]}, {STAGE}, v{VDW[0]}")
-    for q in range(8):                                          # per-piece source offsets: row block q of the wave's rows
-        e(f"s_mul_i32 s88, {S_SXS}, {q}")
-        e(f"v_add_u32 v{VOX + q}, s88, {'%[vox1]' if q & 1 else '%[vox0]'}")
-        e(f"s_mul_i32 s88, {S_SWS}, {q}")
-        e(f"v_add_u32 v{VOW + q}, s88, {'%[vow1]' if q & 1 else '%[vow0]'}")
-    # the X pieces of k tile 2 (what a step's group 3 does for the step after the next)
-    e(f"s_add_u32 s81, {S_SXB}, 256")
-    n_pre = 0
-    if PABL not in ("noload", "nomem"):
-        for q in range(8):
-            e(load_piece(0, "x", q)[1])
-        n_pre = 8
-    e(f"s_add_u32 s82, {S_SWB}, 256")                           # W pieces: k tile 2 next
-    e(f"s_add_u32 s81, {S_SXB}, 384")                           # X pieces: k tile 3 next
-    e(f"s_waitcnt vmcnt({min(63, 16 + epi_vmem + n_pre)})")      # k tile 0 has landed (in-order counter)
-    e("s_barrier")
-    pend = linearize_pgr(e, frag_reads(0, 0, 0), [], [0, 0])
-    LOOP_PENDING = list(pend)
-    LOOP, DONE = e.lab("loop"), e.lab("done")
-
-    def body(s, first=False, left=3):
-        """``left``: k steps after this one (>= 3: the steady state).  ``first``: step 0 — k tile 1 came by LDS-DMA, there
-        is nothing to write."""
-        wl = [load_piece(s, "w", q) for q in range(8)] if left >= 2 else []             # W pieces of k tile tau+2
-        xl = [load_piece(s ^ 1, "x", q) for q in range(8)] if left >= 3 else []         # X pieces of k tile tau+3
-        wr = [write_piece(s ^ 1, s ^ 1, i) for i in range(16)] if (left >= 1 and not first) else []
-        # second halves of groups 0..2: W W L, W W L, ... (16 writes, 8 loads in 24 gaps)
-        mix = []
-        for k in range(8):
-            mix += wr[2 * k:2 * k + 2] + wl[k:k + 1]
-        mix += [None] * (24 - len(mix))
-        # loads older than piece 0 of the k tile being written do not exist; counted from it: its own 16, the 8 X pieces
-        # of the next k tile (previous step's group 3)
-        vm = [16 + (8 if left >= 2 else 0), 0]
-        pend = LOOP_PENDING
-        for kk in range(3):
-            mf = group_mfmas(kk & 1, first=(first and kk == 0))
-            rd = frag_reads(s, kk + 1, (kk + 1) & 1)
-            pend = linearize_pgr(e, slots(mf, rd, [m for m in mix[8 * kk:8 * kk + 8] if m is not None]), pend, vm)
-        if left == 0:
-            linearize_pgr(e, group_mfmas(1), pend, [0, 0])
-            return
-        if first:
-            e(f"s_waitcnt vmcnt({8 + vm[1]})")                   # k tile 1 (LDS-DMA) is in stage 1: only k tile 2's loads may be out
-        e("s_waitcnt lgkmcnt(0)")
-        if PABL != "nobar":
-            e("s_barrier")
-        if left >= 2:
-            e("s_add_u32 s82, s82, 128")
-        ops = slots(group_mfmas(1), frag_reads(s ^ 1, 0, 0), xl)
-        pend = linearize_pgr(e, ops, [], [0, 0])
-        if left >= 3:
-            e("s_add_u32 s81, s81, 128")
-        assert pend == LOOP_PENDING or PABL == "noread", (pend, LOOP_PENDING)
-
-    def step_check(tail):
-        e(f"s_sub_u32 s83, {S_NK}, s84")                        # k steps left, this one included (>= 3 here)
-        e("s_cmp_eq_u32 s83, 3")
-        e(f"s_cbranch_scc1 {tail}")
-
-    TAIL1, TAIL0 = e.lab("tail1"), e.lab("tail0")
-    body(0, first=True)                                         # k step 0 (K >= 4 k tiles: 3 steps follow)
-    e("s_mov_b32 s84, 1")
-    e.label(LOOP)
-    step_check(TAIL1)
-    body(1)
-    e("s_add_u32 s84, s84, 1")
-    step_check(TAIL0)
-    body(0)
-    e("s_add_u32 s84, s84, 1")
-    e(f"s_branch {LOOP}")
-    e.label(TAIL1)
-    body(1, left=2)
-    body(0, left=1)
-    body(1, left=0)
-    e(f"s_branch {DONE}")
-    e.label(TAIL0)
-    body(0, left=2)
-    body(1, left=1)
-    body(0, left=0)
-    e.label(DONE)
-    e("s_waitcnt vmcnt(0)")
-    e("s_waitcnt lgkmcnt(0)")
-    e("s_barrier")                                              # every wave is done with the LDS stages
-    for _ in range(3):
-        e("s_nop 7")                                            # last MFMA results readable by VALU
-
-
 # ---------------------------------------------------------------- epilogues
 T = 32                       # v[32:47] tile values
 GV, BV = 48, 64              # v[48:63] gate runs (GELU: temporaries), v[64:79] bias runs
@@ -580,7 +288,7 @@ def column_vectors(e, kind):
     e(f"s_cmp_eq_u32 {S_NEXT}, 0")
     e(f"s_cbranch_scc1 {NONE}")
     tile_prologue(e, S_NXB, S_NWB)
-    e(f"s_waitcnt vmcnt({8 + NW + pro_pieces()})")                # the column vectors (older than the prologue's DMA pieces)
+    e(f"s_waitcnt vmcnt({8 + NW + PRO_PIECES})")                # the column vectors (older than the prologue's DMA pieces)
     e(f"s_branch {JOIN}")
     e.label(NONE)
     e("s_waitcnt vmcnt(0)")
@@ -737,20 +445,12 @@ def epilogue_resid(e):
     v[128:255] therefore go first — each frees 16 registers when it has been read — and from then on up to 11 tiles
     of old values are in flight instead of 3 (ring slots: v[80:127] + the freed accumulator registers)."""
     es = 4
-    depth = int(os.environ.get("OMH_GW64_RING", "11"))
-    # experiment knob, off: a second permlane level gives a lane 16 CONSECUTIVE columns (64 B per lane, full 128-B lines
-    # per row and instruction pair) — measured 197 -> 202 us on the o-projection: the epilogue is not bound by request count
-    W16 = os.environ.get("OMH_GW64_WIDE16", "0") == "1"
+    depth = 11                                                   # tiles of old values in flight at most
+    # (a second permlane level, giving a lane 16 CONSECUTIVE columns — 64 B per lane, full 128-B lines per row and
+    # instruction pair — measured 197 -> 202 us on the o-projection: the epilogue is not bound by request count)
     column_vectors(e, "resid")
-    VLR_, VCOL_, VOC_ = VLR, VCOL, "%[voc]"
-    if W16:
-        e(f"v_add_u32 v24, {VLR}, {VH}")                         # vector region + 64 h bytes
-        e(f"v_add_u32 v25, {VH}, %[voc]")                        # row offset + 16 h columns
-        e(f"v_lshrrev_b32 v26, 2, {VH}")
-        e(f"v_add_u32 v26, v26, {VCOL}")                         # first column of the wave + 16 h
-        VLR_, VCOL_, VOC_ = "v24", "v26", "v25"
     seq = [(4 + m // 4, m % 4) for m in range(8)] + [(t // NJ, t % NJ) for t in range(16)]
-    free = [CO, CO + 16, CO + 32][:min(3, depth)]
+    free = [CO, CO + 16, CO + 32]
     slot_of, issued, nxt = {}, [], [0]
 
     def request():
@@ -764,8 +464,8 @@ def epilogue_resid(e):
             e(f"s_add_u32 s88, s88, {S_SCB}")
             for p in range(2):
                 for q in range(2):
-                    off = (i * 32) * es + p * 32 + q * 16 if W16 else (i * 32 + 16 * p) * es + q * 16
-                    e(f"buffer_load_dwordx4 {vr(sl + p * 8 + q * 4, 4)}, {VOC_}, %[rc], s88 offen offset:{off}")
+                    off = (i * 32 + 16 * p) * es + q * 16
+                    e(f"buffer_load_dwordx4 {vr(sl + p * 8 + q * 4, 4)}, %[voc], %[rc], s88 offen offset:{off}")
                     issued.append(("L", k))
             nxt[0] += 1
 
@@ -777,14 +477,14 @@ def epilogue_resid(e):
         e(f"s_add_u32 s85, s85, {S_SCB}")
         e(f"v_add_u32 v{VCOLT}, {32 * j}, {VROW}")
         e(f"v_cmp_le_u32 vcc, {S_MB}, v{VCOLT}")
-        e(f"v_add_u32 v{VCOLT}, 1536, {VLR_}")
-        e(f"v_cndmask_b32 v{VSEL}, {VLR_}, v{VCOLT}, vcc")
+        e(f"v_add_u32 v{VCOLT}, 1536, {VLR}")
+        e(f"v_cndmask_b32 v{VSEL}, {VLR}, v{VCOLT}, vcc")
         for p in range(2):
-            col = (i * 32) * 4 + p * 32 if W16 else (i * 32 + 16 * p) * 4
+            col = (i * 32 + 16 * p) * 4
             e(f"ds_read_b128 {vr(GV + p * 8, 4)}, v{VSEL} offset:{col}")
             e(f"ds_read_b128 {vr(GV + p * 8 + 4, 4)}, v{VSEL} offset:{col + 16}")
-            e(f"ds_read_b128 {vr(BV + p * 8, 4)}, {VLR_} offset:{768 + col}")
-            e(f"ds_read_b128 {vr(BV + p * 8 + 4, 4)}, {VLR_} offset:{768 + col + 16}")
+            e(f"ds_read_b128 {vr(BV + p * 8, 4)}, {VLR} offset:{768 + col}")
+            e(f"ds_read_b128 {vr(BV + p * 8 + 4, 4)}, {VLR} offset:{768 + col + 16}")
         for r_ in range(16):
             if t < 16:
                 e(f"v_accvgpr_read_b32 v{T + r_}, a{t * 16 + r_}")
@@ -796,10 +496,6 @@ def epilogue_resid(e):
         for q0 in (0, 2):                                        # quads (0,1), (2,3) -> two runs of 8 consecutive n
             for r_ in range(4):
                 e(f"v_permlane32_swap_b32 v{T + 4 * q0 + r_}, v{T + 4 * (q0 + 1) + r_}")
-        if W16:                                                  # ... and the two runs -> 16 consecutive n per lane
-            e("s_nop 1")
-            for r_ in range(8):
-                e(f"v_permlane32_swap_b32 v{T + r_}, v{T + 8 + r_}")
         request()
         e("s_waitcnt lgkmcnt(0)")
         last = max(x for x, tag in enumerate(issued) if tag == ("L", k))
@@ -807,7 +503,7 @@ def epilogue_resid(e):
         sl = slot_of[k]
         for p in range(2):
             v0 = T + 8 * p
-            e(f"v_add_u32 v{VCOLT}, {i * 32 + (8 if W16 else 16) * p}, {VCOL_}")
+            e(f"v_add_u32 v{VCOLT}, {i * 32 + 16 * p}, {VCOL}")
             e(f"v_cmp_gt_u32 vcc, {S_N}, v{VCOLT}")
             e("s_and_saveexec_b64 s[86:87], vcc")
             for r_ in range(0, 8, 2):
@@ -816,9 +512,9 @@ def epilogue_resid(e):
                 e(f"v_pk_mul_f32 {vr(v0 + r_, 2)}, {vr(v0 + r_, 2)}, {vr(GV + p * 8 + r_, 2)}")
             for r_ in range(0, 8, 2):
                 e(f"v_pk_add_f32 {vr(v0 + r_, 2)}, {vr(sl + p * 8 + r_, 2)}, {vr(v0 + r_, 2)}")
-            off = (i * 32) * es + p * 32 if W16 else (i * 32 + 16 * p) * es
-            e(f"buffer_store_dwordx4 {vr(v0, 4)}, {VOC_}, %[rc], s85 offen offset:{off}")
-            e(f"buffer_store_dwordx4 {vr(v0 + 4, 4)}, {VOC_}, %[rc], s85 offen offset:{off + 16}")
+            off = (i * 32 + 16 * p) * es
+            e(f"buffer_store_dwordx4 {vr(v0, 4)}, %[voc], %[rc], s85 offen offset:{off}")
+            e(f"buffer_store_dwordx4 {vr(v0 + 4, 4)}, %[voc], %[rc], s85 offen offset:{off + 16}")
             issued += [("S", k), ("S", k)]
             e("s_nop 1")
             e("s_mov_b64 exec, s[86:87]")
@@ -1038,12 +734,9 @@ EPI_VMEM_TILE = {"f32": 4, "bf16": 2, "gelu": 2, "geluaux": 4, "resid": 8, "resi
 
 def generate(kind, tag=None):
     global SWAP
-    e = Emit(tag or kind)
+    e = Emit("gw64", tag or kind)
     SWAP = kind == "bf16vt"
-    if PGR:
-        main_loop_pgr(e, EPI_VMEM_TILE[kind] * NTILES)
-    else:
-        main_loop(e, EPI_VMEM_TILE[kind] * NTILES, cpre=(kind == "resid192"))
+    main_loop(e, EPI_VMEM_TILE[kind] * NTILES, cpre=(kind == "resid192"))
     SWAP = False
     if kind == "bf16vt":
         epilogue_vt(e)
@@ -1059,10 +752,9 @@ def generate(kind, tag=None):
 
 
 def first_prologue(tag="pro"):
-    e = Emit(tag)
-    unpack(e, (0, 2, 8))
+    e = Emit("gw64", tag)
     tile_prologue(e, S_NXB, S_NWB)
-    e(f"s_waitcnt vmcnt({pro_pieces()})")
+    e(f"s_waitcnt vmcnt({PRO_PIECES})")
     return e
 
 
@@ -1072,34 +764,6 @@ def main():
     configure(3)                                                 # the 256 x 192 gated-residual stream (old C prefetched)
     streams += [("PRO192", first_prologue("pro192")), ("RESID192", generate("resid192")),
                 ("F32_192", generate("f32", "f32n3")), ("BF16_192", generate("bf16", "bf16n3"))]
-    # Round 6 experiment, NOT part of the shipped library (the tracked .inc is generated without it): the 256 x 256 streams
-    # with two k tiles in flight in registers (main_loop_pgr).  OMH_GW64_P256=1 generates them (gemm_w64.hip compiles its
-    # K_*_P kinds when the macros exist), OMH_GW64_ABLATIONS=1 adds five timing-only builds of the fp32 one
-    # (OMH_GW64_ABL_SET=ldmod: cache-policy variants of its loads instead).  Measured (profiles/r06_gemm_p256.txt): bit for
-    # bit the shipped kernels' results, 4-12 % SLOWER than the 256 x 384 LDS-DMA streams — the L2 -> CU fill path delivers
-    # ~21 B/clk/CU however early the loads are issued, so bytes per flop (tile area) decide, not prefetch depth.
-    if os.environ.get("OMH_GW64_P256", "0") == "1" or os.environ.get("OMH_GW64_ABLATIONS", "0") == "1":
-        configure(4, pgr=True)
-        streams += [("PRO256", first_prologue("pro256"))] + [(f"{kind.upper()}_P256", generate(kind, f"{kind}p4"))
-                                                             for kind in ("f32", "bf16", "gelu", "resid")]
-    if os.environ.get("OMH_GW64_ABLATIONS", "0") == "1":          # timing-only builds
-        global PABL, LDMOD, M16
-        if os.environ.get("OMH_GW64_ABL_SET", "abl") == "m16":    # the SHIPPED 256 x 384 fp32 stream on 16x16x32 MFMAs (garbage results)
-            configure(6)
-            M16 = True
-            streams.append(("F32_M16", generate("f32", "f32m16")))
-            M16 = False
-            configure(4, pgr=True)
-        if os.environ.get("OMH_GW64_ABL_SET", "abl") == "ldmod":
-            for tag, mod in (("A", " nt"), ("B", " sc1"), ("C", " sc0"), ("D", " sc0 sc1"), ("E", " sc1 nt")):
-                LDMOD = mod
-                streams.append((f"F32_P256_{tag}", generate("f32", f"f32p4{tag.lower()}")))
-            LDMOD = ""
-        else:
-            for tag, abl in (("A", "noload"), ("B", "nowrite"), ("C", "nomem"), ("D", "nobar"), ("E", "noread")):
-                PABL = abl
-                streams.append((f"F32_P256_{tag}", generate("f32", f"f32p4{tag.lower()}")))
-            PABL = ""
     configure(6)
     for name, e in streams:
         print(f"#define OMH_GEMM_W64_ASM_{name} \\")

@@ -12,10 +12,10 @@
 // process (the first omh_opt() / omh_set_option() call: variable OMH_<NAME> seeds option <NAME>); after that the launch
 // path never calls getenv and a switch changes only through omh_set_option().  omh_opt() returns NULL for an unset option.
 #define OMH_OPTIONS(X)                                                                                                   \
-    X(ATTN_KERNEL) X(ATTN_SPLIT) X(W64_SPLIT) X(W64_VARIANT) X(CONV_PERSIST) X(CONV_W64_UP2) X(LN_RPW) X(GEMM_GROUP_M)    \
+    X(ATTN_KERNEL) X(ATTN_SPLIT) X(W64_SPLIT) X(CONV_PERSIST) X(CONV_W64_UP2) X(LN_RPW) X(GEMM_GROUP_M)                  \
     X(GEMM_TILE) X(GEMM_RULE) X(GEMM_KERNEL) X(GEMM_W64_GBWD) X(GEMM_W64_GAUX) X(GEMM_W64_R192) X(GEMM_W64_BF16M)        \
     X(GEMM_W64_N192) X(GEMM_TN_SPLIT) X(GEMM_TN_W64) X(GEMM_TN_TILE) X(GEMM_TN_GROUP_TILE) X(GEMM_SPLITK) X(CONV_TILE)   \
-    X(CONV_WIDE_MIN) X(CONV_W64) X(CONV_FUSE_NORM) X(CONV_KW3) X(GEMM_QKV) X(ATTN_BWD_W64) X(GEMM_W64_P256) X(RMS_PAIR_ROW)  \
+    X(CONV_WIDE_MIN) X(CONV_W64) X(CONV_FUSE_NORM) X(CONV_KW3) X(GEMM_QKV) X(ATTN_BWD_W64) X(RMS_PAIR_ROW)                  \
     X(ATTN_BOUNDED) X(W64_SCHED) X(RMS_PAIR_BOUND)
 enum OmhOpt {
 #define X(n) OMH_OPT_##n,

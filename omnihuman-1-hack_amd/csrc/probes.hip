@@ -120,8 +120,8 @@ extern "C" int omh_probe_mfma_tflops(int32_t random_operands, int32_t iters, flo
 
 
 // A HIP stream confined to a subset of the CUs (hipExtStreamCreateWithCUMask): the training step's weight-gradient stream
-// can be kept off the CUs the main stream's latency-critical kernels run on (model_train.OMH_WGRAD_CU_MASK, an A/B
-// switch; measured in DESIGN.md 4.2).  ``cus_per_32``: how many of every 32 consecutive mask bits are set (1..32), taken
+// can be kept off the CUs the main stream's latency-critical kernels run on (measured slower and not adopted, DESIGN.md
+// 4.2: a probe's entry, nothing in the package calls it).  ``cus_per_32``: how many of every 32 consecutive mask bits are set (1..32), taken
 // from the low end (``high`` != 0: from the high end — the complement of a low mask of 32 - cus_per_32) — whatever the
 // driver's bit -> (XCD, CU) interleave is, every XCD then contributes the same number of CUs.
 extern "C" int omh_stream_create_cu_mask(int32_t cus_per_32, int32_t high, omh_stream_t* stream_out) {

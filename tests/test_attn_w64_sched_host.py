@@ -22,7 +22,6 @@ def streams():
     spec = importlib.util.spec_from_file_location("gen_attn_w64_under_test", GEN)
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
-    assert not gen.ABL
     return {(v, s): gen.generate(v, s).lines for v in VARIANTS for s in (0, 1)}, gen
 
 
