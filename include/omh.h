@@ -1045,6 +1045,50 @@ int omh_adamw_pack_multi_dev(const int64_t* table, int32_t n_entries, int64_t to
                              float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const float* coef,
                              omh_stream_t stream);
 
+/* Additive to ABI v12 (OMH_ABI_VERSION unchanged, no existing struct or entry changed): AdamW with FP8 block-scaled
+ * moments, 2.125 bytes of optimizer state per weight instead of 8.
+ *
+ * THE FORMAT.  A moment of a weight viewed as [rows, cols] is kept as
+ *   codes  uint8 [rows, cols]              OCP e4m3fn bit patterns (bias 7, largest finite 448 = 0x7e, 0x7f / 0xff NaN;
+ *                                          not the fnuz flavour), 4-byte aligned when cols % 4 == 0;
+ *   scales fp32  [rows, ceil(cols / 64)]   one per block: block b of row r covers columns [64 b, min(64 b + 64, cols)).
+ * A block never crosses a row; the last block of a row may be short.
+ *   first moment:   m = decode(code) * scale
+ *   second moment:  the stored quantity is its root r = sqrt(v):  v = (decode(code) * scale)^2  (half the dynamic range).
+ * Quantising a block of values x:  scale = max|x| / 448 (fp32, NOT rounded to a power of two: a decay of the whole block
+ * by beta then lands in the scale and leaves the codes alone),  code = RNE_e4m3(x / scale), |x / scale| clamped to 448.
+ * An all-zero block has scale 0 and codes 0 and decodes to 0.  An r code is raised to 0x01 (the smallest subnormal)
+ * whenever v > 0 would round to code 0, so a live first moment never meets a zero denominator.  For finite values the
+ * NaN codes 0x7f / 0xff are never written.
+ * Non-finite values: a block that holds a NaN gets scale NaN and codes 0; one that holds +-inf gets scale inf, code 0 for
+ * its finite values and +-448 for the infinite ones.  Either way the whole block decodes to non-finite values and every
+ * later step keeps it so — what fp32 moments do element by element happens here block by block.
+ *
+ * omh_adamw8_pack_multi: omh_adamw_pack_multi on such state.  table: DEVICE array of n_entries x 13 int64
+ *   {param, grad (fp32 [rows, cols] contiguous), m codes, m scales, r codes, r scales, dst, dstT, rows, cols, ld_dst,
+ *    ld_dstT, first_tile};  dst / dstT: the bf16 operand copies as in omh_adamw_pack_multi, either or both may be 0 (a
+ *   plain weight).  One workgroup per 64 x 64 tile, first_tile = running sum of ceil(rows / 64) * ceil(cols / 64).
+ * One step on a block: decode m_old, r_old; v_old = r_old^2; g' = g / grad_scale (times *coef in the _dev form, in that
+ * association); m = beta1 m_old + (1 - beta1) g', v = beta2 v_old + (1 - beta2) g'^2; the parameter update is
+ * omh_adamw_multi's expression on these fresh, unquantised m and v (bias corrections and eps alike); then m and
+ * r = sqrt(v) are quantised as above.  A non-finite gradient makes the parameter non-finite as the fp32 entries do.
+ * The copies are the bf16 images of the parameters just written.  Nothing outside [rows, cols] is written. */
+int omh_adamw8_pack_multi(const int64_t* table, int32_t n_entries, int64_t total_tiles, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                          omh_stream_t stream);
+int omh_adamw8_pack_multi_dev(const int64_t* table, int32_t n_entries, int64_t total_tiles, float lr, float beta1,
+                              float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                              const float* coef, omh_stream_t stream);
+/* fp32 moments <-> the format above, for state-dict conversion.  table: DEVICE array of n_entries x 6 int64
+ * {fp32 [rows, cols] contiguous, codes, scales, rows, cols, first_tile}, tiles as above.  second_moment != 0: the fp32
+ * tensor is v (>= 0): omh_moments_quantize stores sqrt(v), omh_moments_dequantize returns the square of what it decodes.
+ * All four entries return OMH_E_BADARG for a null table (or coef), counts <= 0 or more than 2^31 - 1 tiles, before the
+ * device is touched. */
+int omh_moments_quantize(const int64_t* table, int32_t n_entries, int64_t total_tiles, int32_t second_moment,
+                         omh_stream_t stream);
+int omh_moments_dequantize(const int64_t* table, int32_t n_entries, int64_t total_tiles, int32_t second_moment,
+                           omh_stream_t stream);
+
 /* Additive to ABI v12 (OMH_ABI_VERSION unchanged, no existing struct or entry changed): low-rank adapters (LoRA) on the
  * block Linears.  The reference has no adapters (its trainers update whole backbones, distilled_trainer.py:69-75), so
  * there is no reference line to follow; the definition is the published one (Hu et al. 2021): an adapted Linear

@@ -301,6 +301,10 @@ _SIGS = {
     "omh_adamw_pack_multi": (i32, [vp, i32, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "omh_adamw_multi_dev": (i32, [vp, i32, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
     "omh_adamw_pack_multi_dev": (i32, [vp, i32, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
+    "omh_adamw8_pack_multi": (i32, [vp, i32, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
+    "omh_adamw8_pack_multi_dev": (i32, [vp, i32, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
+    "omh_moments_quantize": (i32, [vp, i32, i64, i32, vp]),
+    "omh_moments_dequantize": (i32, [vp, i32, i64, i32, vp]),
     "omh_grad_norm_multi": (i32, [vp, i32, i64, vp, vp, f32, f32, vp]),
     "omh_scale_multi": (i32, [vp, i32, i64, vp, vp]),
     "omh_ema_update": (i32, [vp, vp, i64, f32, vp]),

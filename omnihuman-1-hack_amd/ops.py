@@ -1242,6 +1242,43 @@ def adamw_pack_multi_dev(table, n_entries, total_tiles, lr, beta1, beta2, eps, w
                                        grad_scale, _coef(coef), _stream()), "omh_adamw_pack_multi_dev")
 
 
+def adamw8_pack_multi(table, n_entries, total_tiles, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+    """AdamW on FP8 block-scaled moments (+ the bf16 operand copies where an entry has them) in one launch; ``table``:
+    int64 device tensor [n_entries, 13] = {param, grad, m codes, m scales, r codes, r scales, dst, dstT, rows, cols,
+    ld_dst, ld_dstT, first tile} (include/omh.h states the format)."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 13)
+    check(lib.omh_adamw8_pack_multi(_p(table), n_entries, total_tiles, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                                    _stream()), "omh_adamw8_pack_multi")
+
+
+def adamw8_pack_multi_dev(table, n_entries, total_tiles, lr, beta1, beta2, eps, weight_decay, step, coef, grad_scale=1.0):
+    """``adamw8_pack_multi`` with the gradient multiplied by ``coef[0]``, an fp32 DEVICE scalar."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 13)
+    check(lib.omh_adamw8_pack_multi_dev(_p(table), n_entries, total_tiles, lr, beta1, beta2, eps, weight_decay, step,
+                                        grad_scale, _coef(coef), _stream()), "omh_adamw8_pack_multi_dev")
+
+
+def moments_quantize(table, n_entries, total_tiles, second_moment):
+    """fp32 moments -> FP8 codes + fp32 block scales for every entry of ``table``: int64 device tensor [n_entries, 6] =
+    {fp32 [rows, cols], codes uint8 [rows, cols], scales fp32 [rows, ceil(cols / 64)], rows, cols, first tile}.
+    ``second_moment``: the fp32 tensors hold v and the codes sqrt(v) (include/omh.h)."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 6)
+    check(lib.omh_moments_quantize(_p(table), n_entries, total_tiles, int(bool(second_moment)), _stream()),
+          "omh_moments_quantize")
+
+
+def moments_dequantize(table, n_entries, total_tiles, second_moment):
+    """The inverse of ``moments_quantize`` over the same table: the fp32 tensors are written (``second_moment``: with v =
+    the square of what the codes decode to)."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n_entries, 6)
+    check(lib.omh_moments_dequantize(_p(table), n_entries, total_tiles, int(bool(second_moment)), _stream()),
+          "omh_moments_dequantize")
+
+
 NORM_CHUNK = 16384                                              # OMH_NORM_CHUNK (include/omh.h)
 
 

@@ -84,6 +84,71 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     return out[0]
 
 
+# ------------------------------------------------------------------------------------- FP8 block-scaled moments
+# include/omh.h states the format: uint8 e4m3fn codes [rows, cols] + fp32 scales [rows, ceil(cols / 64)] per moment, the
+# second moment kept as its root.
+_STATE8 = ("exp_avg_q", "exp_avg_scale", "exp_avg_sq_root_q", "exp_avg_sq_root_scale")
+
+
+def _view8(p):
+    """[rows, cols] of a parameter with 8-bit moments: the pack tables' view of Linear and patch-embedding weights."""
+    rows = p.shape[0]
+    return rows, p.numel() // rows
+
+
+def _tiles8(rows, cols):
+    return ((rows + 63) // 64) * ((cols + 63) // 64)
+
+
+def _convert_moments(fp32s, codes, scales, second_moment, quantize):
+    """One omh_moments_quantize / omh_moments_dequantize launch over the triples (fp32 [rows, cols], codes, scales)."""
+    if not fp32s:
+        return
+    full, tile0 = [], 0
+    for x, q, sc in zip(fp32s, codes, scales):
+        rows, cols = q.shape
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == rows * cols
+        assert q.dtype == torch.uint8 and q.is_contiguous() and sc.dtype == torch.float32 and sc.is_contiguous()
+        assert tuple(sc.shape) == (rows, (cols + 63) // 64) and x.device == q.device == sc.device
+        full.append([x.data_ptr(), q.data_ptr(), sc.data_ptr(), rows, cols, tile0])
+        tile0 += _tiles8(rows, cols)
+    dev = fp32s[0].device
+    with torch.cuda.device(dev):
+        table = torch.tensor(full, dtype=torch.int64).to(dev)
+        (ops.moments_quantize if quantize else ops.moments_dequantize)(table, len(full), tile0, second_moment)
+
+
+def quantize_moments(tensors, second_moment):
+    """fp32 moments (each viewed as [shape[0], numel // shape[0]]) -> [(codes uint8 [rows, cols], scales fp32 [rows,
+    ceil(cols / 64)])] on their device, one launch per device; ``second_moment``: the tensors hold v, the codes sqrt(v)."""
+    out, by_dev = [], {}
+    for t in tensors:
+        rows, cols = _view8(t)
+        x = t.detach().to(torch.float32).contiguous()
+        q = torch.empty(rows, cols, dtype=torch.uint8, device=t.device)
+        sc = torch.empty(rows, (cols + 63) // 64, dtype=torch.float32, device=t.device)
+        out.append((q, sc))
+        by_dev.setdefault(t.device, []).append((x, q, sc))
+    for trip in by_dev.values():
+        _convert_moments(*zip(*trip), second_moment, True)
+    return out
+
+
+def dequantize_moments(pairs, second_moment, shapes=None):
+    """[(codes, scales)] -> fp32 moments (``second_moment``: v, the square of what the codes decode to), each reshaped to
+    ``shapes[i]`` where given."""
+    out, by_dev = [], {}
+    for i, (q, sc) in enumerate(pairs):
+        q = q.contiguous()
+        sc = sc.to(torch.float32).contiguous()
+        x = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        out.append(x if shapes is None else x.view(shapes[i]))
+        by_dev.setdefault(q.device, []).append((x, q, sc))
+    for trip in by_dev.values():
+        _convert_moments(*zip(*trip), second_moment, False)
+    return out
+
+
 class AdamW(torch.optim.Optimizer):
     """``torch.optim.AdamW``-compatible (lr, betas, eps, weight_decay); one fused kernel per parameter.
 
@@ -93,12 +158,107 @@ class AdamW(torch.optim.Optimizer):
     that launch left on the device.  ``p.grad`` itself is NOT scaled: that is the one visible difference from
     clip-then-step.  ``grad_norm`` holds the norm before clipping of the last such step as a 0-d device tensor (for
     logging without a synchronisation).  ``max_grad_norm`` is an attribute of the optimizer, not a hyper-parameter of
-    the groups: ``state_dict()`` is what it is without it, and a ``torch.optim.AdamW`` state dict loads."""
+    the groups: ``state_dict()`` is what it is without it, and a ``torch.optim.AdamW`` state dict loads.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
+    ``moments="fp8"``: a parameter with ``dim() >= 2`` and ``numel() >= min_8bit_size`` keeps its two moments as FP8
+    block-scaled codes (include/omh.h: 2.125 bytes per weight instead of 8; state keys ``exp_avg_q``, ``exp_avg_scale``,
+    ``exp_avg_sq_root_q``, ``exp_avg_sq_root_scale``) and is stepped by omh_adamw8_pack_multi; every other parameter, and
+    one whose first gradient is not contiguous, keeps fp32 moments and the launches of ``moments="fp32"``, bit for bit.
+    Both are attributes of the optimizer like ``max_grad_norm``.  ``state_dict(dequantize=True)`` returns fp32
+    ``exp_avg`` / ``exp_avg_sq`` that ``torch.optim.AdamW`` loads; ``load_state_dict`` takes either form into either mode."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 moments="fp32", min_8bit_size=4096):
+        if moments not in ("fp32", "fp8"):
+            raise ValueError(f"AdamW: moments must be 'fp32' or 'fp8', got {moments!r}")
+        if isinstance(min_8bit_size, bool) or not isinstance(min_8bit_size, int) or min_8bit_size < 0:
+            raise ValueError(f"AdamW: min_8bit_size must be a non-negative integer, got {min_8bit_size!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.grad_norm = None
+        self.moments = moments
+        self.min_8bit_size = min_8bit_size
+        # model_train.pending_step_bytes reads the bytes per element the moments of a parameter WILL take (default 8)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if moments == "fp8" and self._eligible8(p):
+                    rows, cols = _view8(p)
+                    p._omh_moment_bytes = (2 * p.numel() + 8 * rows * ((cols + 63) // 64)) / p.numel()
+                else:
+                    p.__dict__.pop("_omh_moment_bytes", None)
+
+    def _eligible8(self, p):
+        return (self.moments == "fp8" and p.dim() >= 2 and p.numel() >= max(1, self.min_8bit_size)
+                and p.dtype == torch.float32 and p.is_contiguous())
+
+    @staticmethod
+    def _zeros8(p):
+        rows, cols = _view8(p)
+        nb = (cols + 63) // 64
+        return {"exp_avg_q": torch.zeros(rows, cols, dtype=torch.uint8, device=p.device),
+                "exp_avg_scale": torch.zeros(rows, nb, dtype=torch.float32, device=p.device),
+                "exp_avg_sq_root_q": torch.zeros(rows, cols, dtype=torch.uint8, device=p.device),
+                "exp_avg_sq_root_scale": torch.zeros(rows, nb, dtype=torch.float32, device=p.device)}
+
+    def _params_by_index(self):
+        """state_dict()'s parameter numbering: position in the concatenation of the groups."""
+        return dict(enumerate(p for group in self.param_groups for p in group["params"]))
+
+    def state_dict(self, dequantize=False):
+        """``dequantize=True``: what ``torch.optim.AdamW`` keeps and loads — 8-bit moments as fp32 ``exp_avg`` /
+        ``exp_avg_sq`` (converted on the device) and ``step`` as a 0-d fp32 tensor."""
+        sd = super().state_dict()
+        if not dequantize:
+            return sd
+        for i, st in sd["state"].items():
+            sd["state"][i] = dict(st, step=torch.tensor(float(st["step"]), dtype=torch.float32))
+        params = self._params_by_index()
+        idx = [i for i, st in sd["state"].items() if "exp_avg_q" in st]
+        if idx:
+            shapes = [params[i].shape for i in idx]
+            m = dequantize_moments([(sd["state"][i]["exp_avg_q"], sd["state"][i]["exp_avg_scale"]) for i in idx], False, shapes)
+            v = dequantize_moments([(sd["state"][i]["exp_avg_sq_root_q"], sd["state"][i]["exp_avg_sq_root_scale"])
+                                    for i in idx], True, shapes)
+            for i, m_, v_ in zip(idx, m, v):
+                st = {k: x for k, x in sd["state"][i].items() if k not in _STATE8}
+                st["exp_avg"], st["exp_avg_sq"] = m_, v_
+                sd["state"][i] = st
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Either layout into either mode.  torch casts every state tensor but ``step`` to the parameter's dtype, so the
+        codes arrive as fp32 holding 0 ... 255 (exactly): they are made uint8 again, then the state of every parameter
+        is converted to what this optimizer's mode keeps for it."""
+        super().load_state_dict(state_dict)
+        to8, to32 = [], []
+        for p, st in self.state.items():
+            if "exp_avg_q" in st:
+                for k in ("exp_avg_q", "exp_avg_sq_root_q"):
+                    st[k] = st[k].to(torch.uint8).contiguous()
+                for k in ("exp_avg_scale", "exp_avg_sq_root_scale"):
+                    st[k] = st[k].to(torch.float32).contiguous()
+                if not self._eligible8(p):
+                    to32.append((p, st))
+            elif "exp_avg" in st and self._eligible8(p) and st["exp_avg"].is_cuda:
+                to8.append((p, st))
+        if to8:
+            m = quantize_moments([st["exp_avg"] for _, st in to8], False)
+            v = quantize_moments([st["exp_avg_sq"] for _, st in to8], True)
+            for (p, st), (mq, ms), (rq, rs) in zip(to8, m, v):
+                del st["exp_avg"], st["exp_avg_sq"]
+                st["exp_avg_q"], st["exp_avg_scale"], st["exp_avg_sq_root_q"], st["exp_avg_sq_root_scale"] = mq, ms, rq, rs
+        if to32:
+            shapes = [p.shape for p, _ in to32]
+            m = dequantize_moments([(st["exp_avg_q"], st["exp_avg_scale"]) for _, st in to32], False, shapes)
+            v = dequantize_moments([(st["exp_avg_sq_root_q"], st["exp_avg_sq_root_scale"]) for _, st in to32], True, shapes)
+            for (p, st), m_, v_ in zip(to32, m, v):
+                for k in _STATE8:
+                    del st[k]
+                st["exp_avg"], st["exp_avg_sq"] = m_, v_
+        for p, st in self.state.items():
+            mo = st.get("exp_avg_q", st.get("exp_avg"))
+            if mo is not None:
+                p._omh_moments_allocated = weakref.ref(mo)
 
     def _global_norm(self, grad_scale):
         """One norm launch over the gradients of every group; returns ({id(p): the gradient the step reads}, coef)."""
@@ -134,6 +294,7 @@ class AdamW(torch.optim.Optimizer):
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             by_step = {}
+            by_step8 = {}                                   # rows with FP8 block-scaled moments: their own launch
             keep = []                                       # keeps .contiguous() copies alive until the launch
             touched = []
             marks = []                                      # (TrainPacks, row): copies this step writes itself
@@ -142,7 +303,11 @@ class AdamW(torch.optim.Optimizer):
                 if p.grad is None:
                     continue
                 st = self.state[p]
-                if not st:
+                if not st and self._eligible8(p) and p.grad.dtype == torch.float32 and p.grad.is_contiguous():
+                    st["step"] = 0
+                    st.update(self._zeros8(p))
+                    p._omh_moments_allocated = weakref.ref(st["exp_avg_q"])
+                elif not st:
                     st["step"] = 0
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
@@ -159,6 +324,18 @@ class AdamW(torch.optim.Optimizer):
                 keep.append(g)
                 touched.append(p)
                 assert p.dtype == torch.float32 and p.is_contiguous() and g.dtype == torch.float32
+                if "exp_avg_q" in st:
+                    rows8, cols8 = _view8(p)
+                    row = (p.data_ptr(), g.data_ptr()) + tuple(st[k].data_ptr() for k in _STATE8)
+                    ent = pack_entry_of(p) if fuse else None
+                    pr = ent[0].rows[ent[1]] if ent is not None else None
+                    if pr is not None and pr[8] == 0 and (pr[3], pr[4]) == (rows8, cols8):
+                        row += (pr[1], pr[2], rows8, cols8, pr[5], pr[6])
+                        marks.append(ent)
+                    else:                                       # a plain weight: no copies (or none this pass can write)
+                        row += (0, 0, rows8, cols8, 0, 0)
+                    by_step8.setdefault((st["step"], p.device), []).append(row)
+                    continue
                 row = (p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
                 ent = pack_entry_of(p) if fuse else None
                 if ent is not None:                             # this weight has bf16 operand copies for the training step
@@ -167,6 +344,23 @@ class AdamW(torch.optim.Optimizer):
                     row = row + (pr[1], pr[2], pr[3], pr[4], pr[5], pr[6], 0 if pr[8] == 0 else 1)
                     marks.append((packs, ri))
                 by_step.setdefault((st["step"], p.device), []).append(row)
+            for (step, dev), rows in by_step8.items():
+                cache = self.__dict__.setdefault("_tables", {})
+                key = (gi, dev, len(rows), "fp8")
+                ent = cache.get(key)
+                if ent is None or ent[0] != rows:               # as below: uploaded again only when an address changed
+                    full, tile0 = [], 0
+                    for r in rows:
+                        full.append(list(r) + [tile0])
+                        tile0 += _tiles8(r[8], r[9])
+                    ent = cache[key] = (rows, torch.tensor(full, dtype=torch.int64).to(dev, non_blocking=False), tile0)
+                with torch.cuda.device(dev):
+                    if coef is not None:
+                        ops.adamw8_pack_multi_dev(ent[1], len(rows), ent[2], group["lr"], b1, b2, group["eps"],
+                                                  group["weight_decay"], step, coef, grad_scale)
+                    else:
+                        ops.adamw8_pack_multi(ent[1], len(rows), ent[2], group["lr"], b1, b2, group["eps"],
+                                              group["weight_decay"], step, grad_scale)
             # one multi-tensor launch per (step count, device): ~750 parameter tensors -> 1 kernel
             for (step, dev), rows in by_step.items():
                 # the pointer table is re-uploaded only when an address changed (never under a graphed step,

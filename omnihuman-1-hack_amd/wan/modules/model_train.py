@@ -1109,7 +1109,7 @@ def activation_bytes(model, rows, batch=1):
 
 def pending_step_bytes(model):
     """Memory the rest of the step will still claim after the forward: AdamW's two moments (8 bytes per trainable
-    parameter, until this package's optimizer has allocated them and said so: ``param._omh_moments_allocated``, ADVICE
+    parameter, 2.125 where an ``optim.AdamW(moments="fp8")`` will keep them as FP8 codes, until this package's optimizer has allocated them and said so: ``param._omh_moments_allocated``, ADVICE
     round 4 — counted again on every later step they made ``auto`` recompute although memory sufficed) and the gradients
     where none exist yet (first step, or ``zero_grad(set_to_none=True)``).  ADVICE round 3: without this the first
     step's free-memory reading is overstated by exactly what the backward and the optimizer step allocate."""
@@ -1118,7 +1118,9 @@ def pending_step_bytes(model):
         if p.requires_grad:
             mref = getattr(p, "_omh_moments_allocated", None)                      # set by optim.AdamW.step
             have_moments = mref is not None and mref() is not None
-            pending += p.numel() * ((0 if have_moments else 8) + (0 if p.grad is not None else 4))
+            # bytes per element the moments will take: 8, or what optim.AdamW(moments="fp8") tagged the parameter with
+            per = 0 if have_moments else getattr(p, "_omh_moment_bytes", 8)
+            pending += int(round(p.numel() * per)) + p.numel() * (0 if p.grad is not None else 4)
     return pending
 
 
