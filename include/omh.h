@@ -705,6 +705,29 @@ int64_t omh_dmd_grad_workspace_bytes(int32_t B, int64_t n);
 int omh_dmd_grad_scale(const float* grad, const double* upstream, float inv_total, int64_t total, float* dx,
                        omh_stream_t stream);
 
+/* Additive to ABI v12 (OMH_ABI_VERSION unchanged, no existing struct or entry changed): rotate the FRAME part of keys that
+ * already carry their rotary position by a further `delta_frames` frames — rotations compose, so a cached key of frame f
+ * becomes the key of frame f + delta_frames.  An unbounded rollout keeps its attention sink at a fixed rotary distance
+ * behind the window this way (causal.RollingKVCache(pin_sink=True)).
+ * src, dst: bf16 [B, rows, dim], rows contiguous (row pitch = dim), batch entry b at element b * src_batch_stride /
+ * b * dst_batch_stride (dst is typically a row range of a cache whose batch stride is cap * dim).  A head is head_dim
+ * consecutive columns; its rotary pairs are the consecutive (even, odd) channels, and the frame part is the pairs
+ * j < nf = (head_dim - 4 (head_dim / 6)) / 2 (22 of 64 at head_dim = 128), as in the forward's norm + RoPE kernels.  For these
+ *   (y0, y1) = (x0 cos a_j - x1 sin a_j,  x0 sin a_j + x1 cos a_j),   a_j = delta_frames * theta^(-2j / (2 nf));
+ * a_j, cos a_j and sin a_j are formed on the host in fp64 and rounded once to fp32 (never an fp32 product delta * freq),
+ * the multiply-adds run in fp32 and each result is rounded once to bf16, to nearest even.  Every other column of dst
+ * receives the bits of src, and so does a pair whose (cos, sin) is exactly (1, 0): delta_frames = 0 copies src bit for
+ * bit.  dst may BE src (the same pointer and batch stride); otherwise the two may not overlap.  Any rows >= 1; nothing
+ * outside [rows, dim] of each batch entry is read or written.  16-byte vector loads and stores only; the table travels in
+ * the kernel arguments (one launch on `stream`, no allocation, no copy, nothing read back).
+ * OMH_E_BADARG: a null pointer, B, rows, dim, head_dim < 1, theta <= 0, a batch stride below rows * dim, overlapping
+ * src / dst that are not the same rows; OMH_E_SHAPE: dim % 128, head_dim % 8 or dim % head_dim != 0, nf >
+ * OMH_ROPE_SHIFT_MAX_PAIRS, B > 65535; OMH_E_ALIGN: a pointer not 16-byte aligned or a batch stride % 8 != 0. */
+#define OMH_ROPE_SHIFT_MAX_PAIRS 64
+int omh_rope_shift_frames(const void* src, void* dst, int32_t B, int64_t rows, int32_t dim, int64_t src_batch_stride,
+                          int64_t dst_batch_stride, int64_t delta_frames, int32_t head_dim, double theta,
+                          omh_stream_t stream);
+
 /* ----------------------------------------------------------------------
  * ABI v11.  Measurement, not product: TFLOP/s this GPU sustains on back-to-back
  * v_mfma_f32_32x32x16_bf16 with one wave per SIMD and no memory traffic

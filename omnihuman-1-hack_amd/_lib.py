@@ -330,6 +330,7 @@ _SIGS = {
     "omh_dmd_grad": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i64, vp, vp, vp, vp, vp]),
     "omh_dmd_grad_workspace_bytes": (i64, [i32, i64]),
     "omh_dmd_grad_scale": (i32, [vp, vp, f32, i64, vp, vp]),
+    "omh_rope_shift_frames": (i32, [vp, vp, i32, i64, i32, i64, i64, i64, i32, C.c_double, vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

@@ -18,7 +18,9 @@ says which key groups a query group sees.  ``IntervalMask`` holds such a matrix 
 ``IntervalMask(..., runs=3)`` is the three-run form (``omh_interval3_mask``): teacher forcing with an attention sink.
 
 An attention sink plus a window (``WanModel.set_causal_chunks(fpc, W, S)``) rolls out on a ``RollingKVCache``: S sink slots
-and a ring of W + 1, so the cache's size does not depend on the clip's length.
+and a ring of W + 1, so the cache's size does not depend on the clip's length.  ``RollingKVCache(pin_sink=True)`` also
+keeps the sink at a fixed rotary distance behind the window (include/omh.h, ``omh_rope_shift_frames``), and ``sample`` /
+``stream`` take their noise chunk by chunk: a rollout without an end.
 
 Self forcing trains the student on its own rollouts: ``self_forcing_rollout`` returns clips attached to a graph,
 ``dmd_loss`` puts the distribution-matching objective on them (a frozen teacher and a trainable critic score the noised
@@ -26,6 +28,7 @@ clips; include/omh.h, ``omh_dmd_grad``), ``critic_loss`` is the critic's own flo
 clips and ``dmd_sigmas`` draws the noise levels of both.
 """
 import ctypes
+import itertools
 
 import torch
 
@@ -316,16 +319,31 @@ class RollingKVCache:
     number of commits the resident chunks are the sink and the last W + 1.
 
     ``length`` counts the tokens committed since ``reset()`` and does not stop at the capacity.  ``truncate`` reaches
-    back to the start of the last committed chunk only: what lay before it may be evicted already."""
+    back to the start of the last committed chunk only: what lay before it may be evicted already.
+
+    ``pin_sink=True`` (needs S > 0: ValueError otherwise): the sink keeps a fixed rotary distance to the window however
+    long the rollout runs.  Cached keys carry the rotary position of their frame; for the window that is harmless (RoPE is
+    relative), but the sink of chunk I would sit I chunks behind the queries.  Pinned, the key rows of a sink chunk are
+    copied as they are committed into ``sink_k[l]`` (bf16 [batch, S chunk_tokens, dim], the pristine copy), and the live
+    rows ``k[l][:, :S chunk_tokens]`` are ``ops.rope_shift_frames(sink_k[l], None, sink_delta)`` — always derived from the
+    pristine bits, never from rows that were rotated before: a key is rounded once more and no more.  Chunk I needs
+    ``sink_shift_chunks(I)`` = max(S, I - W) - S chunks, times the frames of a chunk: 0 until the ring has wrapped,
+    afterwards the sink ends where the window's first chunk begins.  ``WanModel.forward_chunk`` calls ``pin()`` before
+    its blocks run; ``sink_delta`` is the shift in frames the live rows hold, ``sink_rows`` the pristine rows that are valid
+    (a cut into a sink chunk invalidates the rows behind it until they are committed again).  V has no rotary position
+    and stays as it is."""
     rolling = True
 
-    def __init__(self, model, batch, chunk_tokens, sink_chunks, left_chunks, device):
+    def __init__(self, model, batch, chunk_tokens, sink_chunks, left_chunks, device, pin_sink=False):
         batch, Ct, S, W = int(batch), int(chunk_tokens), int(sink_chunks), int(left_chunks)
         if batch < 1 or Ct < 1:
             raise ValueError(f"RollingKVCache: batch = {batch} and chunk_tokens = {Ct} must be positive")
         if S < 0 or W < 0:
             raise ValueError(f"RollingKVCache: sink_chunks = {S} >= 0 and left_chunks = {W} >= 0 expected (an unbounded "
                              f"look-back never evicts: use KVCache)")
+        self.pin_sink = bool(pin_sink)
+        if self.pin_sink and S < 1:
+            raise ValueError("RollingKVCache: pin_sink=True needs sink_chunks > 0 (there is no sink to pin)")
         self.model_id = id(model)
         self.batch, self.dim = batch, int(model.dim)
         self.chunk_tokens, self.sink_chunks, self.left_chunks = Ct, S, W
@@ -339,6 +357,37 @@ class RollingKVCache:
         self._vt_store = [torch.zeros(batch * self.dim * self.pitch + 64, dtype=torch.bfloat16, device=device)
                           for _ in range(n)]
         self.vt = [s[:batch * self.dim * self.pitch].view(batch, self.dim, self.pitch) for s in self._vt_store]
+        self.sink_delta = 0                                # frames the live sink rows are rotated past their own position
+        self.sink_rows = 0                                 # pristine rows [0, sink_rows) are the committed ones
+        self.sink_k = [torch.zeros(batch, S * Ct, self.dim, dtype=torch.bfloat16, device=device) for _ in range(n)] \
+            if self.pin_sink else None
+
+    def sink_shift_chunks(self, chunk):
+        """How many chunks the sink is moved up for chunk ``chunk`` of the clip: max(S, chunk - W) - S."""
+        return max(self.sink_chunks, int(chunk) - self.left_chunks) - self.sink_chunks
+
+    def pin(self, frames_per_chunk, head_dim, theta=10000.0):
+        """Bring the live sink rows of every layer to the shift the chunk ``length`` stands in needs — one
+        ``ops.rope_shift_frames`` launch per layer from the pristine copy, and nothing when they hold it already.
+        ValueError when the shift is due before every sink row is committed.  Without ``pin_sink`` it does nothing."""
+        if not self.pin_sink:
+            return
+        due = self.sink_shift_chunks(self.length // self.chunk_tokens) * int(frames_per_chunk)
+        if due == self.sink_delta:
+            return
+        n = self.sink_chunks * self.chunk_tokens
+        if self.sink_rows < n:
+            raise ValueError(f"RollingKVCache.pin: only {self.sink_rows} of {n} sink rows are committed; a short sink chunk "
+                             f"cannot be moved")
+        shift = self._shift
+        if shift is None:
+            from . import ops
+            shift = ops.rope_shift_frames
+        for pristine, live in zip(self.sink_k, self.k):
+            shift(pristine, live[:, :n], due, head_dim, theta)
+        self.sink_delta = due
+
+    _shift = None                                          # (tests put a CPU statement of ops.rope_shift_frames here)
 
     def slot(self, chunk):
         """The slot chunk ``chunk`` of the clip lives in."""
@@ -361,6 +410,12 @@ class RollingKVCache:
         self.check_room(n_tokens)
         if n_tokens > 0:
             self._floor = self.length - self.length % self.chunk_tokens
+            if self.pin_sink and self.length < self.sink_chunks * self.chunk_tokens:
+                # a sink chunk (its slot is its place, and the shift is 0 until the ring wraps): keep the rows as committed
+                rows = slice(self.length, self.length + int(n_tokens))
+                for pristine, live in zip(self.sink_k, self.k):
+                    pristine[:, rows].copy_(live[:, rows])
+                self.sink_rows = rows.stop
         self.length += int(n_tokens)
 
     def truncate(self, n_tokens):
@@ -371,14 +426,16 @@ class RollingKVCache:
             raise ValueError(f"RollingKVCache.truncate({n_tokens}): only [{self._floor}, {self.length}], the last committed "
                              f"chunk, can be cut")
         self.length = n_tokens
+        self.sink_rows = min(self.sink_rows, n_tokens)
 
     def reset(self):
-        self.length = self._floor = 0
+        # (the live sink rows are scratch again: the sink chunks rewrite them at their own positions, shift 0)
+        self.length = self._floor = self.sink_rows = self.sink_delta = 0
 
 
 @torch.no_grad()
 def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks=-1, make_scheduler, guide_scale,
-           context_t=0.0, sink_chunks=0, rolling=False, caches=None, extra_conditions=None):
+           context_t=0.0, sink_chunks=0, rolling=False, caches=None, extra_conditions=None, pin_sink=False):
     """Denoise one clip chunk by chunk.  ``noise``: the initial latents [C, F, H, W] of the clip; ``context`` /
     ``context_null``: what ``WanModel.forward`` takes for a batch of one (a list with one [L, text_dim] tensor, or a
     ``ContextState``).  For every group of ``frames_per_chunk`` latent frames (the last one may be shorter):
@@ -393,6 +450,13 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
     first ``sink_chunks`` chunks of the clip as well.  ``rolling=True`` (needs ``left_chunks`` >= 0; implied by a sink):
     two ``RollingKVCache``s in place of the two ``KVCache``s — cache memory then does not depend on the clip's length.
     ``caches``: a pair (conditional, unconditional) of caches of batch 1 to use in place of fresh ones (they are reset).
+    ``pin_sink=True`` (needs ``sink_chunks`` > 0, implies the rolling caches; caches passed in must have been built with
+    the same value): ``RollingKVCache(pin_sink=True)`` — once the ring has wrapped the sink keys are re-rotated to sit
+    directly behind the window, so that a chunk's result does not depend on how far into the clip it lies; the chunks up
+    to ``sink_chunks + left_chunks`` keep the bits of the unpinned rollout.
+    ``noise`` may also be an iterable that yields the noise one chunk [C, f <= fpc, H, W] at a time — a rollout whose length
+    nobody knows up front (a shorter item must be the last; the iterable is read one chunk ahead).  That form needs
+    rolling caches (ValueError otherwise, before anything runs) and gives the bits of the concatenated tensor.
     ``extra_conditions``: condition tokens as ``WanModel.forward`` takes them, for the conditional branch only (``context``
     is then the raw text, no ``ContextState``).  With ``"frames"`` and ``"window"`` every ``forward_chunk`` call — denoising
     and commit passes alike — keeps only the tokens of the frames from the chunk's first frame - back to its last frame
@@ -400,7 +464,8 @@ def sample(model, noise, context, context_null, *, frames_per_chunk, left_chunks
     The model's own
     ``set_causal_chunks`` setting is restored on the way out.  Returns the latents of the whole clip, fp32 [C, F, H, W]
     — the chunks of ``stream`` with the same arguments, concatenated."""
-    geom = _rollout_geometry("sample", noise, frames_per_chunk, left_chunks, sink_chunks, rolling)
+    caches = None if caches is None else tuple(caches)
+    geom = _rollout_geometry("sample", noise, frames_per_chunk, left_chunks, sink_chunks, rolling, pin_sink, caches)
     chunks = _rollout(model, noise, context, context_null, geom, make_scheduler, guide_scale, context_t, rolling, caches,
                       extra_conditions, who="sample")
     return torch.cat([c.latents for c in chunks], dim=1)
@@ -426,11 +491,11 @@ class StreamChunk:
         return self
 
 
-def _rollout_geometry(who, noise, frames_per_chunk, left_chunks, sink_chunks, rolling):
+def _rollout_geometry(who, noise, frames_per_chunk, left_chunks, sink_chunks, rolling, pin_sink=False, caches=None):
     """The argument rules ``sample`` and ``stream`` share (nothing touches a device).  Returns (fpc, left_chunks,
-    sink_chunks) as the model is set up with them."""
+    sink_chunks, pin_sink) as the model and the caches are set up with them."""
     fpc = int(frames_per_chunk)
-    if noise.dim() != 4:
+    if isinstance(noise, torch.Tensor) and noise.dim() != 4:
         raise ValueError(f"{who}: noise [C, F, H, W] of one clip expected, got {tuple(noise.shape)}")
     left_chunks, sink_chunks = int(left_chunks), int(sink_chunks)
     if rolling and left_chunks < 0:
@@ -439,7 +504,50 @@ def _rollout_geometry(who, noise, frames_per_chunk, left_chunks, sink_chunks, ro
         raise ValueError(f"{who}: sink_chunks = {sink_chunks} >= 0 expected")
     if left_chunks < 0:
         sink_chunks = 0
-    return fpc, left_chunks, sink_chunks
+    if pin_sink and sink_chunks < 1:
+        raise ValueError(f"{who}: pin_sink=True needs sink_chunks > 0 and left_chunks >= 0 (there is no sink to pin)")
+    if caches is not None:
+        caches = tuple(caches)
+        if len(caches) != 2:
+            raise ValueError(f"{who}: caches = (conditional, unconditional) expected")
+        if any(bool(getattr(c, "pin_sink", False)) != bool(pin_sink) for c in caches):
+            raise ValueError(f"{who}: pin_sink = {bool(pin_sink)}, but the caches were built with "
+                             f"pin_sink = {[bool(getattr(c, 'pin_sink', False)) for c in caches]}")
+    if not isinstance(noise, torch.Tensor):
+        if not hasattr(noise, "__iter__"):
+            raise ValueError(f"{who}: noise is a tensor [C, F, H, W] or an iterable of chunks [C, f, H, W]")
+        ring = all(getattr(c, "rolling", False) for c in caches) if caches is not None else (rolling or sink_chunks > 0)
+        if not ring:
+            raise ValueError(f"{who}: noise given chunk by chunk has no length to size a KVCache with; it needs rolling "
+                             f"caches (rolling=True with left_chunks >= 0, or a sink)")
+    return fpc, left_chunks, sink_chunks, bool(pin_sink)
+
+
+def _noise_chunks(who, noise, fpc):
+    """(first frame, noise of the chunk, is it the last) per chunk, from a clip [C, F, H, W] or from an iterable of
+    chunks [C, f <= fpc, H, W] of one C, H, W and device — read one chunk ahead, so that the last one is known as such;
+    an item shorter than ``fpc`` must be the last (ValueError)."""
+    if isinstance(noise, torch.Tensor):
+        F = noise.shape[1]
+        for f0 in range(0, F, fpc):
+            yield f0, noise[:, f0:f0 + fpc], f0 + fpc >= F
+        return
+    f0, cur, shape = 0, None, None
+    for item in noise:
+        if not isinstance(item, torch.Tensor) or item.dim() != 4 or not 1 <= item.shape[1] <= fpc:
+            raise ValueError(f"{who}: every item of noise is a chunk [C, f, H, W] with 1 <= f <= {fpc} frames")
+        key = (item.shape[0], item.shape[2], item.shape[3], item.device)
+        if shape is not None and key != shape:
+            raise ValueError(f"{who}: the chunks of noise must share C, H, W and the device")
+        shape = key
+        if cur is not None:
+            if cur.shape[1] < fpc:
+                raise ValueError(f"{who}: a chunk of {cur.shape[1]} < {fpc} frames must be the last item of noise")
+            yield f0, cur, False
+            f0 += cur.shape[1]
+        cur = item
+    if cur is not None:
+        yield f0, cur, True
 
 
 @torch.no_grad()
@@ -448,11 +556,14 @@ def _rollout(model, noise, context, context_null, geom, make_scheduler, guide_sc
     """The one statement of the chunk-by-chunk rollout: a generator of ``StreamChunk``s (``sample`` concatenates their
     latents, ``stream`` hands them out).  ``decoder``: a ``DecodeStream`` every finished chunk is pushed into; ``overlap``:
     on a side stream of this generator's, see ``stream``; ``events``: record ``ready``."""
-    fpc, left_chunks, sink_chunks = geom
-    F = noise.shape[1]
-    dev = noise.device
+    fpc, left_chunks, sink_chunks, pin_sink = geom
+    source = _noise_chunks(who, noise, fpc)
+    head = next(source, None)                              # (an iterable: its first chunk gives the geometry and the device)
+    if head is None:
+        return
+    first = noise if isinstance(noise, torch.Tensor) else head[1]
+    dev = first.device
     pt, ph, pw = model.patch_size
-    tokens = (F // pt) * (noise.shape[2] // ph) * (noise.shape[3] // pw)
     prev = getattr(model, "_causal_chunks", None)
     model.set_causal_chunks(fpc, left_chunks, sink_chunks)
     try:
@@ -463,15 +574,16 @@ def _rollout(model, noise, context, context_null, geom, make_scheduler, guide_sc
             for c in caches:
                 c.reset()
         elif rolling or sink_chunks > 0:
-            Ct = fpc * (noise.shape[2] // ph) * (noise.shape[3] // pw)
-            caches = tuple(RollingKVCache(model, 1, Ct, sink_chunks, left_chunks, dev) for _ in range(2))
+            Ct = fpc * (first.shape[2] // ph) * (first.shape[3] // pw)
+            caches = tuple(RollingKVCache(model, 1, Ct, sink_chunks, left_chunks, dev, pin_sink=pin_sink) for _ in range(2))
         else:
+            tokens = (first.shape[1] // pt) * (first.shape[2] // ph) * (first.shape[3] // pw)
             caches = (KVCache(model, 1, tokens, dev), KVCache(model, 1, tokens, dev))
         t_ctx = torch.full((1,), float(context_t), device=dev)
         side = torch.cuda.Stream(dev) if (overlap and decoder is not None) else None
         held = None
-        for index, f0 in enumerate(range(0, F, fpc)):
-            lat = noise[:, f0:f0 + fpc].float().contiguous()
+        for index, (f0, chunk_noise, last) in enumerate(itertools.chain((head,), source)):
+            lat = chunk_noise.float().contiguous()
             scheduler = make_scheduler()
             for t in scheduler.timesteps:
                 tt = torch.stack([t])
@@ -498,7 +610,6 @@ def _rollout(model, noise, context, context_null, geom, make_scheduler, guide_sc
                 if events:
                     chunk.ready = torch.cuda.Event()
                     chunk.ready.record(torch.cuda.current_stream(dev))
-            last = f0 + fpc >= F
             if side is None or last:
                 yield chunk
             else:
@@ -512,7 +623,7 @@ def _rollout(model, noise, context, context_null, geom, make_scheduler, guide_sc
 
 def stream(model, noise, context, context_null, *, frames_per_chunk, left_chunks=-1, make_scheduler, guide_scale,
            context_t=0.0, sink_chunks=0, rolling=False, caches=None, extra_conditions=None, vae=None, output="float",
-           overlap=False):
+           overlap=False, pin_sink=False):
     """``sample`` as a generator: one ``StreamChunk`` per chunk, as soon as the chunk is denoised — ``sample(...)`` equals
     ``torch.cat([c.latents for c in stream(...)], 1)`` bit for bit.  ``vae``: a ``WanVAE``; every chunk is pushed into one
     ``vae.decode_stream(output)`` and ``chunk.video`` holds the pixel frames it completes (``output`` = "float": fp32
@@ -528,8 +639,10 @@ def stream(model, noise, context, context_null, *, frames_per_chunk, left_chunks
 
     While the generator is suspended the model stays under this rollout's ``set_causal_chunks`` setting; it is restored
     when the generator finishes or is closed.  The arguments are checked here, before the first chunk is asked for
-    (ValueError, as ``sample``)."""
-    geom = _rollout_geometry("stream", noise, frames_per_chunk, left_chunks, sink_chunks, rolling)
+    (ValueError, as ``sample``).  ``pin_sink`` and ``noise`` as an iterable of chunks: as in ``sample`` — together an
+    open-ended stream, whose frame positions may pass the model's rotary table."""
+    caches = None if caches is None else tuple(caches)
+    geom = _rollout_geometry("stream", noise, frames_per_chunk, left_chunks, sink_chunks, rolling, pin_sink, caches)
     if output not in ("float", "uint8"):
         raise ValueError(f"stream: output = {output!r}, 'float' or 'uint8' expected")
     decoder = vae.decode_stream(output) if vae is not None else None

@@ -14,7 +14,7 @@ from ._lib import (ATTN_ALLOW_SPLIT, ATTN_SHORT_KERNEL, BIAS_M, BIAS_N, BIAS_NON
                    EPI_GELU_BWD_BF16, EPI_GELU_ERF_BF16, EPI_RESID, AttnArgs, GemmArgs, OmhError, check, lib)
 
 __all__ = ["gemm", "flash_attn", "flash_attn_func", "layernorm_modulate", "rmsnorm_rope", "cast_bf16", "patchify", "unpatchify",
-           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "flow_noise", "dmd_grad", "dmd_loss", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw", "cl_to_u8",
+           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "flow_noise", "dmd_grad", "dmd_loss", "rope_shift_frames", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw", "cl_to_u8",
            "softmax_rows", "OmhError",
            "EPI_BF16", "EPI_F32", "EPI_GELU_BF16", "EPI_GELU_ERF_BF16", "EPI_RESID", "EPI_F32_ACCUM", "BIAS_NONE", "BIAS_N", "BIAS_M"]
 
@@ -775,6 +775,27 @@ def dmd_loss(x, x_t, v_cond, v_uncond, v_fake, sigma, guide):
     if torch.is_grad_enabled() and x.requires_grad:
         return _DmdLossFunc.apply(x, *args, float(guide))
     return dmd_grad(x.detach(), *args, guide)[2].view(())
+
+
+def rope_shift_frames(src, dst, delta_frames, head_dim=128, theta=10000.0):
+    """Rotate the frame part of keys that already carry their rotary position by ``delta_frames`` more frames
+    (omh_rope_shift_frames): ``src`` bf16 [B, rows, dim] -> ``dst`` of the same shape (None: a fresh tensor; ``src`` itself:
+    in place).  Both may be row ranges of larger tensors — each has its own batch stride — with contiguous rows of ``dim``
+    elements, dim % 128 == 0.  Only the frame pairs of every head change ((head_dim - 4 (head_dim // 6)) / 2 of them, the
+    angles formed in fp64); every other column of ``dst`` gets the bits of ``src``, and ``delta_frames`` = 0 copies.
+    Returns ``dst``."""
+    if dst is None:
+        dst = torch.empty(src.shape, dtype=src.dtype, device=src.device)
+    _dev(src, dst)
+    assert src.dtype == torch.bfloat16 and dst.dtype == torch.bfloat16 and src.dim() == 3 and dst.shape == src.shape, \
+        "rope_shift_frames: bf16 [B, rows, dim] tensors of one shape are expected"
+    B, rows, dim = src.shape
+    for t in (src, dst):
+        assert t.stride(2) == 1 and t.stride(1) == dim, "rope_shift_frames: contiguous rows of dim elements are expected"
+    check(lib.omh_rope_shift_frames(_p(src), _p(dst), B, rows, dim, src.stride(0) if B > 1 else rows * dim,
+                                    dst.stride(0) if B > 1 else rows * dim, int(delta_frames), int(head_dim), float(theta),
+                                    _stream()), "omh_rope_shift_frames")
+    return dst
 
 
 def conv_pair_supported(Tin, Hin, Win, Cin2, Tout, Hout, Wout, Cout, KT, KH, KW, stride_t=1, stride_hw=1, pad_h=0, pad_w=0,

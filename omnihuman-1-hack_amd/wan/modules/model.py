@@ -510,7 +510,8 @@ class WanSelfAttention(nn.Module):
         otherwise, so on an empty cache the result has its bits.
         A ``causal.RollingKVCache``: the chunk's rows go to ``fc.cache_pos`` (its slot) and the keys are [0, fc.cache_hi) —
         every filled slot; softmax attention does not depend on the order of its keys, and they carry absolute rotary
-        positions.  ``fc.cache_mask`` (a short last chunk in a wrapped ring): the interval kernel skips the stale keys
+        positions (a cache with ``pin_sink`` has moved its sink rows behind the window before the blocks run:
+        ``RollingKVCache.pin``).  ``fc.cache_mask`` (a short last chunk in a wrapped ring): the interval kernel skips the stale keys
         behind the chunk in its slot.
         ``extras`` (forward_chunk(grad=True), model_train.py): ``lse`` and ``o32`` are asked for on top (the choice of the
         kernel does not depend on them), and the chunk's own k rows and V (row-major, what the backward reads) are copied
@@ -1116,27 +1117,38 @@ class WanModel(nn.Module):
                                        Lk=cache.cap, device=device)
         return masks[key]
 
-    def _rope_shifted(self, device, frame_offset):
-        """The cos / sin tables with the FRAME columns moved up by ``frame_offset`` rows: frame f of a chunk then rotates
-        like frame frame_offset + f of the clip; the h / w columns stay.  Cached per offset."""
+    def _rope_shifted(self, device, frame_offset, frames):
+        """The cos / sin tables with the FRAME columns moved up by ``frame_offset`` rows: frame f < ``frames`` of a chunk
+        then rotates like frame frame_offset + f of the clip; the h / w columns stay.  While the chunk ends inside the
+        table its rows are slices of it; past the table (an unbounded rollout) the frame angles of rows [frame_offset,
+        frame_offset + frames) are computed in fp64 by ``rope_params``' formula — the same fp32 cos / sin a longer table
+        would hold.  The few most recent offsets are kept (a rollout asks for a new one every chunk)."""
         cos, sin = self._rope(device)
         if frame_offset == 0:
             return cos, sin
-        key = (str(device), int(frame_offset))
+        inside = frame_offset + frames <= cos.shape[0]
+        key = (str(device), int(frame_offset)) + (() if inside else (int(frames),))
         tabs = getattr(self, "_rope_shift_cache", None)
         if tabs is None or tabs[0] is not cos:
             tabs = self._rope_shift_cache = (cos, {})
-        hit = tabs[1].get(key)
+        hit = tabs[1].pop(key, None)
         if hit is None:
-            if len(tabs[1]) > 256:
-                tabs[1].clear()
             d = self.dim // self.num_heads
             nf = (d - 4 * (d // 6)) // 2                                     # pair-columns of the frame axis
             c2, s2 = cos.clone(), sin.clone()
-            n = cos.shape[0] - frame_offset
-            c2[:n, :nf] = cos[frame_offset:, :nf]
-            s2[:n, :nf] = sin[frame_offset:, :nf]
-            hit = tabs[1][key] = (c2, s2)
+            if inside:
+                n = cos.shape[0] - frame_offset
+                c2[:n, :nf] = cos[frame_offset:, :nf]
+                s2[:n, :nf] = sin[frame_offset:, :nf]
+            else:
+                inv = 1.0 / torch.pow(10000, torch.arange(0, 2 * nf, 2).to(torch.float64).div(2 * nf))
+                ang = torch.outer(torch.arange(frame_offset, frame_offset + frames), inv)     # fp64, as rope_params
+                c2[:frames, :nf] = torch.cos(ang).to(torch.float32).to(device)
+                s2[:frames, :nf] = torch.sin(ang).to(torch.float32).to(device)
+            hit = (c2, s2)
+        tabs[1][key] = hit                                                   # (re-inserted: the newest entry)
+        while len(tabs[1]) > 4:
+            tabs[1].pop(next(iter(tabs[1])))
         return hit
 
     def _rope_repeated(self, device, frames):
@@ -1239,7 +1251,10 @@ class WanModel(nn.Module):
         ``frames_per_chunk``).  With a ``causal.RollingKVCache`` (its geometry must equal the model's (fpc h w, W, S):
         ValueError otherwise) k and V^T go to the chunk's slot and attention runs over every filled slot — the sink, the
         window and the chunk itself, one contiguous key range; a plain ``KVCache`` under ``sink_chunks`` > 0 is a
-        ValueError.  ``commit=True`` advances ``cache.length`` by C once, after the last block;
+        ValueError.  A ``RollingKVCache(pin_sink=True)`` first brings its sink keys to the rotary distance this chunk needs
+        (``RollingKVCache.pin``: at most one ``ops.rope_shift_frames`` launch per layer when the shift changes; denoising and
+        commit passes alike).  ``frame_offset`` may be any value >= 0: past the model's rotary table (1 024 frames) the
+        frame angles are computed in fp64 by the table's formula.  ``commit=True`` advances ``cache.length`` by C once, after the last block;
         ``commit=False`` leaves the cache as it was (the rows behind ``length`` are scratch) — a denoising step of the
         current chunk.  Cross-attention, FFN and head as in ``forward``.  Tokens per chunk must be a multiple of 8 (the
         16-byte stores into the cache and the look-back offset): ValueError otherwise, and when the chunk does not fit.
@@ -1254,7 +1269,8 @@ class WanModel(nn.Module):
         RuntimeError when the cache was ``reset()`` or ``truncate()``d below them in between.  Activations are always
         kept (a re-run would need the cache as it was): ``use_checkpoint`` is ignored and ``checkpoint_policy="always"``
         is a ValueError, as are a ``RollingKVCache`` (its slots are evicted before the backward runs: use ``KVCache``
-        with ``left_chunks``), hence ``sink_chunks`` > 0, and a 2-D ``t``.  Without anything that requires grad it is the
+        with ``left_chunks``; with ``pin_sink`` its sink rows are re-rotated as well), hence ``sink_chunks`` > 0, and a
+        2-D ``t``.  Without anything that requires grad it is the
         inference call.
 
         ``extra_conditions``: as in ``forward``.  With ``"frames"`` the frames are clip-absolute, the chunk's queries are
@@ -1269,6 +1285,10 @@ class WanModel(nn.Module):
             extra_conditions = self._normal_conditions(extra_conditions, chunk=(fo, f))
         if grad:
             # (the refusals come before anything touches a device)
+            if getattr(cache, "pin_sink", False):
+                raise ValueError("forward_chunk(grad=True): a cache with pin_sink=True re-rotates its sink rows for later "
+                                 "chunks, and the backward reads cached rows in place; training under a pinned sink is "
+                                 "not provided")
             if getattr(cache, "rolling", False):
                 raise ValueError("forward_chunk(grad=True): a RollingKVCache evicts slots the backward still reads; use a "
                                  "causal.KVCache with set_causal_chunks(frames_per_chunk, left_chunks)")
@@ -1337,15 +1357,16 @@ class WanModel(nn.Module):
                 raise ValueError(f"forward_chunk: cache.length = {L0} is no multiple of {tpf} tokens per frame; pass frame_offset")
             frame_offset = L0 // tpf
         frame_offset = int(frame_offset)
-        if frame_offset < 0 or frame_offset + f > self.freqs.shape[0]:
-            raise ValueError(f"forward_chunk: frames [{frame_offset}, {frame_offset + f}) leave the rotary table "
-                             f"({self.freqs.shape[0]} frames)")
+        if frame_offset < 0 or f > self.freqs.shape[0]:
+            raise ValueError(f"forward_chunk: frame_offset = {frame_offset} >= 0 and at most {self.freqs.shape[0]} frames per "
+                             f"chunk expected (frames past the rotary table get their angles computed: _rope_shifted)")
         return C, lo, frame_offset
 
-    def _chunk_ctx(self, fc, cache, lo, frame_offset):
-        """An embedded context as that of one chunk against ``cache`` from key ``lo`` on, at ``frame_offset``."""
+    def _chunk_ctx(self, fc, cache, lo, frame_offset, frames):
+        """An embedded context as that of one chunk of ``frames`` frames against ``cache`` from key ``lo`` on, at
+        ``frame_offset``."""
         fc.chunk = fc.interval = None                      # the cache IS the causal structure: plain attention over it
-        fc.rope_cos, fc.rope_sin = self._rope_shifted(fc.e0.device, frame_offset)
+        fc.rope_cos, fc.rope_sin = self._rope_shifted(fc.e0.device, frame_offset, frames)
         fc.cache, fc.cache_lo = cache, lo
         fc.cache_pos = fc.cache_hi = fc.cache_mask = None
 
@@ -1358,8 +1379,9 @@ class WanModel(nn.Module):
             Ct = self._causal_chunks[0] * tpf
         xs, e, fc, grids, lens, ctx_lens = self._embed(x, t, context, C, clip_fea, y, extra_conditions,
                                                        chunk=(frame_offset, C // self._tokens_per_frame(x)))
-        self._chunk_ctx(fc, cache, lo, frame_offset)
+        self._chunk_ctx(fc, cache, lo, frame_offset, C // self._tokens_per_frame(x))
         if rolling:
+            cache.pin(self._causal_chunks[0], self.dim // self.num_heads)   # (a pinned sink: its rows where this chunk needs them)
             # the chunk's slot; the keys are every filled slot.  Before the ring wraps they are [0, L0 + C), KVCache's range;
             # afterwards all slots — one contiguous range, whatever chunk sits where
             fc.cache_pos = cache.slot(L0 // Ct) * Ct

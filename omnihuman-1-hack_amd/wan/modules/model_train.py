@@ -1648,7 +1648,7 @@ def forward_chunk_train(model, x, t, context, cache, frame_offset, commit, clip_
     st.operands = _operands(model, st.packs)
     model.__dict__.setdefault("_omh_live_states", weakref.WeakSet()).add(st)
 
-    st.after_embed = lambda fc: model._chunk_ctx(fc, cache, lo, frame_offset)
+    st.after_embed = lambda fc: model._chunk_ctx(fc, cache, lo, frame_offset, C // model._tokens_per_frame(x))
     st.chunk = (frame_offset, C // model._tokens_per_frame(x))
     tok = extra_conditions.get("tokens") if isinstance(extra_conditions, dict) else extra_conditions
     if isinstance(extra_conditions, dict) and extra_conditions.get("_normal"):
