@@ -715,7 +715,8 @@ int omh_dmd_grad_scale(const float* grad, const double* upstream, float inv_tota
  * j < nf = (head_dim - 4 (head_dim / 6)) / 2 (22 of 64 at head_dim = 128), as in the forward's norm + RoPE kernels.  For these
  *   (y0, y1) = (x0 cos a_j - x1 sin a_j,  x0 sin a_j + x1 cos a_j),   a_j = delta_frames * theta^(-2j / (2 nf));
  * a_j, cos a_j and sin a_j are formed on the host in fp64 and rounded once to fp32 (never an fp32 product delta * freq),
- * the multiply-adds run in fp32 and each result is rounded once to bf16, to nearest even.  Every other column of dst
+ * the multiply-adds run in fp32 — y0 = fma(x0, cos, -(x1 sin)), y1 = fma(x0, sin, x1 cos), the x1 product rounded to fp32 —
+ * and each result is rounded once to bf16, to nearest even.  Every other column of dst
  * receives the bits of src, and so does a pair whose (cos, sin) is exactly (1, 0): delta_frames = 0 copies src bit for
  * bit.  dst may BE src (the same pointer and batch stride); otherwise the two may not overlap.  Any rows >= 1; nothing
  * outside [rows, dim] of each batch entry is read or written.  16-byte vector loads and stores only; the table travels in
@@ -727,6 +728,45 @@ int omh_dmd_grad_scale(const float* grad, const double* upstream, float inv_tota
 int omh_rope_shift_frames(const void* src, void* dst, int32_t B, int64_t rows, int32_t dim, int64_t src_batch_stride,
                           int64_t dst_batch_stride, int64_t delta_frames, int32_t head_dim, double theta,
                           omh_stream_t stream);
+
+/* Additive to ABI v12: the OMH_ROPE_SHIFT_MAX_PAIRS (cos, sin) pairs of one delta, cs[2 j] = cos a_j, cs[2 j + 1] = sin a_j
+ * — the numbers omh_rope_shift_frames hands its kernel (the same host loop: fp64 angle, fp64 cos / sin, one rounding to
+ * fp32), the identity (1, 0) for j >= nf.  A host function; cs: 2 * OMH_ROPE_SHIFT_MAX_PAIRS floats of host memory.
+ * OMH_E_BADARG: cs null, head_dim < 1, theta <= 0; OMH_E_SHAPE: head_dim % 8, nf > OMH_ROPE_SHIFT_MAX_PAIRS. */
+int omh_rope_shift_table(int64_t delta_frames, int32_t head_dim, double theta, float* cs);
+
+/* Additive to ABI v12: `copies` rotated images of the same rows in one launch — the fan-out of teacher forcing under a
+ * pinned sink (WanModel.forward_teacher_forcing(pin_sink=True)), whose query chunk I sees the sink keys rotated by its own
+ * delta_I: every such image is a further range of rows of the key axis.
+ * src: bf16 [B, rows, dim] as in omh_rope_shift_frames.  dst: image c of batch entry b starts at element
+ * b * dst_batch_stride + c * dst_copy_stride and has contiguous rows (in the model: row ranges of the extended K buffer).
+ * tables: DEVICE fp32 [copies, OMH_ROPE_SHIFT_MAX_PAIRS, 2], row c as omh_rope_shift_table(delta_c) writes it (device
+ * memory: many deltas do not fit the kernel-argument segment).  The copy index is a grid dimension.  Per vector the
+ * arithmetic is omh_rope_shift_frames' (fp32 multiply-adds, one RNE rounding, a pair under (1, 0) keeps its bits), so image
+ * c has the bits of omh_rope_shift_frames(src, ., delta_c).  One 16-byte vector per lane, no LDS, no scratch, plain
+ * vector loads and stores.
+ * OMH_E_BADARG: a null pointer, B, rows, dim, head_dim, copies < 1, a copy stride below rows * dim, a batch stride below
+ * the rows it spans, src and dst that overlap (row ranges of ONE buffer with one batch stride are told apart per batch
+ * entry); OMH_E_SHAPE: as omh_rope_shift_frames, copies > 65535; OMH_E_ALIGN: a pointer (tables too) not 16-byte aligned,
+ * a stride % 8 != 0. */
+int omh_rope_shift_fan(const void* src, void* dst, int32_t B, int64_t rows, int32_t dim, int32_t copies,
+                       int64_t src_batch_stride, int64_t dst_batch_stride, int64_t dst_copy_stride, const float* tables,
+                       int32_t head_dim, omh_stream_t stream);
+
+/* Additive to ABI v12: the transpose of the fan-out, for the gradient of the keys —
+ *   dst[b, r] = bf16( base[b, r] + sum_c R(-delta_c) images[b, c, r] ),
+ * R(-delta) being the table's rotation with the sine negated in the kernel.  The sum runs in fp32 in ascending c and is
+ * rounded once, to nearest even; every lane owns its 16 bytes of dst (no atomics: two runs give the same bits).
+ * base, images, dst: bf16, `rows` rows of `dim` columns per batch entry, each operand with its own row pitch (base_ld,
+ * img_ld, dst_ld >= dim: column blocks of wider buffers) and batch stride; image c of batch entry b starts at element
+ * b * img_batch_stride + c * img_copy_stride.  tables: as in omh_rope_shift_fan, or NULL: the plain sum (the gradient of V,
+ * which has no rotary position).  dst may BE base (same pointer, pitch and batch stride); otherwise dst may overlap neither.
+ * One 16-byte vector per lane, no LDS, no scratch, plain vector loads and stores.
+ * Errors as omh_rope_shift_fan (a row pitch below dim: OMH_E_BADARG; every pitch and stride % 8: OMH_E_ALIGN). */
+int omh_rope_shift_fold(const void* base, const void* images, void* dst, int32_t B, int64_t rows, int32_t dim, int32_t copies,
+                        int64_t base_ld, int64_t base_batch_stride, int64_t img_ld, int64_t img_batch_stride,
+                        int64_t img_copy_stride, int64_t dst_ld, int64_t dst_batch_stride, const float* tables, int32_t head_dim,
+                        omh_stream_t stream);
 
 /* ----------------------------------------------------------------------
  * ABI v11.  Measurement, not product: TFLOP/s this GPU sustains on back-to-back

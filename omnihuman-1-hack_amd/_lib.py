@@ -331,6 +331,9 @@ _SIGS = {
     "omh_dmd_grad_workspace_bytes": (i64, [i32, i64]),
     "omh_dmd_grad_scale": (i32, [vp, vp, f32, i64, vp, vp]),
     "omh_rope_shift_frames": (i32, [vp, vp, i32, i64, i32, i64, i64, i64, i32, C.c_double, vp]),
+    "omh_rope_shift_table": (i32, [i64, i32, C.c_double, vp]),
+    "omh_rope_shift_fan": (i32, [vp, vp, i32, i64, i32, i32, i64, i64, i64, vp, i32, vp]),
+    "omh_rope_shift_fold": (i32, [vp, vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, i64, i64, i64, vp, i32, vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

@@ -20,7 +20,9 @@ says which key groups a query group sees.  ``IntervalMask`` holds such a matrix 
 An attention sink plus a window (``WanModel.set_causal_chunks(fpc, W, S)``) rolls out on a ``RollingKVCache``: S sink slots
 and a ring of W + 1, so the cache's size does not depend on the clip's length.  ``RollingKVCache(pin_sink=True)`` also
 keeps the sink at a fixed rotary distance behind the window (include/omh.h, ``omh_rope_shift_frames``), and ``sample`` /
-``stream`` take their noise chunk by chunk: a rollout without an end.
+``stream`` take their noise chunk by chunk: a rollout without an end.  ``forcing_loss(pin_sink=True)`` /
+``WanModel.forward_teacher_forcing(pin_sink=True)`` train under that geometry: ``teacher_forcing_groups(pin_sink=True)``
+is the mask over the key axis extended by the rotated sink copies of ``sink_copy_deltas``.
 
 Self forcing trains the student on its own rollouts: ``self_forcing_rollout`` returns clips attached to a graph,
 ``dmd_loss`` puts the distribution-matching objective on them (a frozen teacher and a trainable critic score the noised
@@ -33,7 +35,7 @@ import itertools
 import torch
 
 __all__ = ["chunk_causal_visible", "KVCache", "RollingKVCache", "sample", "stream", "StreamChunk", "IntervalMask", "interval_visible",
-           "teacher_forcing_groups", "condition_window_visible",
+           "teacher_forcing_groups", "sink_copy_deltas", "condition_window_visible",
            "sink_window_groups", "forcing_loss", "self_forcing_rollout", "dmd_sigmas", "dmd_loss", "critic_loss"]
 
 
@@ -170,13 +172,44 @@ def interval_visible(mask, Lq, Lk, qlen=None, klen=None):
     return dense & (i < qlen) & (j < klen)
 
 
-def teacher_forcing_groups(n_chunks, left_chunks=-1, sink_chunks=0):
+def sink_copy_deltas(n_chunks, left_chunks, sink_chunks, frames_per_chunk):
+    """The rotated copies of the sink keys that teacher forcing under a pinned sink appends to the key axis, in copy order:
+    the list of (chunk I, Delta_I in frames) for the chunks whose shift Delta_I = (max(S, I - W) - S) fpc is positive —
+    I = S + W + 1 ... n - 1, what ``RollingKVCache(pin_sink=True)`` holds its sink keys at when chunk I runs.  Empty when
+    the clip does not outlast the ring.  ValueError for S < 1 or W < 0 (there is no sink to pin)."""
+    n, W, S, fpc = int(n_chunks), int(left_chunks), int(sink_chunks), int(frames_per_chunk)
+    if n < 1 or S < 1 or W < 0 or fpc < 1:
+        raise ValueError(f"sink_copy_deltas: n_chunks = {n} >= 1, sink_chunks = {S} >= 1, left_chunks = {W} >= 0 and "
+                         f"frames_per_chunk = {fpc} >= 1 expected (a pinned sink needs a sink and a window)")
+    return [(I, (max(S, I - W) - S) * fpc) for I in range(S + W + 1, n)]
+
+
+def teacher_forcing_groups(n_chunks, left_chunks=-1, sink_chunks=0, pin_sink=False):
     """The teacher-forcing matrix over the sequence [n clean chunks | n noisy chunks], bool [2n, 2n]: clean row g sees
     clean j <= g (and j >= g - W when W = ``left_chunks`` >= 0); noisy row n + I sees clean j < I (and j >= I - W) and noisy
     n + I only — what ``WanModel.forward_chunk`` attends to at chunk I with ``left_chunks`` = W.  With W >= 0 and
     S = ``sink_chunks`` > 0 the first S clean chunks stay visible behind the window (j >= . - W or j < S): up to three
-    runs per row, an ``IntervalMask(runs=3)``."""
+    runs per row, an ``IntervalMask(runs=3)``.
+
+    ``pin_sink=True`` (needs S >= 1 and W >= 0: ValueError otherwise): the rectangular matrix [2n, 2n + C S] over the
+    EXTENDED key axis [clean | noisy | sink copy 0 | sink copy 1 | ...] — one copy of the S sink chunks per chunk of
+    ``sink_copy_deltas`` (C = max(0, n - S - W - 1) of them, the sink keys rotated to where the pinned rollout holds them
+    for that chunk).  The rows of such a chunk I, clean and noisy, see their own copy instead of the columns [0, S);
+    everything else is the matrix above.  At most three runs per row and two per column."""
     n, W, S = int(n_chunks), int(left_chunks), int(sink_chunks)
+    if pin_sink:
+        if S < 1 or W < 0:
+            raise ValueError(f"teacher_forcing_groups: pin_sink=True needs sink_chunks = {S} >= 1 and left_chunks = {W} >= 0 "
+                             "(there is no sink to pin)")
+        base = teacher_forcing_groups(n, W, S)
+        copies = sink_copy_deltas(n, W, S, 1)
+        vis = torch.zeros(2 * n, 2 * n + len(copies) * S, dtype=torch.bool)
+        vis[:, :2 * n] = base
+        for c, (I, _) in enumerate(copies):
+            for r in (I, n + I):
+                vis[r, 2 * n + c * S:2 * n + (c + 1) * S] = base[r, :S]
+                vis[r, :S] = False
+        return vis
     if n < 1 or S < 0:
         raise ValueError(f"teacher_forcing_groups: n_chunks = {n} >= 1 and sink_chunks = {S} >= 0 expected")
     g = torch.arange(n).view(n, 1)
@@ -650,19 +683,23 @@ def stream(model, noise, context, context_null, *, frames_per_chunk, left_chunks
                     extra_conditions, who="stream", decoder=decoder, overlap=bool(overlap), events=True)
 
 
-def forcing_loss(model, latents, noise, sigmas, timesteps, context, mode="teacher"):
+def forcing_loss(model, latents, noise, sigmas, timesteps, context, mode="teacher", pin_sink=False):
     """The flow-matching loss of a frame-causal student with one noise level per chunk.  ``latents`` / ``noise``: lists of
     [C, F, H, W] (x_0 and epsilon, every clip of one shape); ``sigmas`` / ``timesteps``: [B, F / fpc], per chunk
     (fpc = the model's ``set_causal_chunks`` frames per chunk).  x_t = (1 - sigma) x_0 + sigma epsilon per chunk, the
     target is epsilon - x_0.  ``mode="teacher"``: ``model.forward_teacher_forcing(latents, x_t, timesteps, context)`` —
     the noisy chunks attend to the CLEAN chunks before them; ``mode="diffusion"``: ``model.forward`` on x_t alone with
-    the per-frame timesteps under the staircase (diffusion forcing: they attend to the noisy ones).  Returns the mean
-    squared error over all clips (plain torch on the model's outputs)."""
+    the per-frame timesteps under the staircase (diffusion forcing: they attend to the noisy ones).
+    ``pin_sink=True`` (``mode="teacher"`` under ``set_causal_chunks(fpc, W, S)`` with S >= 1 and W >= 0: ValueError otherwise):
+    ``forward_teacher_forcing(..., pin_sink=True)`` — every chunk sees the sink where ``RollingKVCache(pin_sink=True)`` holds it
+    at rollout.  Returns the mean squared error over all clips (plain torch on the model's outputs)."""
     cc = getattr(model, "_causal_chunks", None)
     if cc is None:
         raise ValueError("forcing_loss: model.set_causal_chunks(frames_per_chunk, left_chunks) first")
     if mode not in ("teacher", "diffusion"):
         raise ValueError(f"forcing_loss: mode = {mode!r}, 'teacher' or 'diffusion' expected")
+    if pin_sink and mode != "teacher":
+        raise ValueError("forcing_loss: pin_sink=True is teacher forcing under the pinned rollout's geometry (mode='teacher')")
     fpc = cc[0]
     latents, noise = list(latents), list(noise)
     F = latents[0].shape[1] // model.patch_size[0]
@@ -675,7 +712,7 @@ def forcing_loss(model, latents, noise, sigmas, timesteps, context, mode="teache
         x_t.append((1 - s) * x0 + s * eps)
         target.append(eps - x0)
     if mode == "teacher":
-        out = model.forward_teacher_forcing(latents, x_t, timesteps, context)
+        out = model.forward_teacher_forcing(latents, x_t, timesteps, context, **({"pin_sink": True} if pin_sink else {}))
     else:
         pt, ph, pw = model.patch_size
         tokens = F * (latents[0].shape[2] // ph) * (latents[0].shape[3] // pw)

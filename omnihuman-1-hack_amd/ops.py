@@ -14,7 +14,7 @@ from ._lib import (ATTN_ALLOW_SPLIT, ATTN_SHORT_KERNEL, BIAS_M, BIAS_N, BIAS_NON
                    EPI_GELU_BWD_BF16, EPI_GELU_ERF_BF16, EPI_RESID, AttnArgs, GemmArgs, OmhError, check, lib)
 
 __all__ = ["gemm", "flash_attn", "flash_attn_func", "layernorm_modulate", "rmsnorm_rope", "cast_bf16", "patchify", "unpatchify",
-           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "flow_noise", "dmd_grad", "dmd_loss", "rope_shift_frames", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw", "cl_to_u8",
+           "dense_f32", "sinusoidal_embedding", "cfg_unipc_step", "flow_x0_step", "flow_noise", "dmd_grad", "dmd_loss", "rope_shift_frames", "rope_shift_table", "rope_shift_fan", "rope_shift_fold", "conv_cl", "rms_silu_cl", "nchw_to_cl", "cl_to_nchw", "cl_to_u8",
            "softmax_rows", "OmhError",
            "EPI_BF16", "EPI_F32", "EPI_GELU_BF16", "EPI_GELU_ERF_BF16", "EPI_RESID", "EPI_F32_ACCUM", "BIAS_NONE", "BIAS_N", "BIAS_M"]
 
@@ -795,6 +795,77 @@ def rope_shift_frames(src, dst, delta_frames, head_dim=128, theta=10000.0):
     check(lib.omh_rope_shift_frames(_p(src), _p(dst), B, rows, dim, src.stride(0) if B > 1 else rows * dim,
                                     dst.stride(0) if B > 1 else rows * dim, int(delta_frames), int(head_dim), float(theta),
                                     _stream()), "omh_rope_shift_frames")
+    return dst
+
+
+ROPE_SHIFT_MAX_PAIRS = 64                                  # == OMH_ROPE_SHIFT_MAX_PAIRS of include/omh.h
+
+
+def rope_shift_table(deltas, head_dim=128, theta=10000.0, device=None):
+    """The (cos, sin) tables of ``rope_shift_fan`` / ``rope_shift_fold``: fp32 [len(deltas), ROPE_SHIFT_MAX_PAIRS, 2], row c
+    what ``rope_shift_frames(., ., deltas[c])`` hands its kernel (omh_rope_shift_table: the same fp64 host arithmetic).
+    Built on the host; ``device``: where the result goes (None: it stays on the CPU)."""
+    deltas = [int(x) for x in deltas]
+    tab = torch.empty(len(deltas), ROPE_SHIFT_MAX_PAIRS, 2, dtype=torch.float32)
+    for c, delta in enumerate(deltas):
+        check(lib.omh_rope_shift_table(delta, int(head_dim), float(theta), tab.data_ptr() + c * tab.stride(0) * 4),
+              "omh_rope_shift_table")
+    return tab if device is None else tab.to(device)
+
+
+def _images_view(t, who):
+    assert t.dtype == torch.bfloat16 and t.dim() == 4 and t.stride(3) == 1, f"{who}: bf16 [B, copies, rows, dim] views are expected"
+
+
+def rope_shift_fan(src, dst, table, head_dim=128):
+    """``dst[:, c] = rope_shift_frames(src, ., delta_c)`` for every copy c in ONE launch (omh_rope_shift_fan), bit for bit.
+    ``src``: bf16 [B, rows, dim] with contiguous rows (its own batch stride); ``dst``: bf16 [B, copies, rows, dim], any
+    batch and copy stride, contiguous rows (``torch.as_strided`` row ranges of a larger buffer — src's own, too, as long
+    as no image meets the source rows); ``table``: ``rope_shift_table([delta_0, ...], device=src.device)``.  Returns ``dst``."""
+    _dev(src, dst, table)
+    _images_view(dst, "rope_shift_fan")
+    assert src.dtype == torch.bfloat16 and src.dim() == 3, "rope_shift_fan: bf16 [B, rows, dim] source expected"
+    B, rows, dim = src.shape
+    copies = dst.shape[1]
+    assert dst.shape == (B, copies, rows, dim), "rope_shift_fan: dst of shape [B, copies, rows, dim] expected"
+    assert src.stride(2) == 1 and src.stride(1) == dim and dst.stride(2) == dim, \
+        "rope_shift_fan: contiguous rows of dim elements are expected"
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape == (copies, ROPE_SHIFT_MAX_PAIRS, 2), \
+        f"rope_shift_fan: table fp32 [{copies}, {ROPE_SHIFT_MAX_PAIRS}, 2] expected (rope_shift_table)"
+    ext = rows * dim
+    cs = dst.stride(1) if copies > 1 else ext
+    check(lib.omh_rope_shift_fan(_p(src), _p(dst), B, rows, dim, copies, src.stride(0) if B > 1 else ext,
+                                 dst.stride(0) if B > 1 else (copies - 1) * cs + ext, cs, _p(table), int(head_dim), _stream()),
+          "omh_rope_shift_fan")
+    return dst
+
+
+def rope_shift_fold(g, dst, table, head_dim=128):
+    """The transpose of ``rope_shift_fan`` (omh_rope_shift_fold): ``g`` = (base bf16 [B, rows, dim], images bf16
+    [B, copies, rows, dim]) -> ``dst[b, r] = bf16(base[b, r] + sum_c R(-delta_c) images[b, c, r])``, the sum in fp32 in
+    ascending c, one rounding, the same bits on every run.  Every operand may be a strided view (column blocks / row ranges
+    of wider buffers: last stride 1, every other a multiple of 8).  ``table``: as in ``rope_shift_fan``; None: the plain sum
+    (V has no rotary position).  ``dst``: None (a fresh tensor), ``base`` itself (in place), or rows apart from both.
+    Returns ``dst``."""
+    base, images = g
+    if dst is None:
+        dst = torch.empty(base.shape, dtype=base.dtype, device=base.device)
+    _dev(base, images, dst, table)
+    _images_view(images, "rope_shift_fold")
+    B, copies, rows, dim = images.shape
+    for t in (base, dst):
+        assert t.dtype == torch.bfloat16 and t.shape == (B, rows, dim) and t.stride(2) == 1, \
+            "rope_shift_fold: base and dst bf16 [B, rows, dim] with unit column stride are expected"
+    if table is not None:
+        assert table.dtype == torch.float32 and table.is_contiguous() and table.shape == (copies, ROPE_SHIFT_MAX_PAIRS, 2), \
+            f"rope_shift_fold: table fp32 [{copies}, {ROPE_SHIFT_MAX_PAIRS}, 2] expected (rope_shift_table)"
+    ld = lambda t, i: t.stride(i) if rows > 1 else dim
+    bs = lambda t, ext: t.stride(0) if B > 1 else ext
+    b_ext, i_ext, d_ext = ((rows - 1) * ld(t, i) + dim for t, i in ((base, 1), (images, 2), (dst, 1)))
+    cs = images.stride(1) if copies > 1 else i_ext
+    check(lib.omh_rope_shift_fold(_p(base), _p(images), _p(dst), B, rows, dim, copies, ld(base, 1), bs(base, b_ext),
+                                  ld(images, 2), bs(images, (copies - 1) * cs + i_ext), cs, ld(dst, 1), bs(dst, d_ext),
+                                  _p(table), int(head_dim), _stream()), "omh_rope_shift_fold")
     return dst
 
 

@@ -191,12 +191,16 @@ class _FwdCtx:
                  # under (frame-aligned condition tokens: WanModel._condition_mask), else None
                  "grids", "ctx_mask",
                  # bounds: where the self-attention calls of this forward take their zeroed score-bound buffers from
-                 "bounds")
+                 "bounds",
+                 # sink_fan: forward_teacher_forcing(pin_sink=True) on a clip that outlasts the ring — (device table of
+                 # ops.rope_shift_table, copies, sink rows): every self-attention appends that many rotated images of its
+                 # sink keys (and copies of their V^T columns) to the key axis; else None
+                 "sink_fan")
 
     def __init__(self):
         self.kv = self.chunk = self.cache = self.cache_layer = self.cache_lo = self.rpb = self.interval = None
         self.cache_pos = self.cache_hi = self.cache_mask = None
-        self.grids = self.ctx_mask = None
+        self.grids = self.ctx_mask = self.sink_fan = None
         self.bounds = _BoundPool()
 
 
@@ -387,8 +391,9 @@ class WanSelfAttention(nn.Module):
                              "block policy and a bounded window_size")
         if policy is not None and chosen is None:
             return None
+        ext = 0 if fc.sink_fan is None else fc.sink_fan[1] * fc.sink_fan[2]        # (rotated sink copies behind the sequence)
         return ops.attn_mask(window, bm if chosen is None else chosen, fc.chunk, fc.interval, H=self.num_heads, Lq=fc.S,
-                             Lk=fc.S, device=device)
+                             Lk=fc.S + ext, device=device)
 
     # packed weights ---------------------------------------------------------
     def _w_qk(self):
@@ -438,21 +443,27 @@ class WanSelfAttention(nn.Module):
         ``flags``: ops.flash_attn_raw's (the training node pins the short-sequence kernel); ``vt_alloc``: where V^T comes
         from; ``mask``: the resolved mask of an earlier call on the same input (a checkpoint re-run), else resolved here.
         The one-launch q | k | v product and the bounded long-sequence stream need ``flags == 0`` and no ``extras``.
-        Returns o; with ``extras`` (o, qk, q, k, vt, mask, lse, o32) — what the backward reads."""
+        ``fc.sink_fan`` (teacher forcing under a pinned sink): k and V^T get ``copies * sink_rows`` more rows / columns per
+        sample behind the S of the sequence; the norm + RoPE kernel and the V^T product write the first S as ever (only
+        pitches change, k one launch per sample), ``ops.rope_shift_fan`` fills the k rows with the rotated sink keys, one
+        device copy the V^T columns, and the attention runs with Lk = S + copies * sink_rows under the extended mask.
+        Returns o; with ``extras`` (o, qk, q, k, vt, mask, lse, o32) — what the backward reads (k: [B * Lk, dim])."""
         if fc.cache is not None:
             return self._attend_cached(h, fc, W, extras)
         B, S, d, N, D = fc.B, fc.S, self.dim, self.num_heads, self.head_dim
         R = B * S
+        fan = fc.sink_fan
+        Lk = S if fan is None else S + fan[1] * fan[2]
         if mask is None:
             mask = self._call_mask(fc, h.device)           # None: a block policy, which chooses below
         # q|k projection kept in bf16 (fp32 accumulate): the normalisation statistics are taken in fp32 from
         # it; measured effect on the 30-layer output < 1e-3 relative RMS, and it halves this step's traffic
         qk = torch.empty(R, 2 * d, dtype=torch.bfloat16, device=h.device)
-        Sp = _round_up(S, 64)
+        Sp = _round_up(Lk, 64)
         fused = W.wqkv is not None and flags == 0 and not extras          # (see _takes_fused)
         assert fused or W.wqk is not None, "a q | k | v record serves only a call without flags and extras"
         if fused:
-            vt = vt_alloc(B, d, Sp, S, h.device)           # (pad columns zero; the GEMM writes the rest)
+            vt = vt_alloc(B, d, Sp, Lk, h.device)          # (pad columns zero; the GEMM writes the rest)
             for b in range(B):                         # one launch per clip: V^T is [B, dim, Sp], a clip's rows fill the chip
                 ops.gemm_raw(ptr(h, b * S * d), ptr(W.wqkv), ptr(qk, b * S * 2 * d), S, 3 * d, d, d, d, 2 * d,
                              EPI_BF16_SPLIT_T, bias=ptr(W.bqkv), bias_mode=BIAS_N, aux=ptr(vt, b * d * Sp), ldaux=Sp,
@@ -461,7 +472,7 @@ class WanSelfAttention(nn.Module):
             ops.gemm_raw(ptr(h), ptr(W.wqk), ptr(qk), R, 2 * d, d, d, d, 2 * d, EPI_BF16, bias=ptr(W.bqk),
                          bias_mode=BIAS_N)
         q = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
-        k = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
+        k = torch.empty(B * Lk, d, dtype=torch.bfloat16, device=h.device)
         # q leaves the norm kernel already multiplied by softmax_scale * log2(e) (attention.py:96-127), in fp32
         # before its one rounding to bf16: the attention kernel's exponentials then need no per-score multiply
         q_scale = D ** -0.5 * LOG2E
@@ -480,24 +491,36 @@ class WanSelfAttention(nn.Module):
                      fc.rope_cos.shape[0], D, ptr(fc.grid32), S)
         if nmax is not None:
             ops.rmsnorm_rope_bf16_pair_bound_raw(*norm_args, ptr(nmax), out_scale0=q_scale, out_scale1=1.0)
-        else:
+        elif fan is None or B == 1:
             ops.rmsnorm_rope_bf16_pair_raw(*norm_args, out_scale0=q_scale, out_scale1=1.0)
+        else:
+            for b in range(B):                             # a sample's k rows start Lk rows behind the last one's
+                ops.rmsnorm_rope_bf16_pair_raw(ptr(qk, b * S * 2 * d), 2 * d, d, ptr(q, b * S * d), ptr(k, b * Lk * d), S, d,
+                                               *norm_args[7:15], ptr(fc.grid32, 3 * b), S, out_scale0=q_scale, out_scale1=1.0)
+        if fan is not None:
+            # the sink keys as the pinned rollout holds them for every later chunk: image c = rows [S + c sr, S + (c + 1) sr)
+            tab, copies, sr = fan
+            ops.rope_shift_fan(k.view(B, Lk, d)[:, :sr], torch.as_strided(k, (B, copies, sr, d), (Lk * d, sr * d, d, 1), S * d),
+                               tab, D)
         if not extras:
             del qk
         if mask is None:                               # the mask is chosen from the q and k this call attends with
             mask = self._call_mask(fc, h.device, self._dynamic_mask(q, k, B, S, fc.seq_lens32))
         if not fused:
             # V^T[b] = Wv h_b^T + bv  ->  [B, dim, Sp]   (pad columns stay zero)
-            vt = vt_alloc(B, d, Sp, S, h.device)
+            vt = vt_alloc(B, d, Sp, Lk, h.device)
             ops.gemm_raw(ptr(W.wv), ptr(h), ptr(vt), d, S, d, d, d, Sp, EPI_BF16, bias=ptr(W.bv), bias_mode=BIAS_M,
                          batch=B,
                          strideA=0, strideB=S * d, strideC=d * Sp)
+        if fan is not None:                            # V has no rotary position: the copies' columns are the sink's
+            vt[:, :, S:Lk].unflatten(2, (fan[1], fan[2])).copy_(vt[:, :, None, :fan[2]].expand(-1, -1, fan[1], -1))
         o = torch.empty(R, d, dtype=torch.bfloat16, device=h.device)
         lse = torch.empty(B, N, S, dtype=torch.float32, device=h.device) if lse else None
         o32 = torch.empty(R, d, dtype=torch.float32, device=h.device) if o32 else None
         # window_size: flash-attn's bottom-right aligned band (model.py:151-156); a bounded one takes the short kernel
-        ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32), B, N, S, S, S * d, d, S * d, d,
-                           d * Sp, S * d, d, Sp, D ** -0.5, lse=ptr(lse) if lse is not None else None, q_prescaled=1,
+        # (under a sink fan-out every clip fills the sequence — forward_teacher_forcing — and every key row is live)
+        ops.flash_attn_raw(ptr(q), ptr(k), ptr(vt), ptr(o), ptr(fc.seq_lens32) if fan is None else None, B, N, S, Lk, S * d, d,
+                           Lk * d, d, d * Sp, S * d, d, Sp, D ** -0.5, lse=ptr(lse) if lse is not None else None, q_prescaled=1,
                            o32=ptr(o32) if o32 is not None else None, flags=flags,
                            qk_norm2_max=ptr(nmax) if nmax is not None else None, mask=mask)
         return (o, qk, q, k, vt, mask, lse, o32) if extras else o
@@ -1172,7 +1195,7 @@ class WanModel(nn.Module):
         return hit
 
     def forward_teacher_forcing(self, x_clean, x_noisy, t, context, context_t=0.0, clip_fea=None, y=None,
-                                extra_conditions=None):
+                                extra_conditions=None, pin_sink=False):
         """All chunks of a clip in one pass, as the rollout sees them (teacher forcing).  Needs ``set_causal_chunks(fpc,
         W)``.  ``x_clean`` / ``x_noisy``: lists of [C_in, F, H, W], every clip of one shape, F a multiple of fpc;
         ``t``: [B, F / fpc], one timestep per noisy chunk.  The sequence of a sample is [clean tokens | noisy tokens]
@@ -1185,12 +1208,22 @@ class WanModel(nn.Module):
         (frame-aligned ``extra_conditions``: clean frame f and noisy frame f see the same tokens),
         ``y`` goes to both halves, the head runs on the noisy rows only.  Returns the list of fp32 [C_out, F, H, W] for the
         noisy half.
+        ``pin_sink=True`` (needs S >= 1 and W >= 0): the rollout is the one on ``causal.RollingKVCache(pin_sink=True)`` — the
+        queries of chunk I > S + W, clean and noisy, score the clean sink chunks with the sink keys rotated by
+        Delta_I = (I - W - S) fpc more frames, where the pinned cache holds them when chunk I runs.  Every such chunk gets
+        its own rotated image of the sink keys behind the 2 S tokens of the key axis (``causal.sink_copy_deltas``,
+        ``ops.rope_shift_fan``: the bits the cache holds), the mask is ``teacher_forcing_groups(.., pin_sink=True)``, and the
+        backward folds the images' dK / dV into the sink rows (``ops.rope_shift_fold``); K and V of a layer grow by
+        (n - S - W - 1) S chunks.  A clip that does not outlast the ring (n <= S + W + 1) runs the call without it, bit for bit.
         ValueError without causal chunks, for a bounded ``window_size``, a block mask or policy, clips of different
-        shapes, F no multiple of fpc, h w no multiple of 8 and a ``t`` of another shape."""
+        shapes, F no multiple of fpc, h w no multiple of 8, a ``t`` of another shape and ``pin_sink`` without a sink."""
         cc = getattr(self, "_causal_chunks", None)
         if cc is None:
             raise ValueError("forward_teacher_forcing: set_causal_chunks(frames_per_chunk, left_chunks) first")
         self._causal_check("forward_teacher_forcing")
+        if pin_sink and (self._causal_sink() < 1 or cc[1] < 0):
+            raise ValueError("forward_teacher_forcing: pin_sink=True needs set_causal_chunks(fpc, W, S) with sink_chunks >= 1 "
+                             "and left_chunks >= 0 (there is no sink to pin)")
         x_clean, x_noisy = list(x_clean), list(x_noisy)
         shapes = {tuple(u.shape) for u in x_clean} | {tuple(u.shape) for u in x_noisy}
         if len(x_clean) != len(x_noisy) or len(shapes) != 1:
@@ -1212,9 +1245,11 @@ class WanModel(nn.Module):
                                "model to a GPU device")
         from ... import causal as _causal
         sink = self._causal_sink()
+        # pin_sink: the chunks past the ring, each with the shift its sink keys carry at rollout (none: today's call)
+        copies = _causal.sink_copy_deltas(F // fpc, cc[1], sink, fpc) if pin_sink else ()
         key = (F // fpc, cc[1], fpc * h * w, str(device)) + ((sink,) if sink else ())
         masks = self.__dict__.setdefault("_tf_masks", {})
-        if key not in masks:
+        if key not in masks and not copies:
             if len(masks) > 64:
                 masks.clear()
             if sink:                                       # clean sink | clean window | own chunk: three runs
@@ -1230,7 +1265,22 @@ class WanModel(nn.Module):
             t = t.float()
         t_frames = torch.cat([torch.full((B, F), float(context_t), dtype=t.dtype, device=device),
                               t.repeat_interleave(fpc, dim=1)], dim=1)
-        self._tf_state = (masks[key], self._rope_repeated(device, F))
+        fan = None
+        if copies:
+            # the extended key axis [clean | noisy | sink @ Delta_{S+W+1} | ...]: its mask and the copies' (cos, sin) tables
+            n, Ct = F // fpc, fpc * h * w
+            key = ("pin", n, cc[1], sink, fpc, Ct, str(device))
+            if key not in masks:
+                if len(masks) > 64:
+                    masks.clear()
+                masks[key] = (_causal.IntervalMask(_causal.teacher_forcing_groups(n, cc[1], sink, pin_sink=True), Ct, device,
+                                                   runs=3),
+                              ops.rope_shift_table([delta for _, delta in copies], self.dim // self.num_heads, device=device))
+            mask, table = masks[key]
+            fan = (table, len(copies), sink * Ct)
+        else:
+            mask = masks[key]
+        self._tf_state = (mask, self._rope_repeated(device, F), fan)
         try:
             out = self.forward(x, t_frames, context, 2 * F * h * w, clip_fea, y, extra_conditions)
         finally:
@@ -1287,8 +1337,9 @@ class WanModel(nn.Module):
             # (the refusals come before anything touches a device)
             if getattr(cache, "pin_sink", False):
                 raise ValueError("forward_chunk(grad=True): a cache with pin_sink=True re-rotates its sink rows for later "
-                                 "chunks, and the backward reads cached rows in place; training under a pinned sink is "
-                                 "not provided")
+                                 "chunks, and the backward reads cached rows in place; self forcing under a pinned sink is "
+                                 "what is still missing (teacher forcing trains under it: "
+                                 "forward_teacher_forcing(pin_sink=True))")
             if getattr(cache, "rolling", False):
                 raise ValueError("forward_chunk(grad=True): a RollingKVCache evicts slots the backward still reads; use a "
                                  "causal.KVCache with set_causal_chunks(frames_per_chunk, left_chunks)")
@@ -1588,6 +1639,7 @@ class WanModel(nn.Module):
         if tf is not None:
             fc.chunk, fc.interval = None, tf[0]
             fc.rope_cos, fc.rope_sin = tf[1]
+            fc.sink_fan = tf[2]                                             # (pin_sink=True past the ring; else None)
         ctx_lens = self._attach_context(fc, context, clip_fea, extra_conditions, chunk)
         return xs, e, fc, grids, lens, ctx_lens
 

@@ -1057,6 +1057,23 @@ def _block_backward(model, blk, idx, st, S, dx, P, tgt=None, slots=None):
         _attn_bwd(q, kf, vf, o, do, S["lse_sa"], None, B, N, Sq, past + Sq, D ** -0.5,
                   (dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]), S["o32_sa"], True, own_lo=past)
         del kf, vf
+    elif fc.sink_fan is not None:
+        # teacher forcing under a pinned sink: the key axis carries `copies` rotated images of the `sr` sink rows behind the
+        # sequence (WanSelfAttention._attend).  dK | dV of all Lk rows go to scratch; the rows of the sequence move to dqkv,
+        # where the sink rows get base + the images' sums — dK with every image rotated back, dV plainly (ops.rope_shift_fold:
+        # fp32 sums in copy order, one rounding, no atomics — the same bits on a checkpoint re-run)
+        tab, copies, sr = fc.sink_fan
+        Lk = Sq + copies * sr
+        v = ops.transpose_bf16_batched(S["vt"], Lk)                   # [B*Lk, d]
+        dkv = bf(B * Lk, 2 * d)
+        _attn_bwd(q, k, v, o, do, S["lse_sa"], None, B, N, Sq, Lk, D ** -0.5, (dqkv[:, :d], dkv[:, :d], dkv[:, d:]),
+                  S["o32_sa"], True, S["mask"])
+        g3, d3 = dkv.view(B, Lk, 2 * d), dqkv.view(B, Sq, 3 * d)
+        d3[:, sr:, d:].copy_(g3[:, sr:Sq])
+        image = lambda c0: torch.as_strided(dkv, (B, copies, sr, d), (Lk * 2 * d, sr * 2 * d, 2 * d, 1), Sq * 2 * d + c0)
+        ops.rope_shift_fold((g3[:, :sr, :d], image(0)), d3[:, :sr, d:2 * d], tab, D)
+        ops.rope_shift_fold((g3[:, :sr, d:], image(d)), d3[:, :sr, 2 * d:], None, D)
+        del v, dkv
     else:
         v = ops.transpose_bf16_batched(S["vt"], Sq)                   # [B*S, d]
         _attn_bwd(q, k, v, o, do, S["lse_sa"], fc.seq_lens32, B, N, Sq, Sq, D ** -0.5,
