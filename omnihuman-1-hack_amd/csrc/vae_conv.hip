@@ -725,6 +725,9 @@ static ConvRoute conv_route(const omh_conv_args& a) {
     const bool w64_ok = !(w64e && w64e[0] == '0') && (w64_forced || (!force && wide));
     const bool w64 = w64_ok && omh_conv_w64_takes(a);
     if (w64_forced) wide = true;                                      // not taken: the wide kernels
+    // ... whose epilogue reads the residual in 16-byte vectors: forcing the stream must not undo the alignment fallback
+    // above (tests/test_gpu_conv_exact.py: the fallbacks)
+    if (((uintptr_t)a.resid & 15) || ((uintptr_t)a.bias & 3)) wide = false;
     return {wide, w64};
 }
 

@@ -276,7 +276,8 @@ def test_conv_cl_w64_folded_upsample(ops, Cin, Cout, T, H, W, monkeypatch):
     ref = torch.nn.functional.conv2d(torch.nn.functional.interpolate(xi, scale_factor=2.0, mode="nearest-exact"), w.float(),
                                      bias, padding=1).permute(0, 2, 3, 1)
     assert out["w64"].shape == ref.shape
-    assert rel_rms(out["w64"], ref) < 2e-3 and rel_rms(out["wide"], ref) < 2e-3
+    # (2e-3 until tests/test_gpu_conv_exact.py held the folded upsample exactly on the stream, the wide and the 128 x 128 kernels)
+    assert rel_rms(out["w64"], ref) < 2e-5 and rel_rms(out["wide"], ref) < 2e-5
     assert rel_rms(out["w64"], out["wide"]) < 1e-5
 
 
