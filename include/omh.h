@@ -926,7 +926,9 @@ typedef struct omh_colsum_batch {
     int32_t C[OMH_COLSUM_MAX]; int32_t is_bf16[OMH_COLSUM_MAX]; int32_t blocks[OMH_COLSUM_MAX];
 } omh_colsum_batch;
 int omh_colsum_accum_multi(const omh_colsum_batch* batch, omh_stream_t stream);
-/* GELU-tanh on bf16 (model.py:273) and its backward dx = dy * gelu'(x_pre). */
+/* GELU-tanh on bf16 (model.py:273) and its backward dx = dy * gelu'(x_pre).  Domain of the backward: |x_pre| < 1.168e13;
+ * beyond, the polynomial factor x 2c (1 + 3 a x^2) overflows fp32 against a sigmoid factor of exactly 0 and the entry
+ * returns NaN where the derivative is 1 or 0 (10 838 bf16 values of each sign; the GEMM epilogue shares the function). */
 int omh_gelu_tanh_bf16(const void* x, void* y, int64_t n, omh_stream_t stream);
 int omh_gelu_tanh_bwd_bf16(const void* dy, const void* x_pre, void* dx, int64_t n, omh_stream_t stream);
 
@@ -1035,7 +1037,8 @@ int omh_patchify_bwd(const float* dtok, int64_t ld, float* out0, float* out1, in
 int omh_sinusoidal_embedding_bwd(const float* dsin, const float* t, float* dt, int32_t B, int32_t dim,
                                  omh_stream_t stream);
 /* Backward of omh_dense_f32 (act_out must have been 0): dW += dy^T act(x), db += sum_b dy,
- * dx (=|+=) (dy W) * act'(x).  dW_accum / dx may be NULL. */
+ * dx (=|+=) (dy W) * act'(x).  dW_accum / dx may be NULL.  db_accum is summed by the launch that forms dW: it may be
+ * NULL, and it must be NULL when dW_accum is (OMH_E_BADARG otherwise: it would silently keep its old values). */
 int omh_dense_f32_bwd(const float* x, const float* W, const float* dy, float* dW_accum, float* db_accum,
                       float* dx, int32_t dx_accumulate, int32_t B, int32_t N, int32_t K, int32_t act_in,
                       omh_stream_t stream);

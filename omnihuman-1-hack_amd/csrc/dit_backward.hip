@@ -955,6 +955,7 @@ extern "C" int omh_dense_f32_bwd(const float* x, const float* W, const float* dy
                                  float* dx, int32_t dx_accumulate, int32_t B, int32_t N, int32_t K, int32_t act_in,
                                  omh_stream_t stream) {
     if (!x || !W || !dy || B <= 0 || N <= 0 || K <= 0) return OMH_E_BADARG;
+    if (db_accum && !dW_accum) return OMH_E_BADARG;                  // db is summed by the dW launch: it would stay as it was
     omh_clear_status();
     if (dW_accum)
         hipLaunchKernelGGL(dense_f32_bwd_w_kernel, dim3((unsigned)(((int64_t)N * K + 255) / 256)), dim3(256), 0,
